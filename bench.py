@@ -18,6 +18,12 @@ The other BASELINE configs are parity-test cases, not the bench line; they can s
     --workload ragged     configs[2]: 256 utterances of 200-1000 frames, padded + lengths mask
     --workload job        configs[3]: 100 000 utterances, sharded over the ranks, one all-gather (strong scaling)
     --dtype bf16          configs[4]
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else the benchmark measures -- the
+PCIe-inclusive and graph-replay rates, per-kernel times and the roofline, the secondary legs of the default line (other
+precisions, ragged, waveforms, PLDA scoring, the 100 000-utterance job) and the CPU baseline -- runs with --full only.
+--dump-outputs DIR writes what the last timed step returned (DIR/embeddings.npy) so that two builds can be compared
+output for output: the inputs are seeded and the same from run to run.
 """
 import argparse
 import datetime
@@ -73,6 +79,26 @@ def traffic_key(dtype, pp16):
 
 def total_flops(T):
     return sum(layer_flops(T)) + 2 * 3000 * 512
+
+
+DUMP_BYTES = 60_000_000     # --dump-outputs writes at most 64 MB in all: 60 MB of data plus the .npy headers
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_BYTES):
+    """--dump-outputs: every array as <dirname>/<name>.npy, float64 kept, anything else as float32.  An array larger than
+    its share of `limit` is cut to a fixed sample of its rows (numpy default_rng(0), in ascending order), the same in every
+    run, so that two builds compare row for row."""
+    os.makedirs(dirname, exist_ok=True)
+    share = limit // len(arrays)
+    for name, a in arrays.items():
+        a = a.detach()
+        if a.dtype != torch.float64:
+            a = a.float()
+        if a.numel() * a.element_size() > share:
+            n = share // (a[0].numel() * a.element_size())
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))
+            a = a[torch.from_numpy(rows).to(a.device)]
+        np.save(os.path.join(dirname, f"{name}.npy"), a.cpu().numpy())
 
 
 def self_launch(n, argv, port=0):
@@ -185,15 +211,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: PCIe-inclusive and graph-replay rates, per-kernel "
+                         "times and the roofline, the secondary legs of the default line, the CPU baseline.  Off: set up, "
+                         "warm up, time the K steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the last one returned as DIR/<name>.npy (float32, at most "
+                         "64 MB: a fixed seeded sample of rows of a larger output)")
     ap.add_argument("--cpu-budget", type=float, default=40.0,
-                    help="seconds of CPU-baseline work over its four legs (B=1/64 x all cores/1 thread; 0 = skip)")
+                    help="(--full) seconds of CPU-baseline work over its four legs (B=1/64 x all cores/1 thread; 0 = skip)")
     ap.add_argument("--preroll", type=float, default=0.5,
                     help="seconds the path runs UNTIMED before the W warm-up steps, so that the GPU has left its idle "
                          "power state when the clock starts: the driver's 5+20 steps are 10-70 ms of work, shorter than "
                          "the ramp (same kernels, bf16: 540 k embeddings/s after 5 warm-up steps, 619 k after 1000; "
                          "fp32 +0.9 %).  0 = off.  The timed region is unchanged: exactly K steps between barriers")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs of the default line (configs[4] bf16 and configs[2] ragged figures)")
+                    help="(--full) skip the secondary legs of the default line (configs[4] bf16 and configs[2] ragged figures)")
     ap.add_argument("--force-collective", action="store_true",
                     help="initialise the RCCL process group and run the all-gather leg even with one rank "
                          "(one-GPU rehearsal of the N>1 code path)")
@@ -345,6 +378,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     attr = attribution(marks, collective, world)
+    if args.dump_outputs and rank == 0:
+        last = full if n_local is not None else emb[(K - 1) * B:K * B] if emb is not None else kept[(K - 1) & 3]
+        dump_outputs(args.dump_outputs, {"embeddings": last})
 
     # ---- single-GPU extras, reported beside the headline and never as `value`.  Skipped for N>1 (they
     # are per-GPU figures, and a graph capture beside a live RCCL communicator is not worth risking
@@ -390,7 +426,7 @@ def main():
             torch.cuda.synchronize(dev)
             dt_graph = time.perf_counter() - t3
 
-    if world == 1 and not args.force_collective:
+    if args.full and world == 1 and not args.force_collective:
         try:
             extras()
         except Exception as e:      # noqa: BLE001
@@ -410,7 +446,7 @@ def main():
         mdl.set_profiling(False, dev)
         return {n: acc[n] / n_iter for n in names}
 
-    avg_ms = per_kernel_ms(model, x, lengths, min(K, 50))
+    avg_ms = per_kernel_ms(model, x, lengths, min(K, 50)) if args.full else None
 
     # ---- secondary legs of the default line (never `value`): the other single-GPU BASELINE configs measured
     # in the same driver run -- configs[4] (the same batch in bf16) and configs[2] (ragged 200-1000 frames)
@@ -583,7 +619,7 @@ def main():
         assert full.shape == (n_job, 512)
         secondary["job100k_bf16_embeddings_per_s"] = round(n_job / (time.perf_counter() - t_j), 1)
 
-    if (world == 1 and not args.force_collective and not args.no_secondary and args.workload == "fixed"
+    if (args.full and world == 1 and not args.force_collective and not args.no_secondary and args.workload == "fixed"
             and args.dtype == "fp32"):
         for leg in (secondary_legs, next_row_legs, job_leg):
             try:
@@ -605,38 +641,7 @@ def main():
             frames_done = world * K * sum(lengths)
             path_flops = (sum(lf) + B * 2 * 3000 * 512) / B
             path_bytes = BYTES_PER_UTT * (sum(lengths) / B) / 300.0 * act_bytes_scale
-        tdnn_names = names[:5]
-        tdnn_ms = sum(avg_ms[n] for n in tdnn_names)
-        # dominant kernel: the plain tdnn_f32_kernel instance (layers 2-4 launch the same code object)
-        dom_ms = (avg_ms["tdnn2"] + avg_ms["tdnn3"] + avg_ms["tdnn4"]) / 3
-        dom_flops = (lf[1] + lf[2] + lf[3]) / 3
-        achieved = dom_flops / (dom_ms * 1e-3) / 1e12
-        bf = args.dtype in ("bf16", "bf16x3")
-        # bf16x3 spends three bf16 MFMAs per algorithmic product: its roof is a third of the bf16 peak
-        peak = {"fp32": FP32_MFMA_PEAK, "bf16": BF16_MFMA_PEAK, "bf16x3": BF16_MFMA_PEAK / 3}[args.dtype]
-        # which kernel layers 2-4 actually went to, as the library reports it (xvec_get_dispatch): bf16 at this batch
-        # and bf16x3 at this batch size run the 256-channel ping-pong mapping (csrc/tdnn_pp16.hip); smaller batches, other
-        # CU counts and XVEC_PP=0 the 128x128 kernel (csrc/tdnn_layer.hip)
-        disp = model.last_dispatch(dev)
-        pp16 = disp[1:4] == ["pp", "pp", "pp"]
-        dom_kernel = (f"xvec::pp16::tdnn_pp_kernel<false, {'true' if args.dtype == 'bf16x3' else 'false'}> (layers 2-4, "
-                      "v_mfma_f32_16x16x32_bf16, LDS-DMA operands"
-                      + (", three K-tiles per 64-channel slab)" if args.dtype == "bf16x3" else ")") if pp16 else
-                      "xvec::tdnn_kernel<0,false,true,true,true,X3> (layers 2-4, bf16 MFMA"
-                      + (", three products per k-step)" if args.dtype == "bf16x3" else ")") if bf else
-                      "xvec::tdnn_kernel<0,false,true,false,false,false> (layers 2-4, fp32 MFMA)")
         value = n_done / dt
-        # HBM bytes per launch of the dominant kernel come from the committed rocprofv3 --pmc pass of
-        # this same command (profiles/traffic.json, written by profiles/summarize_pmc.py); counters
-        # cannot be collected from inside the benchmark process.
-        traffic, traffic_src, traffic_err = None, None, None
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
-            tj = tj[args.dtype]                             # one section per arithmetic
-            key = traffic_key(args.dtype, pp16)
-            traffic, traffic_src = tj[key]["hbm_bytes_per_launch"], tj["source"]
-        except (OSError, KeyError, ValueError) as e:        # said out loud: a renamed or re-tiled kernel must not report stale bytes silently
-            traffic_err = f"profiles/traffic.json has no entry for this run's dominant kernel ({type(e).__name__}: {e}); re-run profiles/run_round.sh"
         out = {
             "metric": "x-vector embeddings/sec (300-frame utt)", "value": round(value, 1), "unit": "embeddings/s",
             "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": round(dt / K * 1e3, 4),
@@ -653,15 +658,50 @@ def main():
                                    + "extract_x_vec layer 6, random-init weights seed 42",
                        "build": xa.hip.version(),
                        "batch_per_gpu": B, "frames": T, "valid_frames_per_s": round(frames_done / dt, 1),
-                       "pcie_inclusive_embeddings_per_s_per_gpu": round(K_pcie * B / dt_pcie, 1) if dt_pcie else None,
-                       "graph_replay_embeddings_per_s_per_gpu": round(K * B / dt_graph, 1) if dt_graph else None,
-                       "pcie_inclusive_overlapped_embeddings_per_s_per_gpu":
-                           round(K_pcie * B / dt_pcie_ovl, 1) if dt_pcie_ovl else None,
                        "preroll_s": args.preroll if n_local is None else 0.0,
                        "sharding": f"utterance-sharded x{world}"
                        + (", one all-gather of [K*B,512] fp32 in the timed region" if collective else ""),
-                       **attr, **secondary},
-            "roofline": {
+                       **attr},
+        }
+        if args.full:
+            out["config"].update({
+                "pcie_inclusive_embeddings_per_s_per_gpu": round(K_pcie * B / dt_pcie, 1) if dt_pcie else None,
+                "graph_replay_embeddings_per_s_per_gpu": round(K * B / dt_graph, 1) if dt_graph else None,
+                "pcie_inclusive_overlapped_embeddings_per_s_per_gpu":
+                    round(K_pcie * B / dt_pcie_ovl, 1) if dt_pcie_ovl else None,
+                **secondary})
+            tdnn_names = names[:5]
+            tdnn_ms = sum(avg_ms[n] for n in tdnn_names)
+            # dominant kernel: the plain tdnn_f32_kernel instance (layers 2-4 launch the same code object)
+            dom_ms = (avg_ms["tdnn2"] + avg_ms["tdnn3"] + avg_ms["tdnn4"]) / 3
+            dom_flops = (lf[1] + lf[2] + lf[3]) / 3
+            achieved = dom_flops / (dom_ms * 1e-3) / 1e12
+            bf = args.dtype in ("bf16", "bf16x3")
+            # bf16x3 spends three bf16 MFMAs per algorithmic product: its roof is a third of the bf16 peak
+            peak = {"fp32": FP32_MFMA_PEAK, "bf16": BF16_MFMA_PEAK, "bf16x3": BF16_MFMA_PEAK / 3}[args.dtype]
+            # which kernel layers 2-4 actually went to, as the library reports it (xvec_get_dispatch): bf16 at this batch
+            # and bf16x3 at this batch size run the 256-channel ping-pong mapping (csrc/tdnn_pp16.hip); smaller batches, other
+            # CU counts and XVEC_PP=0 the 128x128 kernel (csrc/tdnn_layer.hip)
+            disp = model.last_dispatch(dev)
+            pp16 = disp[1:4] == ["pp", "pp", "pp"]
+            dom_kernel = (f"xvec::pp16::tdnn_pp_kernel<false, {'true' if args.dtype == 'bf16x3' else 'false'}> (layers 2-4, "
+                          "v_mfma_f32_16x16x32_bf16, LDS-DMA operands"
+                          + (", three K-tiles per 64-channel slab)" if args.dtype == "bf16x3" else ")") if pp16 else
+                          "xvec::tdnn_kernel<0,false,true,true,true,X3> (layers 2-4, bf16 MFMA"
+                          + (", three products per k-step)" if args.dtype == "bf16x3" else ")") if bf else
+                          "xvec::tdnn_kernel<0,false,true,false,false,false> (layers 2-4, fp32 MFMA)")
+            # HBM bytes per launch of the dominant kernel come from the committed rocprofv3 --pmc pass of
+            # this same command (profiles/traffic.json, written by profiles/summarize_pmc.py); counters
+            # cannot be collected from inside the benchmark process.
+            traffic, traffic_src, traffic_err = None, None, None
+            try:
+                tj = json.load(open(os.path.join(ROOT, "profiles", "traffic.json")))
+                tj = tj[args.dtype]                             # one section per arithmetic
+                key = traffic_key(args.dtype, pp16)
+                traffic, traffic_src = tj[key]["hbm_bytes_per_launch"], tj["source"]
+            except (OSError, KeyError, ValueError) as e:        # said out loud: a renamed or re-tiled kernel must not report stale bytes silently
+                traffic_err = f"profiles/traffic.json has no entry for this run's dominant kernel ({type(e).__name__}: {e}); re-run profiles/run_round.sh"
+            out["roofline"] = {
                 "bound": "mfma", "kernel": dom_kernel,
                 "achieved": round(achieved, 2), "peak": peak / 1e12, "unit": "TFLOP/s",
                 "frac": round(achieved * 1e12 / peak, 4), "traffic": traffic, "traffic_source": traffic_src,
@@ -672,9 +712,8 @@ def main():
                 "tdnn_stack_tflops": round(sum(lf) / (tdnn_ms * 1e-3) / 1e12, 2),
                 "path_flop_frac_of_peak": round(value / world * path_flops / peak, 4),
                 "path_hbm_frac_algorithmic": round(value / world * path_bytes / HBM_PEAK, 4),
-            },
-        }
-        if world == 1 and args.cpu_budget > 0:
+            }
+        if args.full and world == 1 and args.cpu_budget > 0:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             import xvector_oracle as oracle
             p = {k: v for k, v in sd.items() if v.is_floating_point()}

@@ -4,7 +4,7 @@ KV=$1; shift
 for i in 1 2 3; do
   for mode in base knob; do
     if [ $mode = knob ]; then export $KV; else unset ${KV%%=*}; fi
-    python bench.py --steps 30 --warmup 5 --cpu-budget 0 --no-secondary "$@" 2>/dev/null | python -c "
+    python bench.py --full --steps 30 --warmup 5 --cpu-budget 0 --no-secondary "$@" 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 k = d['roofline']['per_kernel_ms']

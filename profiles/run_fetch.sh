@@ -8,7 +8,7 @@ mkdir -p $out
 i=0
 for grp in "FETCH_SIZE" "WRITE_SIZE"; do
   i=$((i+1))
-  rocprofv3 --pmc $grp --output-format csv -d $out/p$i -o p$i -- python3 bench.py --steps 3 --warmup 1 --cpu-budget 0 "$@" > $out/p$i.log 2>&1
+  rocprofv3 --pmc $grp --output-format csv -d $out/p$i -o p$i -- python3 bench.py --full --steps 3 --warmup 1 --cpu-budget 0 "$@" > $out/p$i.log 2>&1
   echo "pass $i ($grp): exit $?"
 done
 python3 profiles/summarize_pmc.py $out > $out/summary.txt 2>&1

@@ -12,7 +12,7 @@ for grp in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY S
            "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
   if [ -n "$PASSES" ] && ! echo " $PASSES " | grep -q " $i "; then continue; fi
-  rocprofv3 --pmc $grp --output-format csv -d $out/p$i -o p$i -- python3 bench.py --steps 3 --warmup 1 --cpu-budget 0 --dtype bf16 > $out/p$i.log 2>&1
+  rocprofv3 --pmc $grp --output-format csv -d $out/p$i -o p$i -- python3 bench.py --full --steps 3 --warmup 1 --cpu-budget 0 --dtype bf16 > $out/p$i.log 2>&1
   echo "pass $i: exit $?"
 done
 python3 profiles/summarize_pmc.py $out $out/traffic.json > $out/summary.txt 2>&1

@@ -12,7 +12,7 @@ from conftest import ROOT
 @pytest.mark.gpu
 @pytest.mark.parametrize("extra", [[], ["--dtype", "bf16"], ["--workload", "ragged"]])
 def test_bench_line(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--cpu-budget", "1"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--cpu-budget", "1"] + extra
     out = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -56,6 +56,48 @@ def test_bench_line(extra):
         assert cfg["mfcc_kernel_form"] == 2          # the reference's MFCC call runs the nfft-512 kernel with the banded filterbank
     else:
         assert "bf16_embeddings_per_s" not in cfg
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_lean_and_dumps_the_last_step(tmp_path, sd42):
+    """A plain run (no --full) times exactly --steps steps and prints the headline without the --full sections;
+    --dump-outputs writes the embeddings the last timed step returned, for the seeded input the bench documents."""
+    import numpy as np
+    import torch
+    import xvector_oracle as oracle
+    from conftest import assert_parity, float_params
+    d = _one_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1",
+                   "--dump-outputs", str(tmp_path / "out")])
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert d["unit"] == "embeddings/s" and abs(d["value"] - 256 * 4 / (d["ms_per_step"] * 4e-3)) / d["value"] < 0.01
+    assert "roofline" not in d and "cpu_baseline" not in d and "bf16_embeddings_per_s" not in d["config"]
+    assert sorted(os.listdir(tmp_path / "out")) == ["embeddings.npy"]
+    emb = np.load(tmp_path / "out" / "embeddings.npy")
+    assert emb.shape == (256, 512) and emb.dtype == np.float32
+    gen = torch.Generator(device="cuda:0").manual_seed(1000)       # bench.py's input of rank 0
+    x = torch.randn((256, 300, 24), generator=gen, device="cuda:0", dtype=torch.float32).cpu()
+    idx = [0, 255]
+    with torch.no_grad():
+        ref = oracle.extract_x_vec(x[idx], float_params(sd42))
+    assert_parity(emb[idx], ref, 1e-4, "bench --dump-outputs embeddings")
+
+
+def test_dump_outputs_caps_the_size_with_a_fixed_sample(tmp_path):
+    """bench.dump_outputs: float32 (float64 kept); an array over its share of the limit is cut to the same seeded rows in
+    every run."""
+    import numpy as np
+    import torch
+    from bench import dump_outputs
+    big = torch.arange(1000 * 8, dtype=torch.float64).reshape(1000, 8)
+    small = torch.ones((4, 3), dtype=torch.float16)
+    for run in ("a", "b"):
+        dump_outputs(str(tmp_path / run), {"big": big, "small": small}, limit=2 * 8 * 8 * 100)
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (100, 8) and np.array_equal(a, b)
+    rows = a[:, 0] / 8
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, big.numpy()[rows.astype(int)])
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (4, 3) and (s == 1).all()
 
 
 def _one_line(cmd, timeout=600):
