@@ -191,11 +191,18 @@ int xvec_get_timings(xvec_handle* h, float* ms, int* n);
  * batch size): kernels[0..4], *n = 5.  bench.py names its roofline kernel and keys profiles/traffic.json by this. */
 enum {
     XVEC_KERNEL_NONE = 0,
-    XVEC_KERNEL_TILE128 = 1, /* xvec::tdnn_kernel<...>          128x128 tiles (csrc/tdnn_layer.hip) */
+    XVEC_KERNEL_TILE128 = 1, /* persistent fp32 kernels with 128x128 output tiles: xvec::tdnn_kernel<...> (csrc/tdnn_layer.hip),
+                                and xvec::wino::tdnn_wino_kernel, fp32 3-tap layers as Winograd F(2,3) (csrc/tdnn_wino.hip) */
     XVEC_KERNEL_PP = 2,      /* xvec::pp16::tdnn_pp_kernel<POOL, X3>  256-channel LDS-DMA mapping, bf16 / bf16x3 at large batches (csrc/tdnn_pp16.hip) */
     XVEC_KERNEL_FIRST = 3    /* xvec::first::tdnn_first_kernel / first3::tdnn_first3_kernel  layer 1 of the bf16 / bf16x3 path, streaming (csrc/tdnn_first.hip) */
 };
 int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n);
+/* Which arithmetic form the LAST launch of each frame-level layer used: forms[0..4], *n = 5.  XVEC_FORM_WINOGRAD_F23: an fp32
+ * layer with three equally spaced taps (layers 2 and 3 of the reference) as Winograd F(2,3) along time -- four products for
+ * two output frames instead of six (csrc/tdnn_wino.hip); every other layer and precision is direct.  XVEC_WINOGRAD=0 in the
+ * environment at xvec_create forces the direct form. */
+enum { XVEC_FORM_DIRECT = 0, XVEC_FORM_WINOGRAD_F23 = 1 };
+int xvec_get_tdnn_form(const xvec_handle* h, int* forms, int* n);
 
 /* ---- next row N3: MFCC front end (the step in front of the path) ----------------------------
  * python_speech_features.mfcc as the reference calls it in its DataLoader workers

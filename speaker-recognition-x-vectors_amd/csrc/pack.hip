@@ -63,6 +63,32 @@ hipError_t launch_pack_tdnn(const float* W, const float* bias, const float* g, c
     return hipGetLastError();
 }
 
+// Winograd F(2,3) weights of a 3-tap layer (tdnn_wino.hip): U_0 = W_0, U_1 = (W_0+W_1+W_2)/2, U_2 = (W_0-W_1+W_2)/2, U_3 = W_2,
+// formed in fp64 and rounded once, in the kernel's K order (32-wide chunk kc of U_0, U_1, U_2, U_3, then kc+1):
+//   Wu[n][(kc*4 + k)*32 + w] = U_k[n][kc*32 + w],   n < n_pad, zero padded.
+__global__ void pack_wino_kernel(const float* __restrict__ W, TdnnGeom g, float* __restrict__ Wu) {
+    const int k_pad = 4 * g.kpt_pad;
+    const int64_t total = (int64_t)g.n_pad * k_pad;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int n = (int)(i / k_pad), kd = (int)(i % k_pad);
+        const int it = kd / kBK, w = kd % kBK;
+        const int k = it & 3, c = (it >> 2) * kBK + w;
+        double v = 0.0;
+        if (n < g.cout && c < g.src_cin) {
+            const float* row = W + (int64_t)n * (g.src_taps * g.src_cin) + c;
+            const double w0 = row[0], w1 = row[g.src_cin], w2 = row[2 * g.src_cin];
+            v = k == 0 ? w0 : k == 1 ? 0.5 * ((w0 + w1) + w2) : k == 2 ? 0.5 * ((w0 - w1) + w2) : w2;
+        }
+        Wu[i] = (float)v;
+    }
+}
+
+hipError_t launch_pack_wino(const float* W, const TdnnGeom& geo, float* Wu, hipStream_t s) {
+    if (geo.src_taps != 3) return hipErrorInvalidValue;
+    pack_wino_kernel<<<1024, 256, 0, s>>>(W, geo, Wu);
+    return hipGetLastError();
+}
+
 // Same matrix in bf16, fragment-major for v_mfma_f32_32x32x16_bf16: the 64 lanes' B operands of one
 // (32-channel column tile, 16-wide k-step) are one contiguous KiB, so a wave fetches them with a
 // single coalesced 16-byte-per-lane load and the weights never pass through LDS.

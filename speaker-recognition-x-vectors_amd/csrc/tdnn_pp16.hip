@@ -539,6 +539,11 @@ __device__ __forceinline__ float swap16_add(float x, float y) {
     const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(y), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
+// quad qs's x in every lane (qs wave-uniform)
+__device__ __forceinline__ float quad_bcast(float x, int qs) {
+    const int src = (int)((threadIdx.x & 15) + 16 * qs) << 2;
+    return __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(x)));
+}
 // quad 0's x in every lane
 __device__ __forceinline__ float quad0(float x) {
     const unsigned u = __float_as_uint(x);
@@ -557,8 +562,10 @@ __device__ __forceinline__ float quad0(float x) {
 // consecutive segments get distinct slots -- and the number of frames behind a partial goes to pool_cnt[slot]
 // (pool_finalize_seg needs it to re-base the pivots).  Every wave writes a partial, possibly of zero frames, for EVERY
 // utterance that overlaps its block's row range: pool_finalize_seg reads exactly those.
-// The pivot of a segment is frame 0 of the 32-frame group in which the segment's first rows fall (a computed row
-// of the same channel, this utterance's or its neighbour's: tdnn_common.h, pool_group_impl on why that is enough).
+// The pivot of a segment is its own first frame: a frame of the same utterance and channel.  (Frame 0 of the group, which
+// round 4 took, may be the previous utterance's: for a channel that is off in this whole utterance every r - K is then the
+// same -K != 0, and n identical terms summed in fp32 leave ~|K| sqrt(eps) of std where the answer is exactly 0 -- 1e-5 at
+// the bench batch.  With the segment's own frame K = 0 there and the sums are exact zeros.)
 struct Seg {
     f32x4 k, s1, s2;            // per lane: its four channels
 };
@@ -623,7 +630,14 @@ __device__ __forceinline__ void pool_rows(const TdnnArgs& a, f32x4& v00, f32x4& 
         const int64_t hi = sc.end < g_end ? sc.end : g_end;           // rows [lo, hi) of the group belong to sc.u
         if (hi > lo) {
             if (sc.n == 0) {                                          // the segment's first rows: take the pivots
-                sg.k = f32x4{quad0(v00[0]), quad0(v01[0]), quad0(v02[0]), quad0(v03[0])};
+                // from its first frame lo: frame 16 fs + 4 qs + es of the group (wave-uniform), held by lane quad qs
+                const int lo_l = (int)(lo - row_g), fs = lo_l >> 4, qs = (lo_l >> 2) & 3, es = lo_l & 3;
+                auto pick = [&](const f32x4& a0, const f32x4& a1) -> float {
+                    const float x0 = es == 0 ? a0[0] : es == 1 ? a0[1] : es == 2 ? a0[2] : a0[3];
+                    const float x1 = es == 0 ? a1[0] : es == 1 ? a1[1] : es == 2 ? a1[2] : a1[3];
+                    return quad_bcast(fs ? x1 : x0, qs);
+                };
+                sg.k = f32x4{pick(v00, v10), pick(v01, v11), pick(v02, v12), pick(v03, v13)};
             }
             if (hi - lo == 32 || PP_KNOCK_MASKED) {                   // the whole group: no masks
                 // plain v_sub / v_add / v_fma (v_pk_*_f32 issue at ~17 cycles each: MI355X_MICROARCH.md, price of fillers;

@@ -75,6 +75,8 @@ struct xvec_handle {
     void* Wp48[XVEC_NUM_TDNN];         // bf16x3: per chunk W_hi then W_lo fragments (2x the size), fragment-major
     void* Wr48[XVEC_NUM_TDNN];         // bf16x3, K-tile major for tdnn_pp16.hip: per K-tile W_hi | W_lo | W_hi (3x the size of Wr16)
     float* Wp[XVEC_NUM_TDNN];
+    float* Wu[XVEC_NUM_TDNN];          // 3-tap layers: Winograd F(2,3) weights U_0..U_3 (tdnn_wino.hip, launch_pack_wino), else null
+    bool use_wino;                     // fp32 3-tap layers as Winograd F(2,3) (XVEC_WINOGRAD=0 forces the direct form: A/B runs)
     float* vec[XVEC_NUM_TDNN];         // bias | scale | shift, n_pad each
     // Plain bf16 DEFERS every layer's BatchNorm into its consumer (refold below): layer l stores relu(z + bias'), layer l+1's
     // bf16 weights carry scale_l and its bias' the shift_l (layer 5's BatchNorm goes to pool_finalize as in every mode).
@@ -99,6 +101,7 @@ struct xvec_handle {
     int num_cu;
     int blocks_per_cu;                 // persistent TDNN blocks per CU (LDS allows 2)
     int last_kernel[XVEC_NUM_TDNN];    // XVEC_KERNEL_* the last launch of each frame-level layer went to (xvec_get_dispatch)
+    int last_form[XVEC_NUM_TDNN];      // XVEC_FORM_* of that launch (xvec_get_tdnn_form)
     // profiling
     bool profiling;
     hipEvent_t ev0[T_COUNT], ev1[T_COUNT];
@@ -277,6 +280,7 @@ int run_tdnn(xvec_handle* h, int layer, TdnnVariant v, const void* X, int ldx, i
         if (v == TdnnVariant::kBf16FirstSrc32) a.x_bytes = 0;       // the caller's fp32 rows (tdnn_first3): x_rows * ldx * 4
     }
     StageTimer t(h, T_L1 + layer, s);
+    h->last_form[layer] = XVEC_FORM_DIRECT;
     // bf16, wide layers, enough rows to give every CU about two 64-frame units: the 256-channel
     // ping-pong mapping (tdnn_pp16.hip; bf16x3: the same kernel over three K-tiles per 64-channel slab); everything else
     // (small batches, layer 1, narrow models, fp32) runs the 128x128 kernel
@@ -312,6 +316,45 @@ int run_tdnn(xvec_handle* h, int layer, TdnnVariant v, const void* X, int ldx, i
     // (tdnn_pp16.hip's segment partials take a 64-bit base per slot and have no such limit)
     if (part && (size_t)((rows_out + 31) / 32 + out_map.n_utts + 1) * 3 * g.n_pad * 4 > 0x7fffffffull)
         return fail(XVEC_ERR_TOO_LARGE, "batch too large: pooling partials exceed 2 GiB; split it");
+    // fp32, three equally spaced taps: Winograd F(2,3) along time (tdnn_wino.hip), 2/3 of the direct form's products; the same
+    // kernel family (persistent fp32, 128 x 128 output tiles)
+    if (v == TdnnVariant::kF32 && h->use_wino && h->Wu[layer] && tdnn_wino_applicable(g, ldx)) {
+        WinoArgs w;
+        memset(&w, 0, sizeof(w));
+        w.X = static_cast<const float*>(X);
+        w.U = h->Wu[layer];
+        w.bias = a.bias;
+        w.scale = a.scale;
+        w.shift = a.shift;
+        w.Y = static_cast<float*>(Y);
+        w.ldx = ldx;
+        w.ldy = a.ldy;
+        w.cpt = g.kpt_pad / kBK;
+        w.k_pad = 4 * g.kpt_pad;
+        w.n_tiles = a.n_tiles;
+        w.out_map = out_map;
+        w.span = a.span;
+        w.d = g.tap_rows;
+        int64_t pairs;
+        if (out_map.offsets == nullptr) {
+            w.p_fixed = wino_pair_count(out_map.fixed_T - out_map.cum, w.d);
+            pairs = (int64_t)out_map.n_utts * w.p_fixed;
+        } else {
+            pairs = (rows_out >> 1) + (int64_t)out_map.n_utts * w.d;    // pair_base(n_utts), tdnn_wino.hip
+        }
+        w.groups_total = (pairs + 31) / 32;
+        int64_t per_col = (int64_t)h->num_cu * h->blocks_per_cu / w.n_tiles;
+        if (per_col < 1) per_col = 1;
+        if (per_col > w.groups_total) per_col = w.groups_total;
+        w.blocks_per_col = (int)per_col;
+        const int nwg = w.blocks_per_col * w.n_tiles;
+        const bool ok = h->blocks_per_cu == 2 && nwg == 2 * h->num_cu && nwg % 16 == 0 && (nwg / 8) % (2 * w.n_tiles) == 0;
+        w.pair_period = ok ? (nwg / 8) / w.n_tiles : 0;
+        HIP_TRY(launch_tdnn_wino(w, s));
+        h->last_kernel[layer] = d.kernel = XVEC_KERNEL_TILE128;
+        h->last_form[layer] = XVEC_FORM_WINOGRAD_F23;
+        return XVEC_OK;
+    }
     HIP_TRY(launch_tdnn(a, v, s));
     h->last_kernel[layer] = d.kernel = XVEC_KERNEL_TILE128;
     return XVEC_OK;
@@ -551,6 +594,8 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
         if (h->blocks_per_cu < 1) h->blocks_per_cu = 1;
         const char* p = getenv("XVEC_PP");
         h->use_pp = !(p && atoi(p) == 0);
+        const char* wg = getenv("XVEC_WINOGRAD");
+        h->use_wino = !(wg && atoi(wg) == 0);
         const char* mt = getenv("XVEC_PP_MIN_TENTHS");
         h->pp_min_tenths = mt && atoi(mt) > 0 ? atoi(mt) : 18;
         const char* cp = getenv("XVEC_PP_CU_PCT");
@@ -567,6 +612,7 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
             hipMalloc(&h->Wp48[i], (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2 * 2) != hipSuccess ||
             hipMalloc(&h->Wr48[i], (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2 * 3) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&h->Wp[i]), (size_t)g.n_pad * g.k_pad * 4) != hipSuccess ||
+            (g.n_taps == 3 && hipMalloc(reinterpret_cast<void**>(&h->Wu[i]), (size_t)g.n_pad * 4 * g.kpt_pad * 4) != hipSuccess) ||
             hipMalloc(reinterpret_cast<void**>(&h->Wraw[i]), (size_t)g.cout * g.src_taps * g.src_cin * 4) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&h->braw[i]), (size_t)g.cout * 4) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&h->vec16[i]), (size_t)3 * g.n_pad * 4) != hipSuccess ||
@@ -608,6 +654,7 @@ void xvec_destroy(xvec_handle* h) {
     if (!h) return;
     for (int i = 0; i < XVEC_NUM_TDNN; ++i) {
         if (h->Wp[i]) (void)hipFree(h->Wp[i]);
+        if (h->Wu[i]) (void)hipFree(h->Wu[i]);
         if (h->Wp16[i]) (void)hipFree(h->Wp16[i]);
         if (h->Wr16[i]) (void)hipFree(h->Wr16[i]);
         if (h->Wp48[i]) (void)hipFree(h->Wp48[i]);
@@ -657,6 +704,7 @@ int xvec_load_tdnn(xvec_handle* h, int layer, const float* weight, const float* 
     HIP_TRY(launch_pack_tdnn(weight, bias, bn_weight, bn_bias, bn_mean, bn_var, eps, g, h->Wp[layer],
                              h->vec[layer], h->vec[layer] + g.n_pad, h->vec[layer] + 2 * g.n_pad,
                              static_cast<hipStream_t>(stream)));
+    if (h->Wu[layer]) HIP_TRY(launch_pack_wino(weight, g, h->Wu[layer], static_cast<hipStream_t>(stream)));
     HIP_TRY(launch_pack_tdnn_rows_bf16x3(weight, h->geo16[layer], h->Wr48[layer], static_cast<hipStream_t>(stream)));
     {
         TdnnGeom g3 = h->geo16[layer];
@@ -955,6 +1003,13 @@ int xvec_affine(xvec_handle* h, int which, const float* x, int32_t M, int relu, 
 int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n) {
     if (!h || !kernels || !n) return fail(XVEC_ERR_ARG, "null argument");
     for (int i = 0; i < XVEC_NUM_TDNN; ++i) kernels[i] = h->last_kernel[i];
+    *n = XVEC_NUM_TDNN;
+    return XVEC_OK;
+}
+
+int xvec_get_tdnn_form(const xvec_handle* h, int* forms, int* n) {
+    if (!h || !forms || !n) return fail(XVEC_ERR_ARG, "null argument");
+    for (int i = 0; i < XVEC_NUM_TDNN; ++i) forms[i] = h->last_form[i];
     *n = XVEC_NUM_TDNN;
     return XVEC_OK;
 }

@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+
 namespace xvec {
 
 constexpr int kBK = 32;          // K-chunk (fp32 elements) staged per main-loop step
@@ -146,6 +148,35 @@ hipError_t launch_fold_bias(const float* W, const float* bias, const float* in_s
                             hipStream_t s);
 // ... and for its bf16x3 form (a.terms == 2): [n_pad/256][3 * k_pad/64][256][64], per K-tile W_hi | W_lo | W_hi
 hipError_t launch_pack_tdnn_rows_bf16x3(const float* W, const TdnnGeom& geo, void* Wr48, hipStream_t s);
+
+// fp32 layer with three equally spaced taps as Winograd F(2,3) along time (tdnn_wino.hip): two outputs (t, t+d) of one
+// utterance per GEMM row ("pair"), four products V_k . U_k^T, K = cin each.  Epilogue as launch_tdnn's kF32 variant.
+struct WinoArgs {
+    const float* X;           // [rows][ldx] fp32, the layer's input layout (RowMap of the output + u*span)
+    const float* U;           // [n_pad][k_pad]: U_0..U_3 with K in (chunk kc, product k) order (launch_pack_wino)
+    const float* bias;        // [n_pad]
+    const float* scale;       // [n_pad]
+    const float* shift;       // [n_pad]
+    float* Y;                 // [rows_out][ldy] fp32
+    int ldx, ldy;
+    int cpt;                  // 32-wide K chunks per product (cin / kBK)
+    int k_pad;                // 4 * cpt * kBK
+    int n_tiles;              // 128-channel columns
+    int blocks_per_col;
+    int64_t groups_total;     // 32-pair groups of the pair axis
+    int pair_period;          // as TdnnArgs
+    RowMap out_map;
+    int span;                 // 2d: frames the layer consumes
+    int d;                    // dilation
+    int p_fixed;              // fixed-length batches: pairs per utterance
+};
+// pairs of an utterance with T output frames, and the pair-axis length of a batch (ragged: with the holes of the
+// pair_base formula, tdnn_wino.hip)
+inline int wino_pair_count(int T, int d) { return d * (T / (2 * d)) + std::min(T % (2 * d), d); }
+bool tdnn_wino_applicable(const TdnnGeom& g, int ldx);
+hipError_t launch_tdnn_wino(const WinoArgs& a, hipStream_t s);
+// U_0 = W_0, U_1 = (W_0+W_1+W_2)/2, U_2 = (W_0-W_1+W_2)/2, U_3 = W_2 of a 3-tap layer (fp64, rounded once) -> Wu [n_pad][4*kpt_pad]
+hipError_t launch_pack_wino(const float* W, const TdnnGeom& geo, float* Wu, hipStream_t s);
 
 struct PoolArgs {
     const float* X;          // [B][T][C]

@@ -488,6 +488,16 @@ class XVectorModel(nn.Module):
         _hip.check(_hip.lib.xvec_get_dispatch(eng.h, buf, C.byref(n)))
         return [_hip.KERNEL_NAMES.get(int(buf[i])) for i in range(n.value)]
 
+    def last_forms(self, device=None) -> list:
+        """Arithmetic form of the last launch of each frame-level layer: "direct" | "winograd_f23" (fp32 layers with three
+        equally spaced taps, csrc/tdnn_wino.hip; XVEC_WINOGRAD=0 at engine creation forces "direct")."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        eng = self._engine(dev)
+        buf = (C.c_int * 8)()
+        n = C.c_int(0)
+        _hip.check(_hip.lib.xvec_get_tdnn_form(eng.h, buf, C.byref(n)))
+        return [_hip.FORM_NAMES.get(int(buf[i])) for i in range(n.value)]
+
     # ------------------------------------------------------------------ caller shims (main.py:135-146)
     def test_step(self, batch, batch_index=0):
         """Same I/O as the reference's Lightning hook: casts to fp32, returns
