@@ -7,7 +7,7 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/xvec_hip.h.
 from . import synth  # noqa: F401  (numpy only)
 
 __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontEnd", "PldaScorer", "hip", "extract",
-           "frontend", "scoring"]
+           "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject"]
 
 
 def __getattr__(name):
@@ -21,7 +21,10 @@ def __getattr__(name):
     if name == "PldaScorer":
         from . import scoring
         return scoring.PldaScorer
-    if name in ("hip", "model", "extract", "frontend", "scoring"):
+    if name in ("PldaStats", "PLDA", "StatObject"):
+        from . import plda
+        return getattr(plda, name)
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -1,0 +1,135 @@
+"""PLDA training, CPU half: the package's host EM (xvector_amd.plda.host_em) against the literal restatement of
+speechbrain's loop (tests/plda_em_ref.py, unpinned), the speechbrain-shaped surface, the C ABI's argument checks and the
+kernels' resources.  The device half is tests/test_plda_train_gpu.py."""
+import os
+import pickle
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import plda_em_ref as ref
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+
+
+def numpy_products(sums_centred, counts):
+    """What xvec_plda_em_products computes, in numpy float64 (the test's stand-in for the device)."""
+    def products(pq, lam):
+        H = (sums_centred @ pq) / (counts[:, None] * lam[None, :] + 1.0)
+        return H.T @ H, H.T @ (counts[:, None] * H), H.T @ sums_centred
+    return products
+
+
+def host_fit(x, labels, rank_f, nb_iter=10, scaling_factor=1.0):
+    from xvector_amd import plda
+    mean, sigma_obs, _, counts, sums = ref.class_stats(x, labels, scaling_factor)
+    F, Sigma = plda.host_em(sigma_obs, counts, rank_f, nb_iter, numpy_products(sums - counts[:, None] * mean, counts))
+    return mean, F, Sigma
+
+
+@pytest.mark.parametrize("rank_f,scaling_factor,string_labels", [(1, 1.0, False), (12, 1.0, True), (12, 0.5, False),
+                                                                 (24, 0.5, True)])
+def test_host_em_matches_restatement(rank_f, scaling_factor, string_labels):
+    dim = 24
+    x, labels, _ = ref.make_data(60, dim, 6, sizes=(1, 12), seed=rank_f)
+    labels = labels.copy()
+    labels[0] = 10_000                       # a class of exactly one row
+    if string_labels:
+        labels = np.array(["id" + str(v) for v in labels], dtype=object)
+    want = ref.plda_em(x, labels, rank_f, 10, scaling_factor)
+    got = host_fit(x, labels, rank_f, 10, scaling_factor)
+    assert ref.rel(got[0], want[0]) <= 1e-10
+    assert ref.rel(got[1] @ got[1].T, want[1] @ want[1].T) <= 1e-10
+    assert ref.rel(got[2], want[2]) <= 1e-10
+
+
+def test_host_em_rejects_bad_rank():
+    from xvector_amd import plda
+    with pytest.raises(ValueError):
+        plda.host_em(np.eye(4), np.ones(3), 5, 1, None)
+    with pytest.raises(ValueError):
+        plda.host_em(np.eye(4), np.ones(3), 0, 1, None)
+
+
+def test_surface_and_pickle(tmp_path):
+    from xvector_amd import plda
+    import xvector_amd as xa
+    assert xa.PLDA is plda.PLDA and xa.PldaStats is plda.PldaStats and xa.StatObject is plda.StatObject
+    xv = np.arange(12.0).reshape(4, 3)
+    st = plda.get_train_x_vec(xv, [3, 3, 7, 1], ["a", "b", "c", "d"])
+    assert list(st.modelset) == ["id3", "id3", "id7", "id1"] and list(st.segset) == ["a", "b", "c", "d"]
+    assert st.stat0.shape == (4, 1) and st.stat1 is xv
+    es = plda.get_x_vec_stat(xv, [5, 6, 7, 8])
+    assert list(es.modelset) == list(es.segset) == ["5", "6", "7", "8"]
+    p = plda.setup_plda(rank_f=2, nb_iter=3)
+    assert (p.rank_f, p.nb_iter, p.scaling_factor, p.mean, p.F, p.Sigma) == (2, 3, 1, None, None, None)
+    p.mean, p.F, p.Sigma = np.zeros(3), np.ones((3, 2)), np.eye(3)
+    path = tmp_path / "plda.pkl"
+    plda.save_plda(p, str(path))
+    q = plda.load_plda(str(path))
+    assert np.array_equal(q.F, p.F) and np.array_equal(q.Sigma, p.Sigma) and q.rank_f == 2
+    assert pickle.loads(pickle.dumps(p)).nb_iter == 3
+    with pytest.raises(NotImplementedError):
+        p.plda(st, whiten=True)
+
+
+def test_training_refuses_cpu_device():
+    from xvector_amd import plda
+    with pytest.raises(RuntimeError):
+        plda.PldaStats(np.zeros((4, 3)), [0, 0, 1, 1], device="cpu")
+
+
+def test_plda_abi_argument_errors_without_gpu():
+    import ctypes as C
+    from xvector_amd import hip
+    lib = hip.lib
+    start = (C.c_int64 * 3)(0, 2, 4)
+    args = lambda **kw: [kw.get("x", 1), 0, kw.get("n", 4), kw.get("dim", 3), kw.get("order", 1), kw.get("start", start),
+                         kw.get("c", 2), 1.0, 1, 1, 1, 1, 1, 1, 1 << 30, None]
+    assert lib.xvec_plda_stats(*args(n=1)) == hip.ERR_ARG and b"two" in lib.xvec_plda_last_error()
+    assert lib.xvec_plda_stats(*args(c=0)) == hip.ERR_ARG
+    assert lib.xvec_plda_stats(*args(dim=0)) == hip.ERR_ARG
+    assert lib.xvec_plda_stats(*args(x=None)) == hip.ERR_ARG and b"null" in lib.xvec_plda_last_error()
+    assert lib.xvec_plda_stats(*args(order=None)) == hip.ERR_ARG
+    assert lib.xvec_plda_stats(*args(start=None)) == hip.ERR_ARG
+    assert lib.xvec_plda_stats(*args(n=5)) == hip.ERR_ARG and b"class_start" in lib.xvec_plda_last_error()
+    bad = (C.c_int64 * 3)(0, 3, 2)
+    assert lib.xvec_plda_stats(*args(start=bad, n=2)) == hip.ERR_ARG and b"decreases" in lib.xvec_plda_last_error()
+    # a valid set of arguments with a workspace that is too small never reaches the device
+    small = args()
+    small[-2] = 8
+    assert lib.xvec_plda_stats(*small) == hip.ERR_WORKSPACE
+    assert lib.xvec_plda_stats_workspace_bytes(1, 3, 1) == 0
+    assert lib.xvec_plda_stats_workspace_bytes(400_000, 512, 1211) > 0
+    em = lambda **kw: [kw.get("p", 1), 1, 1, 1, 1, kw.get("c", 10), kw.get("dim", 8), kw.get("rank", 4), 1, 1, 1 << 30, None]
+    assert lib.xvec_plda_em_products(*em(rank=9)) == hip.ERR_ARG and b"rank_f" in lib.xvec_plda_last_error()
+    assert lib.xvec_plda_em_products(*em(c=0)) == hip.ERR_ARG
+    assert lib.xvec_plda_em_products(*em(p=None)) == hip.ERR_ARG and b"null" in lib.xvec_plda_last_error()
+    assert lib.xvec_plda_em_workspace_bytes(0, 4) == 0 and lib.xvec_plda_em_workspace_bytes(10, 4) > 0
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+def test_plda_kernels_use_no_scratch():
+    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
+           "-Wno-pass-failed", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", "-c", "plda_train.hip", "-o", os.devnull]
+    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    kernels, name = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
+                         ("spill", r"VGPRs Spill: (\d+)"), ("agprs", r" AGPRs: (\d+)")):
+            m = re.search(pat, line)
+            if m and name:
+                kernels[name][key] = int(m.group(1))
+    assert len(kernels) == 10, sorted(kernels)    # class sums x2, mean, centre, scatter x4, reduce, E-step scale
+    for k, r in kernels.items():
+        assert r.get("scratch", 0) == 0 and r.get("spill", 0) == 0, f"{k}: {r}"
+        assert r.get("vgprs", 0) + r.get("agprs", 0) <= 256, f"{k}: {r}"
