@@ -199,9 +199,11 @@ enum {
 int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n);
 /* Which arithmetic form the LAST launch of each frame-level layer used: forms[0..4], *n = 5.  XVEC_FORM_WINOGRAD_F23: an fp32
  * layer with three equally spaced taps (layers 2 and 3 of the reference) as Winograd F(2,3) along time -- four products for
- * two output frames instead of six (csrc/tdnn_wino.hip); every other layer and precision is direct.  XVEC_WINOGRAD=0 in the
- * environment at xvec_create forces the direct form. */
-enum { XVEC_FORM_DIRECT = 0, XVEC_FORM_WINOGRAD_F23 = 1 };
+ * two output frames instead of six (csrc/tdnn_wino.hip).  XVEC_FORM_BF16_SPLIT3: an fp32 layer with one tap (layers 4 and 5)
+ * at a large batch, activations and weights split exactly into three bf16 pieces each, six bf16 products per k-step on the
+ * bf16 matrix pipe (csrc/tdnn_layer.hip).  Every other layer and precision is direct.  XVEC_WINOGRAD=0 / XVEC_SPLIT3=0 in the
+ * environment at xvec_create force the direct form. */
+enum { XVEC_FORM_DIRECT = 0, XVEC_FORM_WINOGRAD_F23 = 1, XVEC_FORM_BF16_SPLIT3 = 2 };
 int xvec_get_tdnn_form(const xvec_handle* h, int* forms, int* n);
 
 /* ---- next row N3: MFCC front end (the step in front of the path) ----------------------------

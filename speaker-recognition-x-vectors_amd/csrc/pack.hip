@@ -126,6 +126,36 @@ hipError_t launch_pack_tdnn_bf16(const float* W, const float* in_scale, const Td
     return hipGetLastError();
 }
 
+// bf16_split3 weights of an fp32 1-tap layer (tdnn_layer.hip, S3): W = W_hi + W_mid + W_lo exactly (W_hi = bf16(W),
+// W_mid = bf16(W - W_hi), W_lo = W - W_hi - W_mid), fragment-major as above with the three planes of one (32-channel column
+// tile, 16-wide k-step) next to each other: block (ct * k_pad / 16 + ks) * 3 + plane, 1 KiB each, in the fp32 K order.
+__global__ void pack_tdnn_weight_split3_kernel(const float* __restrict__ W, TdnnGeom g, __bf16* __restrict__ Wf) {
+    const int64_t total = (int64_t)g.n_pad * g.k_pad * 3;
+    const int ksteps = g.k_pad / 16;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+         i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t blk = i >> 9;
+        const int within = (int)(i & 511), lane = within >> 3, j = within & 7;
+        const int plane = (int)(blk % 3);
+        const int64_t kb = blk / 3;
+        const int ct = (int)(kb / ksteps), ks = (int)(kb % ksteps);
+        const int n = ct * 32 + (lane & 31), kd = tap_major_k(g, ks * 16 + 8 * (lane >> 5) + j);
+        const int tap = kd / g.tap_stride_src, c = kd % g.tap_stride_src;
+        float v = 0.f;
+        if (n < g.cout && tap < g.src_taps && c < g.src_cin) v = W[(int64_t)n * (g.src_taps * g.src_cin) + tap * g.src_cin + c];
+        const __bf16 hi = (__bf16)v;
+        const float r1 = v - (float)hi;
+        const __bf16 mid = (__bf16)r1;
+        Wf[i] = plane == 0 ? hi : plane == 1 ? mid : (__bf16)(r1 - (float)mid);
+    }
+}
+
+hipError_t launch_pack_tdnn_split3(const float* W, const TdnnGeom& geo, void* Wf3, hipStream_t s) {
+    if (geo.n_taps != 1 || geo.k_pad % 32 != 0 || geo.n_pad % 32 != 0) return hipErrorInvalidValue;
+    pack_tdnn_weight_split3_kernel<<<1024, 256, 0, s>>>(W, geo, static_cast<__bf16*>(Wf3));
+    return hipGetLastError();
+}
+
 // bf16 weights for tdnn_pp16.hip, K-TILE major: [256-channel column block][K-tile of 64][256 rows][64 k]
 // (K order as everywhere: 64-element chunks, taps innermost).  Both operands of that kernel reach LDS by
 // DMA in 128-byte row slabs; a K-tile of a column block is then one contiguous 32 KiB, so the 256 CUs

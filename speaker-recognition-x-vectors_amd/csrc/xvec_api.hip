@@ -40,6 +40,10 @@ const int kCtxDil[XVEC_NUM_TDNN] = {1, 2, 3, 0, 0};
 
 enum { T_L1 = 0, T_POOL = 5, T_SEG6 = 6, T_SEG7 = 7, T_OUT = 8, T_PACK = 9, T_COUNT = 10 };
 constexpr int kMaxUtts = 65535;   // utterances per call (16-bit utterance counters in the kernels' row maps)
+// fp32 1-tap layers take the bf16_split3 form from this many output rows per CU on (B >= 58 at T = 300).  The form measured
+// faster at every batch size down to B = 1; the threshold keeps small batches on the direct form they were
+// validated with.
+constexpr int kSplit3MinRowsPerCu = 64;
 
 // RAII: the calling thread's current device is whatever it was before the call
 struct DeviceGuard {
@@ -77,6 +81,9 @@ struct xvec_handle {
     float* Wp[XVEC_NUM_TDNN];
     float* Wu[XVEC_NUM_TDNN];          // 3-tap layers: Winograd F(2,3) weights U_0..U_3 (tdnn_wino.hip, launch_pack_wino), else null
     bool use_wino;                     // fp32 3-tap layers as Winograd F(2,3) (XVEC_WINOGRAD=0 forces the direct form: A/B runs)
+    void* Wp3[XVEC_NUM_TDNN];          // fp32 1-tap layers 2..5: bf16_split3 weight planes hi | mid | lo, fragment-major (pack.hip), else null
+    bool use_split3;                   // fp32 1-tap layers as bf16_split3 at large batches (XVEC_SPLIT3=0 forces the direct form: A/B runs)
+    int split3_min_rows;               // ... from this many output rows per CU on (XVEC_SPLIT3_MIN_ROWS: crossover sweeps)
     float* vec[XVEC_NUM_TDNN];         // bias | scale | shift, n_pad each
     // Plain bf16 DEFERS every layer's BatchNorm into its consumer (refold below): layer l stores relu(z + bias'), layer l+1's
     // bf16 weights carry scale_l and its bias' the shift_l (layer 5's BatchNorm goes to pool_finalize as in every mode).
@@ -318,6 +325,17 @@ int run_tdnn(xvec_handle* h, int layer, TdnnVariant v, const void* X, int ldx, i
         return fail(XVEC_ERR_TOO_LARGE, "batch too large: pooling partials exceed 2 GiB; split it");
     // fp32, three equally spaced taps: Winograd F(2,3) along time (tdnn_wino.hip), 2/3 of the direct form's products; the same
     // kernel family (persistent fp32, 128 x 128 output tiles)
+    // fp32, one tap, large batch: bf16_split3 (tdnn_layer.hip, S3), x = hi + mid + lo and W likewise as bf16 planes, six bf16
+    // products per k-step on the bf16 matrix pipe at 0.375 of the fp32 MFMA time; the same kernel family and epilogues
+    if ((v == TdnnVariant::kF32 || v == TdnnVariant::kF32Pool) && h->use_split3 && h->Wp3[layer] && g.n_taps == 1 &&
+        rows_out >= (int64_t)h->split3_min_rows * h->num_cu) {
+        a.terms = 3;
+        a.Wf = h->Wp3[layer];
+        HIP_TRY(launch_tdnn(a, v, s));
+        h->last_kernel[layer] = d.kernel = XVEC_KERNEL_TILE128;
+        h->last_form[layer] = XVEC_FORM_BF16_SPLIT3;
+        return XVEC_OK;
+    }
     if (v == TdnnVariant::kF32 && h->use_wino && h->Wu[layer] && tdnn_wino_applicable(g, ldx)) {
         WinoArgs w;
         memset(&w, 0, sizeof(w));
@@ -596,6 +614,10 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
         h->use_pp = !(p && atoi(p) == 0);
         const char* wg = getenv("XVEC_WINOGRAD");
         h->use_wino = !(wg && atoi(wg) == 0);
+        const char* s3 = getenv("XVEC_SPLIT3");
+        h->use_split3 = !(s3 && atoi(s3) == 0);
+        const char* s3m = getenv("XVEC_SPLIT3_MIN_ROWS");
+        h->split3_min_rows = s3m && atoi(s3m) >= 0 ? atoi(s3m) : kSplit3MinRowsPerCu;
         const char* mt = getenv("XVEC_PP_MIN_TENTHS");
         h->pp_min_tenths = mt && atoi(mt) > 0 ? atoi(mt) : 18;
         const char* cp = getenv("XVEC_PP_CU_PCT");
@@ -613,6 +635,7 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
             hipMalloc(&h->Wr48[i], (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2 * 3) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&h->Wp[i]), (size_t)g.n_pad * g.k_pad * 4) != hipSuccess ||
             (g.n_taps == 3 && hipMalloc(reinterpret_cast<void**>(&h->Wu[i]), (size_t)g.n_pad * 4 * g.kpt_pad * 4) != hipSuccess) ||
+            (i > 0 && g.n_taps == 1 && hipMalloc(&h->Wp3[i], (size_t)g.n_pad * g.k_pad * 2 * 3) != hipSuccess) ||
             hipMalloc(reinterpret_cast<void**>(&h->Wraw[i]), (size_t)g.cout * g.src_taps * g.src_cin * 4) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&h->braw[i]), (size_t)g.cout * 4) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&h->vec16[i]), (size_t)3 * g.n_pad * 4) != hipSuccess ||
@@ -658,6 +681,7 @@ void xvec_destroy(xvec_handle* h) {
         if (h->Wp16[i]) (void)hipFree(h->Wp16[i]);
         if (h->Wr16[i]) (void)hipFree(h->Wr16[i]);
         if (h->Wp48[i]) (void)hipFree(h->Wp48[i]);
+        if (h->Wp3[i]) (void)hipFree(h->Wp3[i]);
         if (h->Wr48[i]) (void)hipFree(h->Wr48[i]);
         if (h->vec[i]) (void)hipFree(h->vec[i]);
         if (h->Wraw[i]) (void)hipFree(h->Wraw[i]);
@@ -705,6 +729,7 @@ int xvec_load_tdnn(xvec_handle* h, int layer, const float* weight, const float* 
                              h->vec[layer], h->vec[layer] + g.n_pad, h->vec[layer] + 2 * g.n_pad,
                              static_cast<hipStream_t>(stream)));
     if (h->Wu[layer]) HIP_TRY(launch_pack_wino(weight, g, h->Wu[layer], static_cast<hipStream_t>(stream)));
+    if (h->Wp3[layer]) HIP_TRY(launch_pack_tdnn_split3(weight, g, h->Wp3[layer], static_cast<hipStream_t>(stream)));
     HIP_TRY(launch_pack_tdnn_rows_bf16x3(weight, h->geo16[layer], h->Wr48[layer], static_cast<hipStream_t>(stream)));
     {
         TdnnGeom g3 = h->geo16[layer];

@@ -107,7 +107,7 @@ struct TdnnArgs {
     // bf16x3 (fp32 values carried as two bf16 planes hi + lo, three bf16 products per k-step:
     // x_hi*W_hi + x_hi*W_lo + x_lo*W_hi).  terms == 2: X has a lo plane x_plane_bytes after the hi
     // plane and Wf holds, per chunk, the W_hi fragments followed by the W_lo fragments.
-    int terms;                // 1 (plain) or 2
+    int terms;                // 1 (plain) or 2; 3: bf16_split3 of an fp32 1-tap layer (Wf = pack_tdnn_weight_split3_kernel's planes)
     int x_plane_bytes;        // byte distance from the hi plane of X to its lo plane
     int y_plane_bytes;        // > 0: bf16 output as two planes, lo plane this many bytes after Y
     int64_t x_bytes;          // guarded variant: readable bytes from X (0: x_rows * ldx * element size)
@@ -126,6 +126,8 @@ enum class TdnnVariant {
     kBf16FirstToF32   // layer 1, guarded, bf16 -> fp32 (per-layer test entry in bf16x3)
 };
 hipError_t launch_tdnn(const TdnnArgs& a, TdnnVariant v, hipStream_t s);
+// kF32 / kF32Pool of a one-tap layer with terms == 3 (launch_tdnn forwards them): tdnn_split3.hip
+hipError_t launch_tdnn_split3(const TdnnArgs& a, bool pool, hipStream_t s);
 // Large-batch bf16 mapping (tdnn_pp16.hip, v_mfma_f32_16x16x32_bf16): 256-channel columns, 64-frame units.  Reads TdnnArgs with
 //   W = K-tile major bf16 [n_pad/256][k_pad/64][256][64] (K order as the fp32 packing, 64-element chunks), n_tiles = n_pad / 256,
 //   groups_total = ceil(rows / 64) units, blocks_per_col ranges per column (>= 1.8 units each: the measured crossover with the 128x128 kernel).
@@ -140,6 +142,9 @@ hipError_t launch_tdnn_first(const TdnnArgs& a, int num_cu, hipStream_t s);
 // ... and of the bf16x3 path: terms == 2, Wf = the bf16x3 fragment stream, Y = two bf16 planes y_plane_bytes apart; X the caller's fp32 rows
 bool tdnn_first3_applicable(const TdnnArgs& a);
 hipError_t launch_tdnn_first3(const TdnnArgs& a, int num_cu, hipStream_t s);
+// bf16_split3 form of an fp32 1-tap layer (launch_tdnn with terms == 3, kF32 / kF32Pool): Wf = three bf16 planes hi | mid | lo
+// per (32-channel column tile, 16-wide k-step), fragment-major, 3 x n_pad x k_pad bf16 (pack.hip)
+hipError_t launch_pack_tdnn_split3(const float* W, const TdnnGeom& geo, void* Wf3, hipStream_t s);
 // K-tile major bf16 copy of the packed weights for it
 // (in_scale: nullptr, or the producing layer's folded BatchNorm scale per input channel -- plain bf16 defers BatchNorm, pack.hip)
 hipError_t launch_pack_tdnn_rows_bf16(const float* W, const float* in_scale, const TdnnGeom& geo, void* Wr16, hipStream_t s);

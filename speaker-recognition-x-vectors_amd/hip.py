@@ -32,7 +32,7 @@ PLDA_X_F32, PLDA_X_F64 = 0, 1                                   # XVEC_PLDA_X_*
 MODE_LOGITS, MODE_POOLED, MODE_XVEC6, MODE_XVEC7 = 0, 5, 6, 7
 SEG6, SEG7, OUTPUT = 6, 7, 8
 KERNEL_NAMES = {0: None, 1: "tile128", 2: "pp", 3: "first"}      # XVEC_KERNEL_*
-FORM_NAMES = {0: "direct", 1: "winograd_f23"}                     # XVEC_FORM_*
+FORM_NAMES = {0: "direct", 1: "winograd_f23", 2: "bf16_split3"}     # XVEC_FORM_*
 TIMING_NAMES = ("tdnn1", "tdnn2", "tdnn3", "tdnn4", "tdnn5_pool", "pool_finalize",
                 "segment6", "segment7", "output", "pack")
 
