@@ -1,4 +1,4 @@
-// Device helpers shared by the frame-level kernels (tdnn_layer.hip, tdnn_bf16.hip).
+// Device helpers shared by the frame-level kernels (tdnn_layer_impl.h, tdnn_pp16.hip, tdnn_first.hip, tdnn_wino.hip).
 #pragma once
 #include "xvec_internal.h"
 
@@ -102,7 +102,7 @@ constexpr int kPoolPlanes = 3;
 
 // Two of the three floats of one column's partial: as a buffer store (scalar slot offset + one 32-bit lane offset):
 // a plain `part[...] = v` costs a 64-bit address in two VGPRs per store, in an epilogue that has none to spare.
-// (The buffer is < 2 GiB: forward_rows.)  Both lane halves hold every value after add_halves / lower_half: half 0
+// (The buffer is < 2 GiB: plan_layer.)  Both lane halves hold every value after add_halves / lower_half: half 0
 // stores the S1 plane and half 1 the S2 plane with ONE instruction (two whole 128-byte segments), then half 0
 // alone stores the K plane.
 __device__ __forceinline__ void store_partial(__amdgpu_buffer_rsrc_t prs, int ld, int64_t slot, int h, int col, float k,

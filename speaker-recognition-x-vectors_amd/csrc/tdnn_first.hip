@@ -14,7 +14,8 @@
 // above it); bf16x3: first3::tdnn_first3_kernel.
 //
 // Shapes: n_pad == 512, one folded tap with k_pad == 128 (input_size * 5 <= 126 for plain bf16, rows contiguous: ldx ==
-// input_size) and 16-byte aligned rows; run_tdnn falls back to the 128x128 kernel otherwise.
+// input_size) and 16-byte aligned rows (tdnn_first_applicable / tdnn_first3_applicable); the host planner (xvec_api.hip,
+// plan_layer) takes the 128x128 kernel otherwise.
 #include "tdnn_common.h"
 
 namespace xvec {

@@ -62,31 +62,25 @@ extern "C" int xvec_diag_read(unsigned long long* host, int n_words) {
 }
 #endif
 
-hipError_t launch_tdnn(const TdnnArgs& a, TdnnVariant v, hipStream_t s) {
-    if (a.groups_total <= 0 || a.blocks_per_col <= 0 || a.blocks_per_col > a.groups_total || (a.cpt & 1))
-        return hipErrorInvalidValue;
-    const bool x3 = a.terms == 2;     // bf16x3: compile-time mode of the bf16 instantiations
-    const bool s3 = a.terms == 3;     // bf16_split3: the fp32 1-tap layers (store and pooling variants)
-    if (s3 && (a.n_taps != 1 || (v != TdnnVariant::kF32 && v != TdnnVariant::kF32Pool))) return hipErrorInvalidValue;
-    switch (v) {
-        case TdnnVariant::kF32First: return launch_variant<true, false, true, false, false>(a, s);
-        case TdnnVariant::kF32:
-            return s3 ? launch_tdnn_split3(a, false, s) : launch_variant<false, false, true, false, false>(a, s);
-        case TdnnVariant::kF32Pool:
-            return s3 ? launch_tdnn_split3(a, true, s) : launch_variant<false, true, false, false, false>(a, s);
-        case TdnnVariant::kBf16FirstSrc32: return launch_variant<2, false, true, true, true>(a, s);
-        case TdnnVariant::kBf16First:
-            return x3 ? launch_variant<true, false, true, true, true, true>(a, s) : launch_variant<true, false, true, true, true>(a, s);
-        case TdnnVariant::kBf16:
-            return x3 ? launch_variant<false, false, true, true, true, true>(a, s) : launch_variant<false, false, true, true, true>(a, s);
-        case TdnnVariant::kBf16Pool:
-            return x3 ? launch_variant<false, true, false, true, false, true>(a, s) : launch_variant<false, true, false, true, false>(a, s);
-        case TdnnVariant::kBf16ToF32:
-            return x3 ? launch_variant<false, false, true, true, false, true>(a, s) : launch_variant<false, false, true, true, false>(a, s);
-        case TdnnVariant::kBf16FirstToF32:
-            return x3 ? launch_variant<true, false, true, true, false, true>(a, s) : launch_variant<true, false, true, true, false>(a, s);
+// a bf16 variant in its bf16x3 and plain instantiations
+template <int GUARD, bool POOL, bool OUTBF>
+static hipError_t launch_bf16(const TdnnArgs& a, bool x3, hipStream_t s) {
+    return x3 ? launch_variant<GUARD, POOL, !POOL, true, OUTBF, true>(a, s) : launch_variant<GUARD, POOL, !POOL, true, OUTBF>(a, s);
+}
+
+hipError_t launch_tdnn(const TdnnArgs& a, TdnnMode m, hipStream_t s) {
+    const bool pool = m.dst == Dst::kPool, out16 = m.dst == Dst::kAct, x3 = m.prec == Prec::kBf16x3;
+    if (m.prec == Prec::kF32) {       // (an fp32 activation is fp32 output; layer 1 has no pooling epilogue)
+        if (m.src == Src::kRows16 || (pool && m.src != Src::kAct)) return hipErrorInvalidValue;
+        if (m.src == Src::kRows32) return launch_variant<true, false, true, false, false>(a, s);
+        return !pool ? launch_variant<false, false, true, false, false>(a, s) : launch_variant<false, true, false, false, false>(a, s);
     }
-    return hipErrorInvalidValue;
+    if (m.src == Src::kRows32)        // bf16x3 reads the caller's fp32 rows only through tdnn_first3
+        return x3 || !out16 ? hipErrorInvalidValue : launch_variant<2, false, true, true, true>(a, s);
+    const bool guard = m.src == Src::kRows16;
+    if (out16) return guard ? launch_bf16<true, false, true>(a, x3, s) : launch_bf16<false, false, true>(a, x3, s);
+    if (pool) return guard ? hipErrorInvalidValue : launch_bf16<false, true, false>(a, x3, s);
+    return !guard ? launch_bf16<false, false, false>(a, x3, s) : launch_bf16<true, false, false>(a, x3, s);
 }
 
 }  // namespace xvec

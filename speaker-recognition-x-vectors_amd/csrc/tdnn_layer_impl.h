@@ -780,6 +780,8 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
 
 template <typename K>
 static hipError_t launch_kernel(K kern, const TdnnArgs& a, hipStream_t s, LdsOptIn& opt) {
+    if (a.groups_total <= 0 || a.blocks_per_col <= 0 || a.blocks_per_col > a.groups_total || (a.cpt & 1))
+        return hipErrorInvalidValue;
     if (hipError_t e = opt.ensure(reinterpret_cast<const void*>(kern), kLdsBytes); e != hipSuccess) return e;
     const int grid = a.blocks_per_col * a.n_tiles;
     kern<<<dim3(grid), dim3(256), kLdsBytes, s>>>(a);

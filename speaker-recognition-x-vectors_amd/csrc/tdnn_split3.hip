@@ -15,6 +15,7 @@ __global__ __launch_bounds__(256, 2) void tdnn_split3_kernel(const TdnnArgs a) {
 
 hipError_t launch_tdnn_split3(const TdnnArgs& a, bool pool, hipStream_t s) {
     static LdsOptIn opt_store, opt_pool;     // per variant and device
+    if (a.n_taps != 1) return hipErrorInvalidValue;
     return pool ? launch_kernel(tdnn_split3_kernel<true, false>, a, s, opt_pool)
                 : launch_kernel(tdnn_split3_kernel<false, true>, a, s, opt_store);
 }

@@ -45,6 +45,29 @@ constexpr int kMaxUtts = 65535;   // utterances per call (16-bit utterance count
 // validated with.
 constexpr int kSplit3MinRowsPerCu = 64;
 
+// The dispatch knobs, read from the environment once, when a handle is created (A/B runs and crossover sweeps, profiles/)
+struct Policy {
+    int blocks_per_cu;      // XVEC_BLOCKS_PER_CU: persistent TDNN blocks per CU (2: what the LDS allows)
+    bool pp;                // XVEC_PP=0 disables the large-batch bf16 mapping (tdnn_pp16.hip) and the streaming layer 1
+    int pp_min_tenths;      // XVEC_PP_MIN_TENTHS: ... taken from this many tenths of a 64-frame unit per CU on (18)
+    int pp_cu_pct;          // XVEC_PP_CU_PCT (diagnostic): percentage of the CUs the large-batch kernel's grid covers (0 = all)
+    bool wino;              // XVEC_WINOGRAD=0 forces the direct form of the fp32 3-tap layers
+    bool split3;            // XVEC_SPLIT3=0 forces the direct form of the fp32 1-tap layers
+    int split3_min_rows;    // XVEC_SPLIT3_MIN_ROWS: ... which take bf16_split3 from this many output rows per CU on
+};
+
+int env_int(const char* name, int unset) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : unset;
+}
+
+Policy read_policy() {
+    const int tenths = env_int("XVEC_PP_MIN_TENTHS", 18), s3_rows = env_int("XVEC_SPLIT3_MIN_ROWS", kSplit3MinRowsPerCu);
+    return {std::max(1, env_int("XVEC_BLOCKS_PER_CU", 2)), env_int("XVEC_PP", 1) != 0, tenths > 0 ? tenths : 18,
+            env_int("XVEC_PP_CU_PCT", 0), env_int("XVEC_WINOGRAD", 1) != 0, env_int("XVEC_SPLIT3", 1) != 0,
+            s3_rows >= 0 ? s3_rows : kSplit3MinRowsPerCu};
+}
+
 // RAII: the calling thread's current device is whatever it was before the call
 struct DeviceGuard {
     int prev = -1;
@@ -73,17 +96,11 @@ struct xvec_handle {
     void* Wp16[XVEC_NUM_TDNN];         // bf16, fragment-major
     void* Wp16b;                       // layer 1 only: the same with the bias in the two spare k slots (tdnn_first.hip)
     void* Wr16[XVEC_NUM_TDNN];         // bf16, K-tile major [n_pad/256][k_pad/64][256][64] (tdnn_pp16.hip: both operands reach LDS by DMA)
-    bool use_pp;                       // large-batch bf16 mapping enabled (XVEC_PP=0 disables it: A/B runs)
-    int pp_min_tenths;                 // ... from this many tenths of a 64-frame unit per CU on (18; XVEC_PP_MIN_TENTHS: crossover sweeps)
-    int pp_cu_pct;                     // XVEC_PP_CU_PCT (diagnostic): percentage of the CUs the large-batch kernel's grid covers (0 = all)
     void* Wp48[XVEC_NUM_TDNN];         // bf16x3: per chunk W_hi then W_lo fragments (2x the size), fragment-major
     void* Wr48[XVEC_NUM_TDNN];         // bf16x3, K-tile major for tdnn_pp16.hip: per K-tile W_hi | W_lo | W_hi (3x the size of Wr16)
     float* Wp[XVEC_NUM_TDNN];
     float* Wu[XVEC_NUM_TDNN];          // 3-tap layers: Winograd F(2,3) weights U_0..U_3 (tdnn_wino.hip, launch_pack_wino), else null
-    bool use_wino;                     // fp32 3-tap layers as Winograd F(2,3) (XVEC_WINOGRAD=0 forces the direct form: A/B runs)
     void* Wp3[XVEC_NUM_TDNN];          // fp32 1-tap layers 2..5: bf16_split3 weight planes hi | mid | lo, fragment-major (pack.hip), else null
-    bool use_split3;                   // fp32 1-tap layers as bf16_split3 at large batches (XVEC_SPLIT3=0 forces the direct form: A/B runs)
-    int split3_min_rows;               // ... from this many output rows per CU on (XVEC_SPLIT3_MIN_ROWS: crossover sweeps)
     float* vec[XVEC_NUM_TDNN];         // bias | scale | shift, n_pad each
     // Plain bf16 DEFERS every layer's BatchNorm into its consumer (refold below): layer l stores relu(z + bias'), layer l+1's
     // bf16 weights carry scale_l and its bias' the shift_l (layer 5's BatchNorm goes to pool_finalize as in every mode).
@@ -106,7 +123,7 @@ struct xvec_handle {
     bool offs_pending[2];
     int offs_next;
     int num_cu;
-    int blocks_per_cu;                 // persistent TDNN blocks per CU (LDS allows 2)
+    Policy pol;
     int last_kernel[XVEC_NUM_TDNN];    // XVEC_KERNEL_* the last launch of each frame-level layer went to (xvec_get_dispatch)
     int last_form[XVEC_NUM_TDNN];      // XVEC_FORM_* of that launch (xvec_get_tdnn_form)
     // profiling
@@ -139,7 +156,7 @@ Plan make_plan(const xvec_handle* h, int64_t total, int B) {
     p.act5 = o;   o += align_up((size_t)p.rows_alloc * (n5 > nh ? n5 : nh) * 4);   // also the fp32 output of xvec_tdnn_layer
     // pooling partials: one per (32-row group, utterance) -- or, tdnn_pp16.hip, two per (block of a column, utterance)
     p.part_slots = std::max<int64_t>(p.m_pad / 32 + B + 1, 2 * ((int64_t)h->num_cu + B) + 2);
-    p.part = o;   o += align_up((size_t)p.part_slots * 3 * n5 * 4);   // (addressed with 32-bit offsets: forward_rows checks < 2 GiB)
+    p.part = o;   o += align_up((size_t)p.part_slots * 3 * n5 * 4);   // (addressed with 32-bit offsets: plan_layer checks < 2 GiB)
     p.part_cnt = o; o += align_up((size_t)2 * (h->num_cu + B + 2) * 4);     // tdnn_pp16.hip: frames behind each segment partial
     p.pooled = o; o += align_up((size_t)B * 2 * XVEC_POOL_CHANNELS * 4);
     p.seg6 = o;   o += align_up((size_t)B * h->cfg.x_vector_size * 4);
@@ -181,6 +198,32 @@ void fill_geometry(xvec_handle* h, TdnnGeom* geo, int chunk_pair) {
     }
 }
 
+// The handle's weight buffers on the device and their sizes (0: none), the one list xvec_create allocates and xvec_destroy frees
+template <class F>
+void each_weight_buffer(xvec_handle* h, F&& f) {
+    for (int i = 0; i < XVEC_NUM_TDNN; ++i) {
+        const TdnnGeom& g = h->geo[i];
+        const size_t w16 = (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2;      // one bf16 copy of the weights
+        f(&h->Wp16[i], w16);
+        f(&h->Wr16[i], w16);
+        f(&h->Wp48[i], 2 * w16);
+        f(&h->Wr48[i], 3 * w16);
+        f(&h->Wp[i], (size_t)g.n_pad * g.k_pad * 4);
+        f(&h->Wu[i], g.n_taps == 3 ? (size_t)g.n_pad * 4 * g.kpt_pad * 4 : 0);
+        f(&h->Wp3[i], i > 0 && g.n_taps == 1 ? (size_t)g.n_pad * g.k_pad * 2 * 3 : 0);
+        f(&h->Wraw[i], (size_t)g.cout * g.src_taps * g.src_cin * 4);
+        f(&h->braw[i], (size_t)g.cout * 4);
+        f(&h->vec16[i], (size_t)3 * g.n_pad * 4);
+        f(&h->vec[i], (size_t)3 * g.n_pad * 4);
+    }
+    f(&h->Wp16b, (size_t)h->geo16[0].n_pad * h->geo16[0].k_pad * 2);   // layer 1's copy for the streaming kernel (refold)
+    for (int i = 0; i < 3; ++i) {
+        f(&h->affW[i], (size_t)h->affN[i] * h->affK[i] * 4);
+        f(&h->affB[i], (size_t)h->affN[i] * 4);
+        f(&h->affW3[i], h->affK[i] % 4 == 0 ? (size_t)h->affN[i] * h->affK[i] * 4 : 0);   // (launch_split_pairs: K % 4 == 0)
+    }
+}
+
 int aff_index(int which) { return which == XVEC_SEG6 ? 0 : which == XVEC_SEG7 ? 1 : which == XVEC_OUTPUT ? 2 : -1; }
 
 struct StageTimer {
@@ -202,179 +245,184 @@ struct StageTimer {
 // pp_min_tenths / 10 units of 64 frames (1.8: the crossover with the 128x128 kernel measured in round 3 -- 51 utterances of
 // 300 frames for layers 2-4, 18 for layer 5; the same for bf16x3).  Returns the blocks per 256-channel column, 0 if not.
 int pp_blocks_per_col(const xvec_handle* h, int n_pad, int64_t rows_out) {
-    if (!h->use_pp || n_pad % 256 != 0) return 0;
+    const Policy& pol = h->pol;
+    if (!pol.pp || n_pad % 256 != 0) return 0;
     int bpc = h->num_cu / (n_pad / 256);
-    if (h->pp_cu_pct > 0 && h->pp_cu_pct < 100) bpc = (bpc * h->pp_cu_pct + 50) / 100;      // diagnostic knob: fewer, longer row ranges
+    if (pol.pp_cu_pct > 0 && pol.pp_cu_pct < 100) bpc = (bpc * pol.pp_cu_pct + 50) / 100;   // diagnostic knob: fewer, longer row ranges
     const int64_t units = (rows_out + 63) / 64;
-    return (bpc >= 1 && units >= bpc && 10 * units >= h->pp_min_tenths * (int64_t)bpc) ? bpc : 0;
+    return (bpc >= 1 && units >= bpc && 10 * units >= pol.pp_min_tenths * (int64_t)bpc) ? bpc : 0;
 }
 
-// What run_tdnn launched: kernel family and, for the large-batch mapping, the geometry its pooling partials were written
-// with.  Returned to the caller and handed to finalize_pool explicitly (taken from handle state it was right only
-// as long as layer 5 happened to be the last launch before the finalize, on the one thread using the handle).
-struct Dispatch {
-    int kernel = XVEC_KERNEL_NONE;
-    int64_t pool_units = 0;
-    int pool_bpc = 0;
+// Persistent grid of the 128x128 family (direct, bf16_split3, Winograd): blocks per 128-channel column, and the period of the
+// CU-pair-aware range sizes, which need the full 2-blocks-per-CU grid and whole XCD runs per half (0: off)
+void persistent_grid(const xvec_handle* h, int n_tiles, int64_t groups_total, int* blocks_per_col, int* pair_period) {
+    const int per_col = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cu * h->pol.blocks_per_cu / n_tiles, groups_total));
+    const int nwg = per_col * n_tiles;
+    const bool ok = h->pol.blocks_per_cu == 2 && nwg == 2 * h->num_cu && nwg % 16 == 0 && (nwg / 8) % (2 * n_tiles) == 0;
+    *blocks_per_col = per_col;
+    *pair_period = ok ? (nwg / 8) / n_tiles : 0;
+}
+
+// One frame-level layer call: what it computes (TdnnMode) and on what.
+struct LayerCall {
+    int layer;
+    TdnnMode mode;
+    const void* X;            // input rows (Src::kRows32: the caller's fp32 rows), ldx elements apart
+    int ldx;
+    int64_t x_rows;           // rows of X that layer 1's guarded reads may reach (0: unguarded)
+    void* X16;                // bf16x3 from fp32 rows no kernel of the call reads directly: where their hi / lo split goes
+    int64_t x_plane, y_plane; // bf16x3: bytes from the hi to the lo plane of X (of X16 for fp32 rows) / of the output
+    void* Y;                  // output rows (Dst::kAct, kF32)
+    float* part;              // Dst::kPool: the pooling partials, and the frames behind each (tdnn_pp16.hip)
+    int* part_cnt;
+    RowMap map;               // row layout of the output
+    int64_t rows_out;
 };
 
-// Launch one frame-level layer on flat rows.  The variant selects arithmetic and epilogue; bf16
-// variants use the bf16 packing (64-element chunks) of the layer's weights.
-// x3: bf16x3 arithmetic -- X (and Y, when it is bf16) are two bf16 planes `x_plane` / `y_plane` bytes apart
-int run_tdnn(xvec_handle* h, int layer, TdnnVariant v, const void* X, int ldx, int64_t x_rows, void* Y,
-             int64_t rows_out, const RowMap& out_map, float* part, hipStream_t s, bool x3 = false,
-             int64_t x_plane = 0, int64_t y_plane = 0, int* part_cnt = nullptr, Dispatch* disp = nullptr) {
-    Dispatch d_local;
-    Dispatch& d = disp ? *disp : d_local;
-    const bool in16 = v == TdnnVariant::kBf16 || v == TdnnVariant::kBf16Pool || v == TdnnVariant::kBf16ToF32 ||
-                      v == TdnnVariant::kBf16First || v == TdnnVariant::kBf16FirstToF32 || v == TdnnVariant::kBf16FirstSrc32;
-    const TdnnGeom& g = in16 ? h->geo16[layer] : h->geo[layer];
-    TdnnArgs a;
-    memset(&a, 0, sizeof(a));
-    a.X = X;
-    a.W = h->Wp[layer];
-    a.Wf = h->Wp16[layer];
+enum class Launch { kDirect, kPp16, kFirst, kFirst3, kSplit3, kWino };
+
+// What plan_layer chose for a call: the kernel, its complete arguments, and what the launch reports.
+struct LayerPlan {
+    int layer;
+    Launch launch;
+    int kernel, form;         // XVEC_KERNEL_* / XVEC_FORM_* (xvec_get_dispatch / xvec_get_tdnn_form)
+    TdnnMode mode;            // the call's; Src::kRows16 when bf16x3 layer 1 reads the split of its rows (the caller makes it)
+    TdnnArgs a;               // every launch but Winograd's
+    WinoArgs w;
+    int64_t pool_units;       // tdnn_pp16.hip pooling: the geometry of its segment partials (finalize_pool)
+    int pool_bpc;
+};
+
+// The one dispatch decision of the frame-level layers (host code, no HIP calls): the kernel and form of a call, in the order
+// pp16 -> first3 / first -> bf16_split3 -> Winograd -> direct (the 128x128 kernel), its complete arguments, and the size limits.
+int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
+    const int l = c.layer;
+    const bool bf = c.mode.prec != Prec::kF32, x3 = c.mode.prec == Prec::kBf16x3, pool = c.mode.dst == Dst::kPool;
+    const bool from_act = c.mode.src == Src::kAct;
+    const TdnnGeom& g = bf ? h->geo16[l] : h->geo[l];
+    memset(&lp, 0, sizeof(lp));
+    lp.layer = l;
+    lp.mode = c.mode;
+    lp.kernel = XVEC_KERNEL_TILE128;
+    lp.form = XVEC_FORM_DIRECT;
+    TdnnArgs& a = lp.a;
+    a.X = c.X;
+    a.W = h->Wp[l];
+    a.Wf = x3 ? h->Wp48[l] : h->Wp16[l];
     // plain bf16: the folded constants (bias', 1, 0) -- BatchNorm is deferred into the consumer's weights (refold)
-    const float* vecs = (in16 && !x3) ? h->vec16[layer] : h->vec[layer];
+    const float* vecs = (bf && !x3) ? h->vec16[l] : h->vec[l];
     a.bias = vecs;
     a.scale = vecs + g.n_pad;
     a.shift = vecs + 2 * g.n_pad;
-    a.Y = Y;
-    a.x_rows = x_rows;
-    a.ldx = ldx;
+    a.Y = c.Y;
+    a.x_rows = c.x_rows;
+    a.ldx = c.ldx;
     a.ldy = g.n_pad;
     a.n_taps = g.n_taps;
     a.tap_rows = g.tap_rows;
     a.kpt = g.kpt;
-    a.cpt = g.kpt_pad / (in16 ? 2 * kBK : kBK);
-    a.k_pad = g.k_pad;
+    a.cpt = g.kpt_pad / (bf ? 2 * kBK : kBK);
+    a.k_pad = x3 ? 2 * g.k_pad : g.k_pad;
     a.n_tiles = g.n_pad / 128;
-    a.groups_total = (rows_out + 31) / 32;
-    {
-        int64_t per_col = (int64_t)h->num_cu * h->blocks_per_cu / a.n_tiles;
-        if (per_col < 1) per_col = 1;
-        if (per_col > a.groups_total) per_col = a.groups_total;
-        a.blocks_per_col = (int)per_col;
-        // CU-pair-aware range sizes need the full 2-blocks-per-CU grid and whole XCD runs per half
-        const int nwg = a.blocks_per_col * a.n_tiles;
-        const bool ok = h->blocks_per_cu == 2 && nwg == 2 * h->num_cu && nwg % 16 == 0 &&
-                        (nwg / 8) % (2 * a.n_tiles) == 0;
-        a.pair_period = ok ? (nwg / 8) / a.n_tiles : 0;
-    }
-    a.pool_part = part;
-    a.pool_cnt = part_cnt;
-    a.out_map = out_map;
-    a.span = h->geo[layer].ctx_span;
-    a.terms = 1;
-    {
-        // the kernel addresses its input with 32-bit byte offsets from a per-tile descriptor: the
-        // largest is (rows of a tile + look-ahead + u*span re-basing) * row bytes (+ the lo plane)
-        const int64_t es = (in16 && v != TdnnVariant::kBf16FirstSrc32) ? 2 : 4;   // element size of the rows READ
-        const int64_t reach = ((int64_t)out_map.n_utts * a.span + kRowPadTail) * ldx * es + (x3 ? x_plane : 0);
-        if (reach > 0x7fffffff)
-            return fail(XVEC_ERR_TOO_LARGE, "layer %d: %d utterances x %d channels exceed 32-bit row offsets; split the batch",
-                        layer, out_map.n_utts, ldx);
-    }
-    if (x3) {
-        if (x_plane > 0x3fffffff || y_plane > 0x3fffffff)
-            return fail(XVEC_ERR_TOO_LARGE, "batch too large for bf16x3 (plane offsets must fit 30 bits); split it");
-        a.terms = 2;
-        a.Wf = h->Wp48[layer];
-        a.k_pad = 2 * g.k_pad;
-        a.x_plane_bytes = (int)x_plane;
-        a.y_plane_bytes = (int)y_plane;
-        a.x_bytes = x_rows > 0 ? x_plane + x_rows * (int64_t)ldx * 2 : 0;
-        if (v == TdnnVariant::kBf16FirstSrc32) a.x_bytes = 0;       // the caller's fp32 rows (tdnn_first3): x_rows * ldx * 4
-    }
-    StageTimer t(h, T_L1 + layer, s);
-    h->last_form[layer] = XVEC_FORM_DIRECT;
-    // bf16, wide layers, enough rows to give every CU about two 64-frame units: the 256-channel
-    // ping-pong mapping (tdnn_pp16.hip; bf16x3: the same kernel over three K-tiles per 64-channel slab); everything else
-    // (small batches, layer 1, narrow models, fp32) runs the 128x128 kernel
-    if (layer > 0 && (v == TdnnVariant::kBf16 || v == TdnnVariant::kBf16Pool)) {
-        if (const int bpc = pp_blocks_per_col(h, g.n_pad, rows_out)) {
-            const int64_t units = (rows_out + 63) / 64;
-            a.W = x3 ? h->Wr48[layer] : h->Wr16[layer];
-            a.n_tiles = g.n_pad / 256;
-            a.blocks_per_col = bpc;
-            a.groups_total = units;
-            a.pair_period = 0;
-            d.pool_units = units;
-            d.pool_bpc = bpc;
-            HIP_TRY(launch_tdnn_pp16(a, v == TdnnVariant::kBf16Pool, s));
-            h->last_kernel[layer] = d.kernel = XVEC_KERNEL_PP;
-            return XVEC_OK;
-        }
-    }
-    if (x3 && v == TdnnVariant::kBf16FirstSrc32) {      // bf16x3 layer 1 straight from the fp32 rows: only the streaming kernel does that
-        if (!(h->use_pp && layer == 0 && tdnn_first3_applicable(a)))
-            return fail(XVEC_ERR_STATE, "internal: bf16x3 layer 1 from fp32 rows needs the streaming kernel's shapes");
-        HIP_TRY(launch_tdnn_first3(a, h->num_cu, s));
-        h->last_kernel[layer] = d.kernel = XVEC_KERNEL_FIRST;
-        return XVEC_OK;
-    }
-    if (h->use_pp && layer == 0 && v == TdnnVariant::kBf16FirstSrc32 && tdnn_first_applicable(a)) {
-        a.Wf = h->Wp16b;
-        HIP_TRY(launch_tdnn_first(a, h->num_cu, s));
-        h->last_kernel[layer] = d.kernel = XVEC_KERNEL_FIRST;
-        return XVEC_OK;
-    }
-    // pooling partials of the 128x128 kernels: one slot per (32-row group, utterance), addressed with 32-bit offsets
-    // (tdnn_pp16.hip's segment partials take a 64-bit base per slot and have no such limit)
-    if (part && (size_t)((rows_out + 31) / 32 + out_map.n_utts + 1) * 3 * g.n_pad * 4 > 0x7fffffffull)
-        return fail(XVEC_ERR_TOO_LARGE, "batch too large: pooling partials exceed 2 GiB; split it");
-    // fp32, three equally spaced taps: Winograd F(2,3) along time (tdnn_wino.hip), 2/3 of the direct form's products; the same
-    // kernel family (persistent fp32, 128 x 128 output tiles)
-    // fp32, one tap, large batch: bf16_split3 (tdnn_layer.hip, S3), x = hi + mid + lo and W likewise as bf16 planes, six bf16
-    // products per k-step on the bf16 matrix pipe at 0.375 of the fp32 MFMA time; the same kernel family and epilogues
-    if ((v == TdnnVariant::kF32 || v == TdnnVariant::kF32Pool) && h->use_split3 && h->Wp3[layer] && g.n_taps == 1 &&
-        rows_out >= (int64_t)h->split3_min_rows * h->num_cu) {
+    a.groups_total = (c.rows_out + 31) / 32;
+    persistent_grid(h, a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
+    a.pool_part = c.part;
+    a.pool_cnt = c.part_cnt;
+    a.out_map = c.map;
+    a.span = h->geo[l].ctx_span;
+    a.terms = x3 ? 2 : 1;
+    a.y_plane_bytes = x3 ? (int)c.y_plane : 0;
+    int bpc = 0;
+    if (bf && l > 0 && from_act && c.mode.dst != Dst::kF32 && (bpc = pp_blocks_per_col(h, g.n_pad, c.rows_out))) {
+        // bf16, wide layers, enough rows to give every CU about two 64-frame units: the 256-channel ping-pong mapping
+        // (tdnn_pp16.hip; bf16x3: the same kernel over three K-tiles per 64-channel slab)
+        lp.launch = Launch::kPp16;
+        lp.kernel = XVEC_KERNEL_PP;
+        a.W = x3 ? h->Wr48[l] : h->Wr16[l];
+        a.n_tiles = g.n_pad / 256;
+        a.blocks_per_col = lp.pool_bpc = bpc;
+        a.groups_total = lp.pool_units = (c.rows_out + 63) / 64;
+        a.pair_period = 0;
+    } else if (bf && l == 0 && !from_act && c.mode.dst == Dst::kAct && h->pol.pp &&
+               (x3 ? tdnn_first3_applicable(a) : tdnn_first_applicable(a))) {
+        // layer 1 of the bf16 paths as the streaming kernel (tdnn_first.hip), straight from the fp32 rows
+        lp.launch = x3 ? Launch::kFirst3 : Launch::kFirst;
+        lp.kernel = XVEC_KERNEL_FIRST;
+        if (!x3) a.Wf = h->Wp16b;
+    } else if (x3 && c.mode.src == Src::kRows32) {
+        // no other kernel reads bf16x3 layer 1 from fp32 rows: the 128x128 kernel reads their hi / lo split
+        if (!c.X16) return fail(XVEC_ERR_STATE, "internal: bf16x3 layer 1 from fp32 rows needs the streaming kernel's shapes");
+        lp.mode.src = Src::kRows16;
+        a.X = c.X16;
+    } else if (!bf && from_act && h->pol.split3 && h->Wp3[l] && c.rows_out >= (int64_t)h->pol.split3_min_rows * h->num_cu) {
+        // fp32, one tap (Wp3), large batch: bf16_split3 (tdnn_split3.hip), x = hi + mid + lo and W likewise as bf16 planes, six
+        // bf16 products per k-step on the bf16 matrix pipe at 0.375 of the fp32 MFMA time; the same kernel family and epilogues
+        lp.launch = Launch::kSplit3;
+        lp.form = XVEC_FORM_BF16_SPLIT3;
         a.terms = 3;
-        a.Wf = h->Wp3[layer];
-        HIP_TRY(launch_tdnn(a, v, s));
-        h->last_kernel[layer] = d.kernel = XVEC_KERNEL_TILE128;
-        h->last_form[layer] = XVEC_FORM_BF16_SPLIT3;
-        return XVEC_OK;
-    }
-    if (v == TdnnVariant::kF32 && h->use_wino && h->Wu[layer] && tdnn_wino_applicable(g, ldx)) {
-        WinoArgs w;
-        memset(&w, 0, sizeof(w));
-        w.X = static_cast<const float*>(X);
-        w.U = h->Wu[layer];
+        a.Wf = h->Wp3[l];
+    } else if (!bf && from_act && !pool && h->pol.wino && h->Wu[l] && tdnn_wino_applicable(g, c.ldx)) {
+        // fp32, three equally spaced taps: Winograd F(2,3) along time (tdnn_wino.hip), 2/3 of the direct form's products; the
+        // same kernel family (persistent fp32, 128 x 128 output tiles)
+        lp.launch = Launch::kWino;
+        lp.form = XVEC_FORM_WINOGRAD_F23;
+        WinoArgs& w = lp.w;
+        w.X = static_cast<const float*>(c.X);
+        w.U = h->Wu[l];
         w.bias = a.bias;
         w.scale = a.scale;
         w.shift = a.shift;
-        w.Y = static_cast<float*>(Y);
-        w.ldx = ldx;
+        w.Y = static_cast<float*>(c.Y);
+        w.ldx = c.ldx;
         w.ldy = a.ldy;
         w.cpt = g.kpt_pad / kBK;
         w.k_pad = 4 * g.kpt_pad;
         w.n_tiles = a.n_tiles;
-        w.out_map = out_map;
+        w.out_map = c.map;
         w.span = a.span;
         w.d = g.tap_rows;
-        int64_t pairs;
-        if (out_map.offsets == nullptr) {
-            w.p_fixed = wino_pair_count(out_map.fixed_T - out_map.cum, w.d);
-            pairs = (int64_t)out_map.n_utts * w.p_fixed;
-        } else {
-            pairs = (rows_out >> 1) + (int64_t)out_map.n_utts * w.d;    // pair_base(n_utts), tdnn_wino.hip
-        }
+        w.p_fixed = c.map.offsets ? 0 : wino_pair_count(c.map.fixed_T - c.map.cum, w.d);
+        const int64_t pairs = c.map.offsets ? (c.rows_out >> 1) + (int64_t)c.map.n_utts * w.d     // pair_base(n_utts), tdnn_wino.hip
+                                            : (int64_t)c.map.n_utts * w.p_fixed;
         w.groups_total = (pairs + 31) / 32;
-        int64_t per_col = (int64_t)h->num_cu * h->blocks_per_cu / w.n_tiles;
-        if (per_col < 1) per_col = 1;
-        if (per_col > w.groups_total) per_col = w.groups_total;
-        w.blocks_per_col = (int)per_col;
-        const int nwg = w.blocks_per_col * w.n_tiles;
-        const bool ok = h->blocks_per_cu == 2 && nwg == 2 * h->num_cu && nwg % 16 == 0 && (nwg / 8) % (2 * w.n_tiles) == 0;
-        w.pair_period = ok ? (nwg / 8) / w.n_tiles : 0;
-        HIP_TRY(launch_tdnn_wino(w, s));
-        h->last_kernel[layer] = d.kernel = XVEC_KERNEL_TILE128;
-        h->last_form[layer] = XVEC_FORM_WINOGRAD_F23;
-        return XVEC_OK;
+        persistent_grid(h, w.n_tiles, w.groups_total, &w.blocks_per_col, &w.pair_period);
     }
-    HIP_TRY(launch_tdnn(a, v, s));
-    h->last_kernel[layer] = d.kernel = XVEC_KERNEL_TILE128;
+    const bool rows32 = lp.mode.src == Src::kRows32;
+    const int64_t x_plane = x3 && !rows32 ? c.x_plane : 0;
+    if (x3) {
+        a.x_plane_bytes = (int)x_plane;
+        a.x_bytes = c.x_rows > 0 && !rows32 ? x_plane + c.x_rows * (int64_t)c.ldx * 2 : 0;   // (fp32 rows: x_rows * ldx * 4)
+    }
+    // size limits: the kernels address their input with 32-bit byte offsets from a per-tile descriptor, the largest being
+    // (rows of a tile + look-ahead + u*span re-basing) * row bytes (+ the lo plane)
+    const int64_t es = (bf && !rows32) ? 2 : 4;   // element size of the rows READ
+    if (((int64_t)c.map.n_utts * a.span + kRowPadTail) * c.ldx * es + x_plane > 0x7fffffff)
+        return fail(XVEC_ERR_TOO_LARGE, "layer %d: %d utterances x %d channels exceed 32-bit row offsets; split the batch",
+                    l, c.map.n_utts, c.ldx);
+    if (x3 && (x_plane > 0x3fffffff || c.y_plane > 0x3fffffff))
+        return fail(XVEC_ERR_TOO_LARGE, "batch too large for bf16x3 (plane offsets must fit 30 bits); split it");
+    // pooling partials of the 128x128 kernels: one slot per (32-row group, utterance), addressed with 32-bit offsets
+    // (tdnn_pp16.hip's segment partials take a 64-bit base per slot and have no such limit)
+    if (pool && lp.launch != Launch::kPp16 &&
+        (size_t)((c.rows_out + 31) / 32 + c.map.n_utts + 1) * 3 * g.n_pad * 4 > 0x7fffffffull)
+        return fail(XVEC_ERR_TOO_LARGE, "batch too large: pooling partials exceed 2 GiB; split it");
+    return XVEC_OK;
+}
+
+// Run a planned layer under its stage timer and record what it ran.
+int launch_layer(xvec_handle* h, const LayerPlan& lp, hipStream_t s) {
+    StageTimer t(h, T_L1 + lp.layer, s);
+    const bool pool = lp.mode.dst == Dst::kPool;
+    switch (lp.launch) {
+        case Launch::kPp16: HIP_TRY(launch_tdnn_pp16(lp.a, pool, s)); break;
+        case Launch::kFirst: HIP_TRY(launch_tdnn_first(lp.a, h->num_cu, s)); break;
+        case Launch::kFirst3: HIP_TRY(launch_tdnn_first3(lp.a, h->num_cu, s)); break;
+        case Launch::kSplit3: HIP_TRY(launch_tdnn_split3(lp.a, pool, s)); break;
+        case Launch::kWino: HIP_TRY(launch_tdnn_wino(lp.w, s)); break;
+        case Launch::kDirect: HIP_TRY(launch_tdnn(lp.a, lp.mode, s)); break;
+    }
+    h->last_kernel[lp.layer] = lp.kernel;
+    h->last_form[lp.layer] = lp.form;
     return XVEC_OK;
 }
 
@@ -416,104 +464,96 @@ int check_loaded(const xvec_handle* h, int mode) {
     return XVEC_OK;
 }
 
-// merge the pooling partials layer 5 left (in the form of the kernel that wrote them: `d`, from its run_tdnn) into pooled[B, 3000]
-int finalize_pool(xvec_handle* h, const Dispatch& d, const float* part, const int* part_cnt, const RowMap& map, float* pooled,
-                  hipStream_t s) {
+// merge the pooling partials planned layer 5 left (in the form of the kernel that wrote them) into pooled[B, 3000]
+int finalize_pool(xvec_handle* h, const LayerPlan& l5, float* pooled, hipStream_t s) {
     PoolFinalizeArgs f;
     memset(&f, 0, sizeof(f));
-    f.part = part;
+    f.part = l5.a.pool_part;
     f.out = pooled;
-    f.map = map;
+    f.map = l5.a.out_map;
     f.C = XVEC_POOL_CHANNELS;
     f.n_pad = h->geo[4].n_pad;
     f.sub_rows = 32;
     f.scale = h->vec[4] + f.n_pad;              // the pooling epilogues leave sums of r = relu(z + bias)
     f.shift = h->vec[4] + 2 * f.n_pad;
-    if (d.kernel == XVEC_KERNEL_PP) {               // tdnn_pp16.hip: one partial per (block, utterance, half)
-        f.cnt = part_cnt;
-        f.units_total = d.pool_units;
-        f.blocks_per_col = d.pool_bpc;
+    if (l5.kernel == XVEC_KERNEL_PP) {              // tdnn_pp16.hip: one partial per (block, utterance, half)
+        f.cnt = l5.a.pool_cnt;
+        f.units_total = l5.pool_units;
+        f.blocks_per_col = l5.pool_bpc;
     }
     HIP_TRY(launch_pool_finalize(f, s));
     return XVEC_OK;
 }
 
-// bf16x3 layer 1 can read the caller's fp32 rows itself (tdnn_first3: no hi/lo split pass) when the streaming kernel's
-// shapes hold (the reference's 24 MFCCs x 5 frames -> 512 channels do); run_tdnn checks the same through tdnn_first3_applicable
-bool first3_ok(const xvec_handle* h, const void* x_rows, int ldx) {
-    const TdnnGeom& g = h->geo16[0];
-    return h->use_pp && g.n_pad == 512 && g.k_pad == 128 && g.n_taps == 1 && g.kpt <= 128 && (ldx * 4) % 16 == 0 &&
-           (reinterpret_cast<uintptr_t>(x_rows) & 15) == 0;
+// The five frame-level layers of a batch, planned before anything is enqueued: a batch a size limit refuses leaves the stream
+// and the handle as they were.  x_rows: [total, ldx] packed rows (offs_dev == nullptr: B utterances of fixed_T rows each).
+// Layer 1 reads the caller's rows (guarded against the end of the buffer and the K tail; bf16 rounds them on the way in,
+// bf16x3 reads them as they are or their hi / lo split); every activation buffer holds fp32, bf16 or two bf16 planes in the
+// space of one fp32.  Layer 5 carries the statistics-pooling epilogue: its [frames,1500] output stays on chip.
+int plan_stack(const xvec_handle* h, const float* x_rows, int ldx, const int64_t* offs_dev, int B, int fixed_T, const Plan& p,
+               int dtype, char* ws, LayerPlan (&lp)[XVEC_NUM_TDNN]) {
+    const Prec prec = dtype == XVEC_F32 ? Prec::kF32 : dtype == XVEC_BF16 ? Prec::kBf16 : Prec::kBf16x3;
+    if (prec != Prec::kF32 && p.total > 0x7fffffff) return fail(XVEC_ERR_TOO_LARGE, "too many frames for one bf16 batch; split it");
+    const int nh = h->geo[0].n_pad;
+    LayerCall c;
+    memset(&c, 0, sizeof(c));
+    c.mode = {prec, Src::kRows32, Dst::kAct};
+    c.X = x_rows;
+    c.ldx = ldx;
+    c.x_rows = p.total;
+    c.X16 = ws + p.x16;
+    c.x_plane = p.rows_alloc * (int64_t)ldx * 2;
+    // every layer's output is compact: utterance u keeps len_u - cum frames after `cum` frames of
+    // context have been consumed (4, 8, 14, 14, 14 after layers 1..5)
+    c.map = {offs_dev, B, fixed_T, 0};
+    for (int l = 0; l < XVEC_NUM_TDNN; ++l) {
+        c.layer = l;
+        c.map.cum += h->geo[l].ctx_span;
+        c.rows_out = p.total - (int64_t)B * c.map.cum;
+        if (l == XVEC_NUM_TDNN - 1) {
+            c.mode.dst = Dst::kPool;
+            c.Y = nullptr;
+            c.y_plane = 0;
+            c.part = reinterpret_cast<float*>(ws + p.part);
+            c.part_cnt = reinterpret_cast<int*>(ws + p.part_cnt);
+        } else {
+            c.Y = ws + (l & 1 ? p.actB : p.actA);
+            c.y_plane = p.rows_alloc * (int64_t)nh * 2;          // bytes of one bf16 plane of an activation buffer
+        }
+        if (int rc = plan_layer(h, c, lp[l])) return rc;
+        c.mode.src = Src::kAct;
+        c.X = c.Y;
+        c.ldx = nh;
+        c.x_rows = 0;
+        c.x_plane = c.y_plane;
+    }
+    return XVEC_OK;
 }
 
-// x_rows: [total, ldx] packed rows (offs_host == nullptr: B utterances of fixed_T rows each)
-int forward_rows(xvec_handle* h, const float* x_rows, int ldx, const int64_t* offs_dev, int B, int fixed_T,
-                 const Plan& p, int mode, int dtype, float* out, char* ws, hipStream_t s) {
-    float* actA = reinterpret_cast<float*>(ws + p.actA);
-    float* actB = reinterpret_cast<float*>(ws + p.actB);
-    float* part = reinterpret_cast<float*>(ws + p.part);
-    int* part_cnt = reinterpret_cast<int*>(ws + p.part_cnt);
+// Run the planned stack (x_rows, ldx as planned) and the segment layers of `mode`.
+int forward_rows(xvec_handle* h, const LayerPlan (&lp)[XVEC_NUM_TDNN], const float* x_rows, int ldx, int B, const Plan& p,
+                 int mode, int dtype, float* out, char* ws, hipStream_t s) {
     float* pooled = mode == XVEC_MODE_POOLED ? out : reinterpret_cast<float*>(ws + p.pooled);
     float* s6 = reinterpret_cast<float*>(ws + p.seg6);
     float* s7 = reinterpret_cast<float*>(ws + p.seg7);
-    const int nh = h->geo[0].n_pad;
     int rc;
-    const bool x3 = dtype == XVEC_BF16X3;
-    const bool b16 = dtype == XVEC_BF16 || x3;
-    // layer 1 reads the caller's rows (guarded against the end of the buffer and the K tail); in
-    // bf16 mode the MFCC rows are first rounded to bf16 into the workspace (bf16x3: split into a hi
-    // and a lo plane; every activation buffer then holds two bf16 planes in the space of one fp32).
-    // Layer 5 carries the statistics-pooling epilogue: its [frames,1500] output stays on chip.
-    // (plain bf16: layer 1 reads the fp32 rows itself and rounds them in its staging path; bf16x3 too when the
-    // streaming kernel's shapes hold -- first3_ok -- and otherwise needs the hi/lo split pass)
-    const bool first3 = x3 && first3_ok(h, x_rows, ldx);
-    const TdnnVariant v1 = x3 && !first3 ? TdnnVariant::kBf16First : b16 ? TdnnVariant::kBf16FirstSrc32 : TdnnVariant::kF32First;
-    const TdnnVariant vm = b16 ? TdnnVariant::kBf16 : TdnnVariant::kF32;
-    const TdnnVariant v5 = b16 ? TdnnVariant::kBf16Pool : TdnnVariant::kF32Pool;
-    // every layer's output is compact: utterance u keeps len_u - cum frames after `cum` frames of
-    // context have been consumed (4, 8, 14, 14, 14 after layers 1..5)
-    RowMap map;
-    map.offsets = offs_dev;
-    map.n_utts = B;
-    map.fixed_T = fixed_T;
-    map.cum = 0;
-    void* bufs[2] = {actA, actB};
-    const void* in = x_rows;
-    int ld_in = ldx;
-    const int64_t act_plane = p.rows_alloc * (int64_t)nh * 2;        // bytes of one bf16 plane of an activation buffer
-    int64_t in_plane = 0;
-    if (b16 && p.total > 0x7fffffff) return fail(XVEC_ERR_TOO_LARGE, "too many frames for one bf16 batch; split it");
-    if (x3 && !first3) {    // [total, ldx] fp32 -> bf16 hi and lo planes (same row stride in elements)
+    if (lp[0].mode.src == Src::kRows16) {    // [total, ldx] fp32 -> bf16 hi and lo planes (same row stride in elements)
         StageTimer t(h, T_PACK, s);
-        void* x16 = ws + p.x16;
-        in_plane = p.rows_alloc * (int64_t)ldx * 2;
-        HIP_TRY(launch_pack_rows_split(x_rows, p.total, ldx, ldx, in_plane / 2, x16, s));
-        in = x16;
+        HIP_TRY(launch_pack_rows_split(x_rows, p.total, ldx, ldx, lp[0].a.x_plane_bytes / 2, ws + p.x16, s));
     }
-    Dispatch d5;                                                     // what layer 5 went to: finalize_pool reads its partials
-    for (int l = 0; l < XVEC_NUM_TDNN; ++l) {
-        map.cum += h->geo[l].ctx_span;
-        const int64_t rows_out = p.total - (int64_t)B * map.cum;
-        const TdnnVariant v = l == 0 ? v1 : l == 4 ? v5 : vm;
-        void* out_buf = l == 4 ? nullptr : bufs[l & 1];
-        if ((rc = run_tdnn(h, l, v, in, ld_in, l == 0 ? p.total : 0, out_buf, rows_out, map, l == 4 ? part : nullptr, s,
-                           x3, in_plane, l == 4 ? 0 : act_plane, l == 4 ? part_cnt : nullptr, l == 4 ? &d5 : nullptr)))
-            return rc;
-        in = out_buf;
-        ld_in = nh;
-        in_plane = act_plane;
-    }
+    for (const LayerPlan& l : lp)
+        if ((rc = launch_layer(h, l, s))) return rc;
     {
         StageTimer t(h, T_POOL, s);
-        if ((rc = finalize_pool(h, d5, part, part_cnt, map, pooled, s))) return rc;
+        if ((rc = finalize_pool(h, lp[XVEC_NUM_TDNN - 1], pooled, s))) return rc;
     }
     if (mode == XVEC_MODE_POOLED) return XVEC_OK;
     const int xv = h->cfg.x_vector_size, K6 = 2 * XVEC_POOL_CHANNELS;
     // plain bf16 (parity bar 1e-2): the segment layers' products as bf16x3 (affine.hip); XVEC_BF16X3 promises the fp32
     // bar end to end and keeps the fp32 MFMAs here (x3 segment layers measured 3x the fp32 ones' error: 6e-6)
-    const bool w3 = b16 && !x3;
+    const bool w3 = dtype == XVEC_BF16;
     // the frame-level activations are dead from here on: layers 1-4's buffers serve as split-K scratch
-    float* scr = actA;
+    float* scr = reinterpret_cast<float*>(ws + p.actA);
     const size_t scr_bytes = (p.actB - p.actA) * 2;                 // actA and actB are adjacent
     if (mode == XVEC_MODE_XVEC6) {
         StageTimer t(h, T_SEG6, s);
@@ -578,6 +618,56 @@ int common_checks(xvec_handle* h, const void* x, int B, int mode, int dtype, con
     return check_loaded(h, mode);
 }
 
+// The per-layer entries' common part: arguments, handle state, workspace, and the call on x staged into the layer's native row
+// layout (stride = the producer's n_pad; layer 1: fp32 rows padded to cin_pad).  B and T are checked by the caller.
+int layer_entry(const xvec_handle* h, int layer, const void* x, const void* out, int B, int T, int dtype, void* workspace,
+                size_t workspace_bytes, Plan& p, LayerCall& c) {
+    if (!x || !out || !workspace) return fail(XVEC_ERR_ARG, "null tensor pointer");
+    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return fail(XVEC_ERR_ARG, "unknown dtype %d", dtype);
+    if (!h->tdnn_loaded[layer]) return fail(XVEC_ERR_STATE, "time_context_layers.%d weights not loaded", layer);
+    if (dtype == XVEC_BF16 && !h->folded[layer])
+        return fail(XVEC_ERR_STATE, "time_context_layers.%d: plain bf16 folds the BatchNorm of layer %d into it; load that layer too", layer, layer - 1);
+    p = make_plan(h, (int64_t)B * T, B);
+    if (workspace_bytes < p.bytes)
+        return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
+    char* ws = static_cast<char*>(workspace);
+    const bool x3 = dtype == XVEC_BF16X3;
+    const int span = h->geo[layer].ctx_span;
+    memset(&c, 0, sizeof(c));
+    c.layer = layer;
+    c.mode = {dtype == XVEC_F32 ? Prec::kF32 : x3 ? Prec::kBf16x3 : Prec::kBf16, layer == 0 ? Src::kRows32 : Src::kAct, Dst::kF32};
+    c.ldx = layer == 0 ? h->cin_pad : h->geo[layer - 1].n_pad;
+    c.X = ws + (layer > 0 ? p.actA : x3 ? p.actB : p.xpad);    // (bf16x3 layer 1: the fp32 rows its hi / lo split is made from)
+    c.x_rows = p.total;
+    c.X16 = ws + p.x16;
+    c.x_plane = x3 ? p.rows_alloc * (int64_t)c.ldx * 2 : 0;
+    c.map = {nullptr, B, T, span};
+    c.rows_out = (int64_t)B * (T - span);
+    return XVEC_OK;
+}
+
+// Stage a per-layer entry's input x[B,T,cin] where its planned layer reads it: bf16 / two bf16 planes as in xvec_forward.
+int stage_layer_input(const xvec_handle* h, const LayerCall& c, const LayerPlan& lp, const float* x, int B, int T, const Plan& p,
+                      char* ws, hipStream_t s) {
+    const int l = c.layer, cin = h->geo[l].src_cin;
+    if (c.mode.prec == Prec::kBf16x3) {     // fp32 rows first (padding to ldx), then the hi / lo split unless the layer reads those
+        float* x32 = reinterpret_cast<float*>(ws + p.actB);
+        HIP_TRY(launch_pack_rows(x, nullptr, B, T, cin, c.ldx, x32, false, s));
+        if (lp.mode.src != Src::kRows32)
+            HIP_TRY(launch_pack_rows_split(x32, p.total, c.ldx, c.ldx, c.x_plane / 2, const_cast<void*>(lp.a.X), s));
+        return XVEC_OK;
+    }
+    // plain bf16, layers 2-5: the kernel reads the producing layer's relu output and carries that layer's BatchNorm in its
+    // weights (refold), so the caller's x -- the reference's layer input, BatchNorm applied -- is taken back through it
+    // (layer 1 reads fp32 rows and rounds them itself, exactly as in xvec_forward)
+    const bool b16 = c.mode.prec == Prec::kBf16 && l > 0;
+    const float* un = b16 ? h->vec[l - 1] : nullptr;
+    const int npp = b16 ? h->geo[l - 1].n_pad : 0;
+    HIP_TRY(launch_pack_rows(x, nullptr, B, T, cin, c.ldx, const_cast<void*>(c.X), b16, s, un ? un + npp : nullptr,
+                             un ? un + 2 * npp : nullptr));
+    return XVEC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -606,57 +696,22 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg;
     h->num_cu = prop.multiProcessorCount;
-    {
-        const char* e = getenv("XVEC_BLOCKS_PER_CU");   // diagnostic knob (profiles/ab_env.sh); 2 = what the LDS allows
-        h->blocks_per_cu = e ? atoi(e) : 2;
-        if (h->blocks_per_cu < 1) h->blocks_per_cu = 1;
-        const char* p = getenv("XVEC_PP");
-        h->use_pp = !(p && atoi(p) == 0);
-        const char* wg = getenv("XVEC_WINOGRAD");
-        h->use_wino = !(wg && atoi(wg) == 0);
-        const char* s3 = getenv("XVEC_SPLIT3");
-        h->use_split3 = !(s3 && atoi(s3) == 0);
-        const char* s3m = getenv("XVEC_SPLIT3_MIN_ROWS");
-        h->split3_min_rows = s3m && atoi(s3m) >= 0 ? atoi(s3m) : kSplit3MinRowsPerCu;
-        const char* mt = getenv("XVEC_PP_MIN_TENTHS");
-        h->pp_min_tenths = mt && atoi(mt) > 0 ? atoi(mt) : 18;
-        const char* cp = getenv("XVEC_PP_CU_PCT");
-        h->pp_cu_pct = cp ? atoi(cp) : 0;
-    }
+    h->pol = read_policy();
     h->cin_pad = round_up(cfg->input_size, 4);
     fill_geometry(h, h->geo, 2 * kBK);
     fill_geometry(h, h->geo16, 4 * kBK);
-    for (int i = 0; i < XVEC_NUM_TDNN; ++i) {
-        const TdnnGeom& g = h->geo[i];
-        if (hipMalloc(&h->Wp16[i], (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2) != hipSuccess ||
-            hipMalloc(&h->Wr16[i], (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2) != hipSuccess ||
-            (i == 0 && hipMalloc(&h->Wp16b, (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2) != hipSuccess) ||
-            hipMalloc(&h->Wp48[i], (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2 * 2) != hipSuccess ||
-            hipMalloc(&h->Wr48[i], (size_t)h->geo16[i].n_pad * h->geo16[i].k_pad * 2 * 3) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&h->Wp[i]), (size_t)g.n_pad * g.k_pad * 4) != hipSuccess ||
-            (g.n_taps == 3 && hipMalloc(reinterpret_cast<void**>(&h->Wu[i]), (size_t)g.n_pad * 4 * g.kpt_pad * 4) != hipSuccess) ||
-            (i > 0 && g.n_taps == 1 && hipMalloc(&h->Wp3[i], (size_t)g.n_pad * g.k_pad * 2 * 3) != hipSuccess) ||
-            hipMalloc(reinterpret_cast<void**>(&h->Wraw[i]), (size_t)g.cout * g.src_taps * g.src_cin * 4) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&h->braw[i]), (size_t)g.cout * 4) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&h->vec16[i]), (size_t)3 * g.n_pad * 4) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&h->vec[i]), (size_t)3 * g.n_pad * 4) != hipSuccess) {
-            xvec_destroy(h);
-            return fail(XVEC_ERR_HIP, "hipMalloc of packed weights failed");
-        }
-    }
     const int N[3] = {cfg->x_vector_size, cfg->x_vector_size, cfg->num_classes};
     const int K[3] = {2 * XVEC_POOL_CHANNELS, cfg->x_vector_size, cfg->x_vector_size};
-    for (int i = 0; i < 3; ++i) {
-        h->affN[i] = N[i];
-        h->affK[i] = K[i];
-        if (hipMalloc(reinterpret_cast<void**>(&h->affW[i]), (size_t)N[i] * K[i] * 4) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void**>(&h->affB[i]), (size_t)N[i] * 4) != hipSuccess ||
-            (K[i] % 4 == 0 && hipMalloc(&h->affW3[i], (size_t)N[i] * K[i] * 4) != hipSuccess)) {
-            xvec_destroy(h);
-            return fail(XVEC_ERR_HIP, "hipMalloc of affine weights failed");
-        }
-    }
+    std::copy(N, N + 3, h->affN);
+    std::copy(K, K + 3, h->affK);
     bool ok = true;
+    each_weight_buffer(h, [&](auto** ptr, size_t bytes) {
+        ok = ok && (bytes == 0 || hipMalloc(reinterpret_cast<void**>(ptr), bytes) == hipSuccess);
+    });
+    if (!ok) {
+        xvec_destroy(h);
+        return fail(XVEC_ERR_HIP, "hipMalloc of packed weights failed");
+    }
     for (int i = 0; i < 2 && ok; ++i)
         ok = hipEventCreateWithFlags(&h->offs_evt[i], hipEventDisableTiming) == hipSuccess &&
              hipHostMalloc(reinterpret_cast<void**>(&h->offs_pinned[i]), (size_t)(kMaxUtts + 1) * 8,
@@ -675,25 +730,10 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
 
 void xvec_destroy(xvec_handle* h) {
     if (!h) return;
-    for (int i = 0; i < XVEC_NUM_TDNN; ++i) {
-        if (h->Wp[i]) (void)hipFree(h->Wp[i]);
-        if (h->Wu[i]) (void)hipFree(h->Wu[i]);
-        if (h->Wp16[i]) (void)hipFree(h->Wp16[i]);
-        if (h->Wr16[i]) (void)hipFree(h->Wr16[i]);
-        if (h->Wp48[i]) (void)hipFree(h->Wp48[i]);
-        if (h->Wp3[i]) (void)hipFree(h->Wp3[i]);
-        if (h->Wr48[i]) (void)hipFree(h->Wr48[i]);
-        if (h->vec[i]) (void)hipFree(h->vec[i]);
-        if (h->Wraw[i]) (void)hipFree(h->Wraw[i]);
-        if (h->braw[i]) (void)hipFree(h->braw[i]);
-        if (h->vec16[i]) (void)hipFree(h->vec16[i]);
-    }
-    if (h->Wp16b) (void)hipFree(h->Wp16b);
-    for (int i = 0; i < 3; ++i) {
-        if (h->affW[i]) (void)hipFree(h->affW[i]);
-        if (h->affB[i]) (void)hipFree(h->affB[i]);
-        if (h->affW3[i]) (void)hipFree(h->affW3[i]);
-    }
+    each_weight_buffer(h, [](auto** ptr, size_t) {
+        if (*ptr) (void)hipFree(*ptr);
+        *ptr = nullptr;
+    });
     for (int i = 0; i < 2; ++i) {
         if (h->offs_pinned[i]) (void)hipHostFree(h->offs_pinned[i]);
         if (h->offs_evt[i]) (void)hipEventDestroy(h->offs_evt[i]);
@@ -803,14 +843,16 @@ int xvec_forward(xvec_handle* h, const float* x, const int32_t* lengths_host, in
         const Plan p = make_plan(h, (int64_t)B * T, B);
         if (workspace_bytes < p.bytes)
             return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
-        const float* rows = x;
-        if (h->cin_pad != C) {   // channel count not a multiple of 4: pad rows once
+        float* xp = reinterpret_cast<float*>(ws + p.xpad);
+        const bool pad = h->cin_pad != C;                 // channel count not a multiple of 4: pad rows once
+        const float* rows = pad ? xp : x;
+        LayerPlan lp[XVEC_NUM_TDNN];
+        if ((rc = plan_stack(h, rows, h->cin_pad, nullptr, B, T, p, dtype, ws, lp))) return rc;
+        if (pad) {
             StageTimer t(h, T_PACK, s);
-            float* xp = reinterpret_cast<float*>(ws + p.xpad);
             HIP_TRY(launch_pack_rows(x, nullptr, B, T, C, h->cin_pad, xp, false, s));
-            rows = xp;
         }
-        return forward_rows(h, rows, h->cin_pad, nullptr, B, T, p, mode, dtype, out, ws, s);
+        return forward_rows(h, lp, rows, h->cin_pad, B, p, mode, dtype, out, ws, s);
     }
 
     // ragged: pack the valid frames, run the stack on sum(lengths) rows only
@@ -824,14 +866,16 @@ int xvec_forward(xvec_handle* h, const float* x, const int32_t* lengths_host, in
     const Plan p = make_plan(h, total, B);
     if (workspace_bytes < p.bytes)
         return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
-    if ((rc = stage_offsets(h, nullptr, lengths_host, B, reinterpret_cast<int64_t*>(ws + p.offs), s))) return rc;
-    const int64_t* offs_dev = reinterpret_cast<const int64_t*>(ws + p.offs);
+    int64_t* offs_dev = reinterpret_cast<int64_t*>(ws + p.offs);
     float* xp = reinterpret_cast<float*>(ws + p.xpad);
+    LayerPlan lp[XVEC_NUM_TDNN];
+    if ((rc = plan_stack(h, xp, h->cin_pad, offs_dev, B, 0, p, dtype, ws, lp))) return rc;
+    if ((rc = stage_offsets(h, nullptr, lengths_host, B, offs_dev, s))) return rc;
     {
         StageTimer t(h, T_PACK, s);
         HIP_TRY(launch_pack_rows(x, offs_dev, B, T, C, h->cin_pad, xp, false, s));
     }
-    return forward_rows(h, xp, h->cin_pad, offs_dev, B, 0, p, mode, dtype, out, ws, s);
+    return forward_rows(h, lp, xp, h->cin_pad, B, p, mode, dtype, out, ws, s);
 }
 
 int xvec_forward_packed(xvec_handle* h, const float* x_packed, const int64_t* offsets_host, int32_t B, int mode,
@@ -854,98 +898,62 @@ int xvec_forward_packed(xvec_handle* h, const float* x_packed, const int64_t* of
     const Plan p = make_plan(h, total, B);
     if (workspace_bytes < p.bytes)
         return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
-    if ((rc = stage_offsets(h, offsets_host, nullptr, B, reinterpret_cast<int64_t*>(ws + p.offs), s))) return rc;
-    const int64_t* offs_dev = reinterpret_cast<const int64_t*>(ws + p.offs);
-    const float* rows = x_packed;
     const int C = h->cfg.input_size;
-    if (h->cin_pad != C) {
-        if (total > 0x7fffffff) return fail(XVEC_ERR_ARG, "too many frames");
+    int64_t* offs_dev = reinterpret_cast<int64_t*>(ws + p.offs);
+    float* xp = reinterpret_cast<float*>(ws + p.xpad);
+    const bool pad = h->cin_pad != C;
+    if (pad && total > 0x7fffffff) return fail(XVEC_ERR_ARG, "too many frames");
+    const float* rows = pad ? xp : x_packed;
+    LayerPlan lp[XVEC_NUM_TDNN];
+    if ((rc = plan_stack(h, rows, h->cin_pad, offs_dev, B, 0, p, dtype, ws, lp))) return rc;
+    if ((rc = stage_offsets(h, offsets_host, nullptr, B, offs_dev, s))) return rc;
+    if (pad) {
         StageTimer t(h, T_PACK, s);
-        float* xp = reinterpret_cast<float*>(ws + p.xpad);
         HIP_TRY(launch_pack_rows(x_packed, nullptr, 1, (int)total, C, h->cin_pad, xp, false, s));
-        rows = xp;
     }
-    return forward_rows(h, rows, h->cin_pad, offs_dev, B, 0, p, mode, dtype, out, ws, s);
+    return forward_rows(h, lp, rows, h->cin_pad, B, p, mode, dtype, out, ws, s);
 }
 
 int xvec_tdnn_layer(xvec_handle* h, int layer, const float* x, int32_t B, int32_t T, int dtype, float* y,
                     void* workspace, size_t workspace_bytes, xvec_stream stream) {
     if (!h || layer < 0 || layer >= XVEC_NUM_TDNN) return fail(XVEC_ERR_ARG, "bad handle or layer %d", layer);
-    if (!x || !y || !workspace) return fail(XVEC_ERR_ARG, "null tensor pointer");
-    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return fail(XVEC_ERR_ARG, "unknown dtype %d", dtype);
-    if (!h->tdnn_loaded[layer]) return fail(XVEC_ERR_STATE, "time_context_layers.%d weights not loaded", layer);
-    if (dtype == XVEC_BF16 && !h->folded[layer])
-        return fail(XVEC_ERR_STATE, "time_context_layers.%d: plain bf16 folds the BatchNorm of layer %d into it; load that layer too", layer, layer - 1);
-    DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
-    HIP_TRY(guard.enter(h->cfg.device));
     const TdnnGeom& g = h->geo[layer];
     if (B < 1 || T <= g.ctx_span) return fail(XVEC_ERR_ARG, "need B>=1 and T>%d (got B=%d T=%d)", g.ctx_span, B, T);
-    const Plan p = make_plan(h, (int64_t)B * T, B);
-    if (workspace_bytes < p.bytes)
-        return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
+    Plan p;
+    LayerCall c;
+    int rc = layer_entry(h, layer, x, y, B, T, dtype, workspace, workspace_bytes, p, c);
+    if (rc) return rc;
+    DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
+    HIP_TRY(guard.enter(h->cfg.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    // bf16 mode: activations between layers are bf16 (layer 1 still reads fp32 MFCCs); the result is
-    // widened back to fp32 for the caller
-    const bool x3 = dtype == XVEC_BF16X3;
-    const bool b16 = dtype == XVEC_BF16;
-    const bool in16 = b16 || x3;
-    // stage the compact input into the layer's native row layout (stride = producer's n_pad)
-    const int ldx = (layer == 0) ? h->cin_pad : h->geo[layer - 1].n_pad;
-    // (plain bf16 layer 1 reads fp32 rows and rounds them itself, exactly as in xvec_forward)
-    const bool rows16 = in16 && !(b16 && layer == 0);
-    void* xin = ws + (layer == 0 ? (rows16 ? p.x16 : p.xpad) : p.actA);
-    int64_t x_plane = 0;
-    const bool l0_first3 = x3 && layer == 0 && first3_ok(h, ws + p.actB, ldx);   // layer 1 as xvec_forward runs it (tdnn_first3)
-    if (x3) {   // fp32 rows first (padding to ldx), then the hi/lo split; bf16x3 returns fp32 directly
-        void* x32 = ws + p.actB;
-        HIP_TRY(launch_pack_rows(x, nullptr, B, T, g.src_cin, ldx, x32, false, s));
-        x_plane = p.rows_alloc * (int64_t)ldx * 2;
-        if (!l0_first3) HIP_TRY(launch_pack_rows_split(static_cast<const float*>(x32), p.total, ldx, ldx, x_plane / 2, xin, s));
-    } else {
-        // plain bf16, layers 2-5: the kernel reads the producing layer's relu output and carries that layer's BatchNorm in its
-        // weights (refold), so the caller's x -- the reference's layer input, BatchNorm applied -- is taken back through it
-        const float* un = (b16 && layer > 0) ? h->vec[layer - 1] : nullptr;
-        const int npp = layer > 0 ? h->geo[layer - 1].n_pad : 0;
-        HIP_TRY(launch_pack_rows(x, nullptr, B, T, g.src_cin, ldx, xin, rows16, s, un ? un + npp : nullptr, un ? un + 2 * npp : nullptr));
+    const bool b16 = c.mode.prec == Prec::kBf16;
+    // The caller gets fp32.  Plain bf16 keeps its bf16 activation, widened with this layer's BatchNorm.  bf16x3 runs the
+    // layer as the whole path does where a kernel of its own writes the two bf16 planes the next layer reads (tdnn_first3,
+    // tdnn_pp16.hip at its batch sizes) and joins them (layer 5 writes fp32 from the 128x128 kernel: the whole path pools it).
+    c.Y = ws + p.act5;
+    LayerPlan lp;
+    bool planes = false;
+    if (c.mode.prec == Prec::kBf16x3 && layer < XVEC_NUM_TDNN - 1) {
+        LayerCall cp = c;
+        cp.mode.dst = Dst::kAct;
+        cp.y_plane = p.rows_alloc * (int64_t)g.n_pad * 2;
+        rc = plan_layer(h, cp, lp);
+        planes = lp.launch == Launch::kFirst3 || lp.launch == Launch::kPp16;
+        if (planes && rc) return rc;
     }
-    void* yflat = ws + (layer == 4 || x3 ? p.act5 : p.actB);
-    const TdnnVariant v = layer == 0 ? (b16 ? TdnnVariant::kBf16FirstSrc32 : x3 ? TdnnVariant::kBf16FirstToF32 : TdnnVariant::kF32First)
-                                     : (b16 ? TdnnVariant::kBf16 : x3 ? TdnnVariant::kBf16ToF32 : TdnnVariant::kF32);
-    RowMap map;
-    map.offsets = nullptr;
-    map.n_utts = B;
-    map.fixed_T = T;
-    map.cum = g.ctx_span;
+    if (!planes) {
+        if (b16) c.mode.dst = Dst::kAct;
+        if ((rc = plan_layer(h, c, lp))) return rc;
+    }
+    if ((rc = stage_layer_input(h, c, lp, x, B, T, p, ws, s)) || (rc = launch_layer(h, lp, s))) return rc;
     const int To = T - g.ctx_span;
-    if (l0_first3) {    // fp32 rows in, the two bf16 planes out, joined for the caller
-        const int64_t y_plane = p.rows_alloc * (int64_t)g.n_pad * 2;
-        void* y16 = ws + p.actA;
-        int rc = run_tdnn(h, layer, TdnnVariant::kBf16FirstSrc32, ws + p.actB, ldx, p.total, y16, (int64_t)B * To, map, nullptr,
-                          s, true, 0, y_plane);
-        if (rc) return rc;
-        HIP_TRY(launch_unpack_rows_split(y16, y_plane / 2, g.n_pad, B, To, To, g.cout, y, s));
-        return XVEC_OK;
+    if (planes) {
+        HIP_TRY(launch_unpack_rows_split(c.Y, lp.a.y_plane_bytes / 2, g.n_pad, B, To, To, g.cout, y, s));
+    } else {
+        HIP_TRY(launch_unpack_rows(c.Y, b16, g.n_pad, B, To, To, g.cout, y, s, b16 ? h->vec[layer] + g.n_pad : nullptr,
+                                   b16 ? h->vec[layer] + 2 * g.n_pad : nullptr));
     }
-    // bf16x3, layers 2-4 at the sizes xvec_forward gives to the large-batch kernel: that kernel, with its output as
-    // the two bf16 planes the next layer would read, joined (hi + lo) for the caller -- so that the per-layer entry runs
-    // what the whole path runs; otherwise the 128x128 kernel writes fp32 directly
-    if (x3 && layer > 0 && layer < XVEC_NUM_TDNN - 1) {
-        if (pp_blocks_per_col(h, h->geo16[layer].n_pad, (int64_t)B * To)) {
-            const int64_t y_plane = p.rows_alloc * (int64_t)g.n_pad * 2;
-            void* y16 = ws + p.actB;
-            int rc = run_tdnn(h, layer, TdnnVariant::kBf16, xin, ldx, p.total, y16, (int64_t)B * To, map, nullptr, s, true,
-                              x_plane, y_plane);
-            if (rc) return rc;
-            HIP_TRY(launch_unpack_rows_split(y16, y_plane / 2, g.n_pad, B, To, To, g.cout, y, s));
-            return XVEC_OK;
-        }
-    }
-    int rc = run_tdnn(h, layer, v, xin, ldx, p.total, yflat, (int64_t)B * To, map, nullptr, s, x3, x_plane, 0);
-    if (rc) return rc;
-    // (plain bf16 stored relu(z + bias'): this layer's BatchNorm is applied here, in fp32, as its consumer's weights would)
-    HIP_TRY(launch_unpack_rows(yflat, b16, g.n_pad, B, To, To, g.cout, y, s, b16 ? h->vec[layer] + g.n_pad : nullptr,
-                               b16 ? h->vec[layer] + 2 * g.n_pad : nullptr));
     return XVEC_OK;
 }
 
@@ -953,47 +961,24 @@ int xvec_tdnn_pool_layer(xvec_handle* h, const float* x, int32_t B, int32_t T, i
                          size_t workspace_bytes, xvec_stream stream) {
     const int layer = XVEC_NUM_TDNN - 1;
     if (!h) return fail(XVEC_ERR_ARG, "null handle");
-    if (!x || !out || !workspace) return fail(XVEC_ERR_ARG, "null tensor pointer");
-    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return fail(XVEC_ERR_ARG, "unknown dtype %d", dtype);
-    if (!h->tdnn_loaded[layer]) return fail(XVEC_ERR_STATE, "time_context_layers.%d weights not loaded", layer);
-    if (dtype == XVEC_BF16 && !h->folded[layer])
-        return fail(XVEC_ERR_STATE, "time_context_layers.%d: plain bf16 folds the BatchNorm of layer %d into it; load that layer too", layer, layer - 1);
+    const int span = h->geo[layer].ctx_span;
+    if (B < 1 || B > kMaxUtts || T <= span) return fail(XVEC_ERR_ARG, "need 1<=B<=%d and T>%d (got B=%d T=%d)", kMaxUtts, span, B, T);
+    Plan p;
+    LayerCall c;
+    int rc = layer_entry(h, layer, x, out, B, T, dtype, workspace, workspace_bytes, p, c);
+    if (rc) return rc;
     DeviceGuard guard;
     HIP_TRY(guard.enter(h->cfg.device));
-    const TdnnGeom& g = h->geo[layer];
-    if (B < 1 || B > kMaxUtts || T <= g.ctx_span) return fail(XVEC_ERR_ARG, "need 1<=B<=%d and T>%d (got B=%d T=%d)", kMaxUtts, g.ctx_span, B, T);
-    const Plan p = make_plan(h, (int64_t)B * T, B);
-    if (workspace_bytes < p.bytes)
-        return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
-    const bool x3 = dtype == XVEC_BF16X3, in16 = x3 || dtype == XVEC_BF16;
-    // the input in the layer's native row layout (the producer's n_pad; bf16 / two bf16 planes as in xvec_forward)
-    const int ldx = h->geo[layer - 1].n_pad;
-    void* xin = ws + p.actA;
-    int64_t x_plane = 0;
-    if (x3) {
-        void* x32 = ws + p.actB;
-        HIP_TRY(launch_pack_rows(x, nullptr, B, T, g.src_cin, ldx, x32, false, s));
-        x_plane = p.rows_alloc * (int64_t)ldx * 2;
-        HIP_TRY(launch_pack_rows_split(static_cast<const float*>(x32), p.total, ldx, ldx, x_plane / 2, xin, s));
-    } else {
-        const float* un = dtype == XVEC_BF16 ? h->vec[layer - 1] : nullptr;     // plain bf16: see xvec_tdnn_layer
-        const int npp = h->geo[layer - 1].n_pad;
-        HIP_TRY(launch_pack_rows(x, nullptr, B, T, g.src_cin, ldx, xin, in16, s, un ? un + npp : nullptr, un ? un + 2 * npp : nullptr));
-    }
-    RowMap map;
-    map.offsets = nullptr;
-    map.n_utts = B;
-    map.fixed_T = T;
-    map.cum = g.ctx_span;
-    float* part = reinterpret_cast<float*>(ws + p.part);
-    int* part_cnt = reinterpret_cast<int*>(ws + p.part_cnt);
-    Dispatch d5;
-    int rc = run_tdnn(h, layer, in16 ? TdnnVariant::kBf16Pool : TdnnVariant::kF32Pool, xin, ldx, 0, nullptr,
-                      (int64_t)B * (T - g.ctx_span), map, part, s, x3, x_plane, 0, part_cnt, &d5);
-    if (rc) return rc;
-    return finalize_pool(h, d5, part, part_cnt, map, out, s);
+    c.mode.dst = Dst::kPool;
+    c.x_rows = 0;
+    c.part = reinterpret_cast<float*>(ws + p.part);
+    c.part_cnt = reinterpret_cast<int*>(ws + p.part_cnt);
+    LayerPlan lp;
+    if ((rc = plan_layer(h, c, lp)) || (rc = stage_layer_input(h, c, lp, x, B, T, p, ws, s)) || (rc = launch_layer(h, lp, s)))
+        return rc;
+    return finalize_pool(h, lp, out, s);
 }
 
 int xvec_stat_pool(const float* x, const int32_t* lengths_dev, int32_t B, int32_t T, int32_t C, float* out,

@@ -113,20 +113,16 @@ struct TdnnArgs {
     int64_t x_bytes;          // guarded variant: readable bytes from X (0: x_rows * ldx * element size)
 };
 
-// kernel instantiations: input/weight arithmetic x epilogue
-enum class TdnnVariant {
-    kF32First,        // fp32, guarded reads of the caller's rows (layer 1)
-    kF32,             // fp32 -> fp32
-    kF32Pool,         // fp32 -> pooling partials only (layer 5)
-    kBf16First,       // layer 1 of the bf16 path: guarded reads of the bf16-converted MFCC rows
-    kBf16FirstSrc32,  // the same reading the caller's fp32 rows, rounded to bf16 on the way in (no pack pass)
-    kBf16,            // bf16 -> bf16
-    kBf16Pool,        // bf16 -> pooling partials only
-    kBf16ToF32,       // bf16 -> fp32 (per-layer test entry: layer 5, and every layer in bf16x3)
-    kBf16FirstToF32   // layer 1, guarded, bf16 -> fp32 (per-layer test entry in bf16x3)
-};
-hipError_t launch_tdnn(const TdnnArgs& a, TdnnVariant v, hipStream_t s);
-// kF32 / kF32Pool of a one-tap layer with terms == 3 (launch_tdnn forwards them): tdnn_split3.hip
+// What one frame-level layer call computes (the host planner, xvec_api.hip, picks the kernel and form from it; launch_tdnn the
+// 128x128 kernel's template flags): its precision (bf16x3: fp32 values as two bf16 planes hi + lo); where it reads -- layer 1's
+// guarded reads of the caller's fp32 rows (bf16: rounded on the way in) or of bf16 rows made from them (bf16x3: their hi / lo
+// split), or the previous layer's activation; what it writes -- the next layer's activation, fp32 for a caller, or pooling partials
+enum class Prec { kF32, kBf16, kBf16x3 };
+enum class Src { kRows32, kRows16, kAct };
+enum class Dst { kAct, kF32, kPool };
+struct TdnnMode { Prec prec; Src src; Dst dst; };
+hipError_t launch_tdnn(const TdnnArgs& a, TdnnMode m, hipStream_t s);
+// bf16_split3 form of an fp32 one-tap layer (terms == 3), store or pooling epilogue: tdnn_split3.hip
 hipError_t launch_tdnn_split3(const TdnnArgs& a, bool pool, hipStream_t s);
 // Large-batch bf16 mapping (tdnn_pp16.hip, v_mfma_f32_16x16x32_bf16): 256-channel columns, 64-frame units.  Reads TdnnArgs with
 //   W = K-tile major bf16 [n_pad/256][k_pad/64][256][64] (K order as the fp32 packing, 64-element chunks), n_tiles = n_pad / 256,
@@ -142,8 +138,8 @@ hipError_t launch_tdnn_first(const TdnnArgs& a, int num_cu, hipStream_t s);
 // ... and of the bf16x3 path: terms == 2, Wf = the bf16x3 fragment stream, Y = two bf16 planes y_plane_bytes apart; X the caller's fp32 rows
 bool tdnn_first3_applicable(const TdnnArgs& a);
 hipError_t launch_tdnn_first3(const TdnnArgs& a, int num_cu, hipStream_t s);
-// bf16_split3 form of an fp32 1-tap layer (launch_tdnn with terms == 3, kF32 / kF32Pool): Wf = three bf16 planes hi | mid | lo
-// per (32-channel column tile, 16-wide k-step), fragment-major, 3 x n_pad x k_pad bf16 (pack.hip)
+// weights of the bf16_split3 form (launch_tdnn_split3): Wf = three bf16 planes hi | mid | lo per (32-channel column tile,
+// 16-wide k-step), fragment-major, 3 x n_pad x k_pad bf16 (pack.hip)
 hipError_t launch_pack_tdnn_split3(const float* W, const TdnnGeom& geo, void* Wf3, hipStream_t s);
 // K-tile major bf16 copy of the packed weights for it
 // (in_scale: nullptr, or the producing layer's folded BatchNorm scale per input channel -- plain bf16 defers BatchNorm, pack.hip)
@@ -155,7 +151,7 @@ hipError_t launch_fold_bias(const float* W, const float* bias, const float* in_s
 hipError_t launch_pack_tdnn_rows_bf16x3(const float* W, const TdnnGeom& geo, void* Wr48, hipStream_t s);
 
 // fp32 layer with three equally spaced taps as Winograd F(2,3) along time (tdnn_wino.hip): two outputs (t, t+d) of one
-// utterance per GEMM row ("pair"), four products V_k . U_k^T, K = cin each.  Epilogue as launch_tdnn's kF32 variant.
+// utterance per GEMM row ("pair"), four products V_k . U_k^T, K = cin each.  Epilogue as launch_tdnn's fp32 store variant.
 struct WinoArgs {
     const float* X;           // [rows][ldx] fp32, the layer's input layout (RowMap of the output + u*span)
     const float* U;           // [n_pad][k_pad]: U_0..U_3 with K in (chunk kc, product k) order (launch_pack_wino)

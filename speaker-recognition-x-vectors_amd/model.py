@@ -491,7 +491,7 @@ class XVectorModel(nn.Module):
     def last_forms(self, device=None) -> list:
         """Arithmetic form of the last launch of each frame-level layer: "direct" | "winograd_f23" (fp32 layers with three
         equally spaced taps, csrc/tdnn_wino.hip; XVEC_WINOGRAD=0 at engine creation forces "direct") | "bf16_split3" (fp32
-        one-tap layers at large batches, three exact bf16 pieces per operand, csrc/tdnn_layer.hip; XVEC_SPLIT3=0 forces
+        one-tap layers at large batches, three exact bf16 pieces per operand, csrc/tdnn_split3.hip; XVEC_SPLIT3=0 forces
         "direct")."""
         dev = torch.device(device) if device is not None else next(self.parameters()).device
         eng = self._engine(dev)

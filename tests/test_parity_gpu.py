@@ -522,9 +522,12 @@ def test_bf16x3_layers_and_full_size(gpu_model, sd42, synth):
     _hip.lib.xvec_workspace_bytes.restype = C.c_size_t
     n = _hip.lib.xvec_workspace_bytes(eng.h, C.c_int64(65535 * 16), C.c_int32(65535))
     ws = torch.empty(n, dtype=torch.uint8, device=DEV)
+    dispatch, forms = m.last_dispatch(), m.last_forms()
     rc = _hip.lib.xvec_forward(eng.h, C.c_void_p(big.data_ptr()), None, 65535, 16, 6, 2, C.c_void_p(outb.data_ptr()),
                                C.c_void_p(ws.data_ptr()), C.c_size_t(n), None)
     assert rc == _hip.ERR_TOO_LARGE and "bf16x3" in _hip.last_error()
+    # every layer is planned before the first launch: the refused call ran nothing
+    assert m.last_dispatch() == dispatch and m.last_forms() == forms
 
 
 
