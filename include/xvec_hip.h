@@ -199,12 +199,20 @@ enum {
 int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n);
 /* Which arithmetic form the LAST launch of each frame-level layer used: forms[0..4], *n = 5.  XVEC_FORM_WINOGRAD_F23: an fp32
  * layer with three equally spaced taps (layers 2 and 3 of the reference) as Winograd F(2,3) along time -- four products for
- * two output frames instead of six (csrc/tdnn_wino.hip).  XVEC_FORM_BF16_SPLIT3: an fp32 layer with one tap (layers 4 and 5)
+ * two output frames instead of six -- with either operand scheme: fp32 (csrc/tdnn_wino.hip) or bf16_split3 at large batches
+ * (csrc/tdnn_wino_s3.hip); xvec_get_tdnn_operands tells them apart.  XVEC_FORM_BF16_SPLIT3: an fp32 layer with one tap (layers 4 and 5)
  * at a large batch, activations and weights split exactly into three bf16 pieces each, six bf16 products per k-step on the
  * bf16 matrix pipe (csrc/tdnn_layer.hip).  Every other layer and precision is direct.  XVEC_WINOGRAD=0 / XVEC_SPLIT3=0 in the
  * environment at xvec_create force the direct form. */
 enum { XVEC_FORM_DIRECT = 0, XVEC_FORM_WINOGRAD_F23 = 1, XVEC_FORM_BF16_SPLIT3 = 2 };
 int xvec_get_tdnn_form(const xvec_handle* h, int* forms, int* n);
+/* Which operand scheme the LAST launch of each frame-level layer fed the matrix pipe: operands[0..4], *n = 5.
+ * XVEC_OPERANDS_FP32: fp32 MFMAs.  XVEC_OPERANDS_BF16 / _BF16X3: the bf16 and bf16x3 precisions (xvec_cfg).
+ * XVEC_OPERANDS_BF16_SPLIT3: an fp32 layer whose operands are split exactly into three bf16 pieces each (six bf16 products
+ * per k-step): the bf16_split3 form of layers 4-5 and the Winograd form of layers 2-3 at large batches.  XVEC_WINO_SPLIT3=0
+ * at xvec_create keeps the Winograd form on fp32 operands. */
+enum { XVEC_OPERANDS_FP32 = 0, XVEC_OPERANDS_BF16 = 1, XVEC_OPERANDS_BF16X3 = 2, XVEC_OPERANDS_BF16_SPLIT3 = 3 };
+int xvec_get_tdnn_operands(const xvec_handle* h, int* operands, int* n);
 
 /* ---- next row N3: MFCC front end (the step in front of the path) ----------------------------
  * python_speech_features.mfcc as the reference calls it in its DataLoader workers

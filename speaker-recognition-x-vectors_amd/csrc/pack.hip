@@ -89,6 +89,39 @@ hipError_t launch_pack_wino(const float* W, const TdnnGeom& geo, float* Wu, hipS
     return hipGetLastError();
 }
 
+// The same U_k for the bf16_split3 Winograd kernel (tdnn_wino_s3.hip): U_k formed in fp64 as above, then split into three
+// bf16 pieces greedily in fp64 (hi = bf16(U), mid = bf16(U - hi), lo = bf16(U - hi - mid): the pieces carry the fp64 value to
+// about 2^-25 relative, no fp32 rounding in between), fragment-major: 1 KiB block ((ct * ksteps + ks) * 4 + k) * 3 + plane of
+// (32-channel column tile ct, 16-wide k-step ks, product k), lane (r, h) element j = piece of U_k[32 ct + r][16 ks + 8 h + j].
+__global__ void pack_wino_split3_kernel(const float* __restrict__ W, TdnnGeom g, __bf16* __restrict__ Wf) {
+    const int ksteps = g.kpt_pad / 16;
+    const int64_t total = (int64_t)g.n_pad * g.kpt_pad * 4 * 3;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t blk = i >> 9;
+        const int within = (int)(i & 511), lane = within >> 3, j = within & 7;
+        const int plane = (int)(blk % 3), k = (int)((blk / 3) & 3);
+        const int64_t kb = blk / 12;
+        const int ct = (int)(kb / ksteps), ks = (int)(kb % ksteps);
+        const int n = ct * 32 + (lane & 31), c = ks * 16 + 8 * (lane >> 5) + j;
+        double v = 0.0;
+        if (n < g.cout && c < g.src_cin) {
+            const float* row = W + (int64_t)n * (g.src_taps * g.src_cin) + c;
+            const double w0 = row[0], w1 = row[g.src_cin], w2 = row[2 * g.src_cin];
+            v = k == 0 ? w0 : k == 1 ? 0.5 * ((w0 + w1) + w2) : k == 2 ? 0.5 * ((w0 - w1) + w2) : w2;
+        }
+        const __bf16 hi = (__bf16)v;
+        const double r1 = v - (double)(float)hi;
+        const __bf16 mid = (__bf16)r1;
+        Wf[i] = plane == 0 ? hi : plane == 1 ? mid : (__bf16)(r1 - (double)(float)mid);
+    }
+}
+
+hipError_t launch_pack_wino_split3(const float* W, const TdnnGeom& geo, void* Wu3, hipStream_t s) {
+    if (geo.src_taps != 3 || geo.kpt_pad % 16 != 0 || geo.n_pad % 32 != 0) return hipErrorInvalidValue;
+    pack_wino_split3_kernel<<<1024, 256, 0, s>>>(W, geo, static_cast<__bf16*>(Wu3));
+    return hipGetLastError();
+}
+
 // Same matrix in bf16, fragment-major for v_mfma_f32_32x32x16_bf16: the 64 lanes' B operands of one
 // (32-channel column tile, 16-wide k-step) are one contiguous KiB, so a wave fetches them with a
 // single coalesced 16-byte-per-lane load and the weights never pass through LDS.

@@ -44,6 +44,9 @@ constexpr int kMaxUtts = 65535;   // utterances per call (16-bit utterance count
 // faster at every batch size down to B = 1; the threshold keeps small batches on the direct form they were
 // validated with.
 constexpr int kSplit3MinRowsPerCu = 64;
+// fp32 3-tap layers take the Winograd form on bf16_split3 operands (tdnn_wino_s3.hip) from this many output rows per CU on, and
+// the fp32 Winograd kernel below it (profiles/wino_s3_crossover.txt)
+constexpr int kWinoS3MinRowsPerCu = 64;
 
 // The dispatch knobs, read from the environment once, when a handle is created (A/B runs and crossover sweeps, profiles/)
 struct Policy {
@@ -54,6 +57,8 @@ struct Policy {
     bool wino;              // XVEC_WINOGRAD=0 forces the direct form of the fp32 3-tap layers
     bool split3;            // XVEC_SPLIT3=0 forces the direct form of the fp32 1-tap layers
     int split3_min_rows;    // XVEC_SPLIT3_MIN_ROWS: ... which take bf16_split3 from this many output rows per CU on
+    bool wino_split3;       // XVEC_WINO_SPLIT3=0 forces the fp32 operands of the Winograd form (tdnn_wino.hip)
+    int wino_s3_min_rows;   // XVEC_WINO_SPLIT3_MIN_ROWS: ... which takes bf16_split3 operands from this many output rows per CU on
 };
 
 int env_int(const char* name, int unset) {
@@ -63,9 +68,11 @@ int env_int(const char* name, int unset) {
 
 Policy read_policy() {
     const int tenths = env_int("XVEC_PP_MIN_TENTHS", 18), s3_rows = env_int("XVEC_SPLIT3_MIN_ROWS", kSplit3MinRowsPerCu);
+    const int ws3_rows = env_int("XVEC_WINO_SPLIT3_MIN_ROWS", kWinoS3MinRowsPerCu);
     return {std::max(1, env_int("XVEC_BLOCKS_PER_CU", 2)), env_int("XVEC_PP", 1) != 0, tenths > 0 ? tenths : 18,
             env_int("XVEC_PP_CU_PCT", 0), env_int("XVEC_WINOGRAD", 1) != 0, env_int("XVEC_SPLIT3", 1) != 0,
-            s3_rows >= 0 ? s3_rows : kSplit3MinRowsPerCu};
+            s3_rows >= 0 ? s3_rows : kSplit3MinRowsPerCu, env_int("XVEC_WINO_SPLIT3", 1) != 0,
+            ws3_rows >= 0 ? ws3_rows : kWinoS3MinRowsPerCu};
 }
 
 // RAII: the calling thread's current device is whatever it was before the call
@@ -100,6 +107,7 @@ struct xvec_handle {
     void* Wr48[XVEC_NUM_TDNN];         // bf16x3, K-tile major for tdnn_pp16.hip: per K-tile W_hi | W_lo | W_hi (3x the size of Wr16)
     float* Wp[XVEC_NUM_TDNN];
     float* Wu[XVEC_NUM_TDNN];          // 3-tap layers: Winograd F(2,3) weights U_0..U_3 (tdnn_wino.hip, launch_pack_wino), else null
+    void* Wu3[XVEC_NUM_TDNN];          // 3-tap layers: the same U_k as bf16_split3 planes, fragment-major (launch_pack_wino_split3), else null
     void* Wp3[XVEC_NUM_TDNN];          // fp32 1-tap layers 2..5: bf16_split3 weight planes hi | mid | lo, fragment-major (pack.hip), else null
     float* vec[XVEC_NUM_TDNN];         // bias | scale | shift, n_pad each
     // Plain bf16 DEFERS every layer's BatchNorm into its consumer (refold below): layer l stores relu(z + bias'), layer l+1's
@@ -126,6 +134,7 @@ struct xvec_handle {
     Policy pol;
     int last_kernel[XVEC_NUM_TDNN];    // XVEC_KERNEL_* the last launch of each frame-level layer went to (xvec_get_dispatch)
     int last_form[XVEC_NUM_TDNN];      // XVEC_FORM_* of that launch (xvec_get_tdnn_form)
+    int last_operands[XVEC_NUM_TDNN];  // XVEC_OPERANDS_* of that launch (xvec_get_tdnn_operands)
     // profiling
     bool profiling;
     hipEvent_t ev0[T_COUNT], ev1[T_COUNT];
@@ -210,6 +219,7 @@ void each_weight_buffer(xvec_handle* h, F&& f) {
         f(&h->Wr48[i], 3 * w16);
         f(&h->Wp[i], (size_t)g.n_pad * g.k_pad * 4);
         f(&h->Wu[i], g.n_taps == 3 ? (size_t)g.n_pad * 4 * g.kpt_pad * 4 : 0);
+        f(&h->Wu3[i], g.n_taps == 3 ? (size_t)g.n_pad * 4 * g.kpt_pad * 2 * 3 : 0);
         f(&h->Wp3[i], i > 0 && g.n_taps == 1 ? (size_t)g.n_pad * g.k_pad * 2 * 3 : 0);
         f(&h->Wraw[i], (size_t)g.cout * g.src_taps * g.src_cin * 4);
         f(&h->braw[i], (size_t)g.cout * 4);
@@ -279,13 +289,14 @@ struct LayerCall {
     int64_t rows_out;
 };
 
-enum class Launch { kDirect, kPp16, kFirst, kFirst3, kSplit3, kWino };
+enum class Launch { kDirect, kPp16, kFirst, kFirst3, kSplit3, kWino, kWinoS3 };
 
 // What plan_layer chose for a call: the kernel, its complete arguments, and what the launch reports.
 struct LayerPlan {
     int layer;
     Launch launch;
     int kernel, form;         // XVEC_KERNEL_* / XVEC_FORM_* (xvec_get_dispatch / xvec_get_tdnn_form)
+    int operands;             // XVEC_OPERANDS_* (xvec_get_tdnn_operands)
     TdnnMode mode;            // the call's; Src::kRows16 when bf16x3 layer 1 reads the split of its rows (the caller makes it)
     TdnnArgs a;               // every launch but Winograd's
     WinoArgs w;
@@ -305,6 +316,7 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
     lp.mode = c.mode;
     lp.kernel = XVEC_KERNEL_TILE128;
     lp.form = XVEC_FORM_DIRECT;
+    lp.operands = !bf ? XVEC_OPERANDS_FP32 : x3 ? XVEC_OPERANDS_BF16X3 : XVEC_OPERANDS_BF16;
     TdnnArgs& a = lp.a;
     a.X = c.X;
     a.W = h->Wp[l];
@@ -359,6 +371,7 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
         // bf16 products per k-step on the bf16 matrix pipe at 0.375 of the fp32 MFMA time; the same kernel family and epilogues
         lp.launch = Launch::kSplit3;
         lp.form = XVEC_FORM_BF16_SPLIT3;
+        lp.operands = XVEC_OPERANDS_BF16_SPLIT3;
         a.terms = 3;
         a.Wf = h->Wp3[l];
     } else if (!bf && from_act && !pool && h->pol.wino && h->Wu[l] && tdnn_wino_applicable(g, c.ldx)) {
@@ -386,6 +399,13 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
                                             : (int64_t)c.map.n_utts * w.p_fixed;
         w.groups_total = (pairs + 31) / 32;
         persistent_grid(h, w.n_tiles, w.groups_total, &w.blocks_per_col, &w.pair_period);
+        if (h->pol.wino_split3 && h->Wu3[l] && tdnn_wino_s3_applicable(g, c.ldx) &&
+            c.rows_out >= (int64_t)h->pol.wino_s3_min_rows * h->num_cu) {
+            // large batch: the same pairs and grid with bf16_split3 operands (tdnn_wino_s3.hip), 0.375 of the fp32 MFMA time
+            lp.launch = Launch::kWinoS3;
+            lp.operands = XVEC_OPERANDS_BF16_SPLIT3;
+            w.U3 = h->Wu3[l];
+        }
     }
     const bool rows32 = lp.mode.src == Src::kRows32;
     const int64_t x_plane = x3 && !rows32 ? c.x_plane : 0;
@@ -419,10 +439,12 @@ int launch_layer(xvec_handle* h, const LayerPlan& lp, hipStream_t s) {
         case Launch::kFirst3: HIP_TRY(launch_tdnn_first3(lp.a, h->num_cu, s)); break;
         case Launch::kSplit3: HIP_TRY(launch_tdnn_split3(lp.a, pool, s)); break;
         case Launch::kWino: HIP_TRY(launch_tdnn_wino(lp.w, s)); break;
+        case Launch::kWinoS3: HIP_TRY(launch_tdnn_wino_s3(lp.w, s)); break;
         case Launch::kDirect: HIP_TRY(launch_tdnn(lp.a, lp.mode, s)); break;
     }
     h->last_kernel[lp.layer] = lp.kernel;
     h->last_form[lp.layer] = lp.form;
+    h->last_operands[lp.layer] = lp.operands;
     return XVEC_OK;
 }
 
@@ -769,6 +791,7 @@ int xvec_load_tdnn(xvec_handle* h, int layer, const float* weight, const float* 
                              h->vec[layer], h->vec[layer] + g.n_pad, h->vec[layer] + 2 * g.n_pad,
                              static_cast<hipStream_t>(stream)));
     if (h->Wu[layer]) HIP_TRY(launch_pack_wino(weight, g, h->Wu[layer], static_cast<hipStream_t>(stream)));
+    if (h->Wu3[layer]) HIP_TRY(launch_pack_wino_split3(weight, g, h->Wu3[layer], static_cast<hipStream_t>(stream)));
     if (h->Wp3[layer]) HIP_TRY(launch_pack_tdnn_split3(weight, g, h->Wp3[layer], static_cast<hipStream_t>(stream)));
     HIP_TRY(launch_pack_tdnn_rows_bf16x3(weight, h->geo16[layer], h->Wr48[layer], static_cast<hipStream_t>(stream)));
     {
@@ -1020,6 +1043,13 @@ int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n) {
 int xvec_get_tdnn_form(const xvec_handle* h, int* forms, int* n) {
     if (!h || !forms || !n) return fail(XVEC_ERR_ARG, "null argument");
     for (int i = 0; i < XVEC_NUM_TDNN; ++i) forms[i] = h->last_form[i];
+    *n = XVEC_NUM_TDNN;
+    return XVEC_OK;
+}
+
+int xvec_get_tdnn_operands(const xvec_handle* h, int* operands, int* n) {
+    if (!h || !operands || !n) return fail(XVEC_ERR_ARG, "null argument");
+    for (int i = 0; i < XVEC_NUM_TDNN; ++i) operands[i] = h->last_operands[i];
     *n = XVEC_NUM_TDNN;
     return XVEC_OK;
 }

@@ -155,6 +155,7 @@ hipError_t launch_pack_tdnn_rows_bf16x3(const float* W, const TdnnGeom& geo, voi
 struct WinoArgs {
     const float* X;           // [rows][ldx] fp32, the layer's input layout (RowMap of the output + u*span)
     const float* U;           // [n_pad][k_pad]: U_0..U_3 with K in (chunk kc, product k) order (launch_pack_wino)
+    const void* U3;           // bf16_split3 operands (tdnn_wino_s3.hip): the same U_k as hi | mid | lo bf16 planes (launch_pack_wino_split3)
     const float* bias;        // [n_pad]
     const float* scale;       // [n_pad]
     const float* shift;       // [n_pad]
@@ -176,8 +177,14 @@ struct WinoArgs {
 inline int wino_pair_count(int T, int d) { return d * (T / (2 * d)) + std::min(T % (2 * d), d); }
 bool tdnn_wino_applicable(const TdnnGeom& g, int ldx);
 hipError_t launch_tdnn_wino(const WinoArgs& a, hipStream_t s);
+// ... on bf16_split3 operands (tdnn_wino_s3.hip): 16-wide chunks of all four products, six bf16 products per k-step
+bool tdnn_wino_s3_applicable(const TdnnGeom& g, int ldx);
+hipError_t launch_tdnn_wino_s3(const WinoArgs& a, hipStream_t s);
 // U_0 = W_0, U_1 = (W_0+W_1+W_2)/2, U_2 = (W_0-W_1+W_2)/2, U_3 = W_2 of a 3-tap layer (fp64, rounded once) -> Wu [n_pad][4*kpt_pad]
 hipError_t launch_pack_wino(const float* W, const TdnnGeom& geo, float* Wu, hipStream_t s);
+// ... the same U_k (fp64, split into three bf16 pieces) for tdnn_wino_s3.hip: 1 KiB fragment-major blocks
+// ((32-channel column tile, 16-wide k-step, product, plane hi | mid | lo)), 4 x n_pad x kpt_pad x 3 bf16
+hipError_t launch_pack_wino_split3(const float* W, const TdnnGeom& geo, void* Wu3, hipStream_t s);
 
 struct PoolArgs {
     const float* X;          // [B][T][C]

@@ -33,6 +33,7 @@ MODE_LOGITS, MODE_POOLED, MODE_XVEC6, MODE_XVEC7 = 0, 5, 6, 7
 SEG6, SEG7, OUTPUT = 6, 7, 8
 KERNEL_NAMES = {0: None, 1: "tile128", 2: "pp", 3: "first"}      # XVEC_KERNEL_*
 FORM_NAMES = {0: "direct", 1: "winograd_f23", 2: "bf16_split3"}     # XVEC_FORM_*
+OPERAND_NAMES = {0: "fp32", 1: "bf16", 2: "bf16x3", 3: "bf16_split3"}     # XVEC_OPERANDS_*
 TIMING_NAMES = ("tdnn1", "tdnn2", "tdnn3", "tdnn4", "tdnn5_pool", "pool_finalize",
                 "segment6", "segment7", "output", "pack")
 
@@ -91,6 +92,7 @@ _SIGS = {
     "xvec_get_timings": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "xvec_get_dispatch": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_get_tdnn_form": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "xvec_get_tdnn_operands": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_mfcc_create": (C.c_int, [C.POINTER(MfccCfg), C.POINTER(_vp)]),
     "xvec_mfcc_destroy": (None, [_vp]),
     "xvec_mfcc_last_error": (C.c_char_p, []),

@@ -500,6 +500,17 @@ class XVectorModel(nn.Module):
         _hip.check(_hip.lib.xvec_get_tdnn_form(eng.h, buf, C.byref(n)))
         return [_hip.FORM_NAMES.get(int(buf[i])) for i in range(n.value)]
 
+    def last_operands(self, device=None) -> list:
+        """Operand scheme of the last launch of each frame-level layer: "fp32" | "bf16" | "bf16x3" | "bf16_split3" (an fp32
+        layer with both operands split exactly into three bf16 pieces: layers 4-5's bf16_split3 form, and layers 2-3's Winograd
+        form at large batches, csrc/tdnn_wino_s3.hip; XVEC_WINO_SPLIT3=0 at engine creation keeps that one on "fp32")."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        eng = self._engine(dev)
+        buf = (C.c_int * 8)()
+        n = C.c_int(0)
+        _hip.check(_hip.lib.xvec_get_tdnn_operands(eng.h, buf, C.byref(n)))
+        return [_hip.OPERAND_NAMES.get(int(buf[i])) for i in range(n.value)]
+
     # ------------------------------------------------------------------ caller shims (main.py:135-146)
     def test_step(self, batch, batch_index=0):
         """Same I/O as the reference's Lightning hook: casts to fp32, returns

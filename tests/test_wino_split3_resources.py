@@ -1,0 +1,67 @@
+"""Resource budget of the Winograd F(2,3) kernel on bf16_split3 operands (csrc/tdnn_wino_s3.hip), compiled for gfx950 on the
+CPU: no scratch, no spill, at most 256 registers (two blocks of four wave64 per CU), and the LDS it declares per block -- two
+buffers of 4 products x 3 bf16 planes x 64 pairs x 16 k, the epilogue constants, two 64-pair row tables and their base rows --
+small enough for the two blocks per CU.  And the split of the U planes (csrc/pack.hip, pack_wino_split3_kernel), restated
+on the host: three bf16 pieces that carry U_k to about 2^-25 relative."""
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import ROOT
+
+CSRC = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
+HIPCC = "/opt/rocm/bin/hipcc"
+PLANNED_LDS = 2 * (4 * 3 * 64 * 16 * 2) + 3 * 128 * 4 + 2 * 2 * 64 * 4 + 2 * 8
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("make") is None, reason="needs hipcc")
+def test_wino_s3_kernel_resources():
+    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
+           "-Wno-pass-failed", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", "-c", "tdnn_wino_s3.hip", "-o", os.devnull]
+    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    kernels, name = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
+                         ("agprs", r" AGPRs: (\d+)"), ("spill", r"VGPRs Spill: (\d+)"),
+                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
+            m = re.search(pat, line)
+            if m and name:
+                kernels[name][key] = int(m.group(1))
+    assert len(kernels) == 1 and "tdnn_wino_s3_kernel" in next(iter(kernels)), kernels
+    r = next(iter(kernels.values()))
+    assert r["scratch"] == 0 and r.get("spill", 0) == 0, r
+    assert r["vgprs"] + r.get("agprs", 0) <= 256, r
+    assert r["occupancy"] >= 2, r
+    src = open(os.path.join(CSRC, "tdnn_wino_s3.hip")).read()
+    assert "kS3LdsBytes = 2 * kS3Stage + kS3Const + 2 * kTbl * 4 + 2 * 8" in src
+    assert "__launch_bounds__(256, 2) void tdnn_wino_s3_kernel" in src
+    assert PLANNED_LDS == 51728 and 2 * PLANNED_LDS <= 160 * 1024
+
+
+def _bf16(x):
+    """Round float64 values to bf16 (8 significant bits, nearest even), returned as float64."""
+    m, e = np.frexp(np.asarray(x, dtype=np.float64))
+    return np.ldexp(np.round(m * 256.0) / 256.0, e)
+
+
+def test_u_plane_split_carries_u():
+    rng = np.random.default_rng(5)
+    W = (rng.standard_normal((3, 4096)) * 0.05).astype(np.float32).astype(np.float64)
+    U = np.stack([W[0], 0.5 * ((W[0] + W[1]) + W[2]), 0.5 * ((W[0] - W[1]) + W[2]), W[2]])
+    hi = _bf16(U)
+    r1 = U - hi
+    mid = _bf16(r1)
+    lo = _bf16(r1 - mid)
+    rel = np.abs(hi + mid + lo - U) / np.abs(U).clip(1e-30)
+    assert rel.max() <= 2.0 ** -24, rel.max()
+    # U_0 and U_3 are fp32 values: three pieces hold them exactly
+    assert np.array_equal(hi[0] + mid[0] + lo[0], U[0]) and np.array_equal(hi[3] + mid[3] + lo[3], U[3])
