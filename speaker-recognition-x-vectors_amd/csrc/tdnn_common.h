@@ -1,4 +1,6 @@
-// Device helpers shared by the frame-level kernels (tdnn_layer_impl.h, tdnn_pp16.hip, tdnn_first.hip, tdnn_wino.hip).
+// Device helpers shared by the frame-level kernels (tdnn_layer_impl.h, tdnn_wino_rows.h, tdnn_pp16.hip, tdnn_first.hip); the
+// buffer descriptors and lane-half exchanges also serve affine.hip, score.hip and plda_train.hip.  xvec_api.hip includes it for
+// wino_pair_count, the one rule here that the host planner shares with a kernel.
 #pragma once
 #include "xvec_internal.h"
 
@@ -31,13 +33,18 @@ __device__ __forceinline__ float add_halves(float x) {
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_n(const void* p, int num_bytes) {
-    // uniform by construction (kernel argument + blockIdx-derived offset); readfirstlane makes
-    // that provable so hipcc emits no waterfall loop around the buffer loads
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+// A 64-bit value that is wave-uniform by construction, made provably so for hipcc (readfirstlane is 32 bits wide): what is
+// derived from it then lives in scalar registers
+__device__ __forceinline__ unsigned long long uniform64(unsigned long long v) {
     const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v);
     const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    void* q = reinterpret_cast<void*>(((unsigned long long)hi << 32) | lo);
+    return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_n(const void* p, int num_bytes) {
+    // uniform by construction (kernel argument + blockIdx-derived offset); uniform64 makes
+    // that provable so hipcc emits no waterfall loop around the buffer loads
+    void* q = reinterpret_cast<void*>(uniform64(reinterpret_cast<unsigned long long>(p)));
     return __builtin_amdgcn_make_buffer_rsrc(q, (short)0, __builtin_amdgcn_readfirstlane(num_bytes), 0x00020000);
 }
 
@@ -50,6 +57,74 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc_bounded(const void* 
     int64_t left = total - off;
     left = left < 0 ? 0 : (left > 0x7fffffff ? 0x7fffffff : left);
     return make_rsrc_n(static_cast<const char*>(base) + off, (int)left);
+}
+
+// 16 bytes at byte offset voff (per lane) + soff (uniform) of a descriptor
+__device__ __forceinline__ float4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
+    // (whole-vector bit cast: __builtin_bit_cast on single elements of the result made hipcc
+    // 7.2 narrow the load to one dword and splat it)
+    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
+    const f32x4 f = __builtin_bit_cast(f32x4, v);
+    return make_float4(f.x, f.y, f.z, f.w);
+}
+
+// Range [g_begin, g_end) of row groups (a.groups_total of them: 32 rows, or 32 Winograd pairs) of block p of a column, for the
+// persistent kernels of the 128x128 family (tdnn_body, both Winograd kernels).  G groups over P = a.blocks_per_col ranges: sizes
+// differ by at most one.  With two blocks per CU the dispatcher places blocks b and b + grid/2 on the same CU (observed,
+// profiles/diag/placement.hip; speed only): the ranges that get the extra group are chosen among the first-slot blocks first, so
+// a CU's two blocks sum to the same work everywhere.  persistent_grid() (xvec_api.hip) is the host counterpart: it sizes the grid
+// and sets a.pair_period only where that placement holds.
+__device__ __forceinline__ void group_range(const TdnnArgs& a, int p, int64_t& begin, int64_t& end) {
+    int64_t g_begin, g_end;
+    if (a.pair_period > 0) {
+        const int P = a.blocks_per_col, PQ = a.pair_period, hq = PQ >> 1;
+        const int64_t base = a.groups_total / P;
+        const int rem = (int)(a.groups_total % P);
+        const int rem1 = rem < (P >> 1) ? rem : (P >> 1), rem2 = rem - rem1;
+        const int xq = p / PQ, w = p % PQ;
+        const int nf = xq * hq + (w < hq ? w : hq);          // first-slot ranges before p
+        const int ns = xq * hq + (w > hq ? w - hq : 0);      // second-slot ranges before p
+        g_begin = base * p + (nf < rem1 ? nf : rem1) + (ns < rem2 ? ns : rem2);
+        const bool extra = (w < hq) ? (nf < rem1) : (ns < rem2);
+        g_end = g_begin + base + (extra ? 1 : 0);
+    } else {
+        g_begin = a.groups_total * (int64_t)p / a.blocks_per_col;
+        g_end = a.groups_total * (int64_t)(p + 1) / a.blocks_per_col;
+    }
+    begin = g_begin;      // (written once, here: with stores through the references in both branches hipcc orders
+    end = g_end;          //  tdnn_body's code differently)
+}
+
+// Winograd F(2,3) pair space (tdnn_wino.hip): pairs of an utterance with T output frames at dilation d.  The host planner sizes
+// the pair axis of a fixed-length batch with it (TdnnArgs::p_fixed), the kernels count the pairs of every utterance of a tile.
+__host__ __device__ __forceinline__ int wino_pair_count(int T, int d) {
+    const int r = T % (2 * d);
+    return d * (T / (2 * d)) + (r < d ? r : d);
+}
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+// bf16_split3 (tdnn_layer_impl.h: the form): four fp32 values -> their hi, mid and lo bf16 pieces (8 bytes each)
+__device__ __forceinline__ void split3(const float4& v, u32x2& hi, u32x2& mid, u32x2& lo) {
+    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
+    const f32x4 x = {v.x, v.y, v.z, v.w};
+    const bf16x4v h = __builtin_convertvector(x, bf16x4v);
+    const f32x4 r1 = x - __builtin_convertvector(h, f32x4);
+    const bf16x4v m = __builtin_convertvector(r1, bf16x4v);
+    const f32x4 r2 = r1 - __builtin_convertvector(m, f32x4);
+    const bf16x4v l = __builtin_convertvector(r2, bf16x4v);
+    hi = __builtin_bit_cast(u32x2, h);
+    mid = __builtin_bit_cast(u32x2, m);
+    lo = __builtin_bit_cast(u32x2, l);
+}
+
+// ... and the six products of one 16-wide k-step on them, x[] and w[] = the hi | mid | lo fragments of the two operands:
+//   lo*W_hi + mid*W_mid + hi*W_lo + mid*W_hi + hi*W_mid + hi*W_hi into ONE accumulator
+__device__ __forceinline__ void s3_mfma6(f32x16& acc, const float4* x, const float4* w) {
+#define XV_S3M(xp_, wp_) \
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x[xp_]), __builtin_bit_cast(bf16x8, w[wp_]), acc, 0, 0, 0);
+    XV_S3M(2, 0) XV_S3M(1, 1) XV_S3M(0, 2) XV_S3M(1, 0) XV_S3M(0, 1) XV_S3M(0, 0)
+#undef XV_S3M
 }
 
 // ReLU + folded BatchNorm on one accumulator whose REGISTERS are channels (store variant): element e =
@@ -145,9 +220,11 @@ __device__ __forceinline__ int64_t sload_i64(const int64_t* p) {
 }
 
 // first compact row of utterance u; u is made provably wave-uniform so that everything derived from it
-// (64-bit row numbers, masks) lives in scalar registers
+// (64-bit row numbers, masks) lives in scalar registers.  RAGGED is a template parameter on purpose: with a
+// run-time "offsets ? load : multiply" hipcc emitted VECTOR loads of the offsets followed by s_waitcnt
+// vmcnt(0) -- on the fixed-length path too -- and every one of those waits drained the loads in flight.
 template <bool RAGGED>
-__device__ __forceinline__ int64_t pool_first_row(const RowMap& m, int u) {
+__device__ __forceinline__ int64_t first_row(const RowMap& m, int u) {
     u = __builtin_amdgcn_readfirstlane(u);
     if (RAGGED) return sload_i64(m.offsets + u) - (int64_t)u * m.cum;
     return (int64_t)u * (m.fixed_T - m.cum);
@@ -184,7 +261,7 @@ __device__ __forceinline__ void pool_group_impl(const TdnnArgs& a, const f32x16&
     const __amdgpu_buffer_rsrc_t prs = make_rsrc(a.pool_part);
     while (pc.end <= row_g && pc.u < m.n_utts - 1) {
         pc.u = __builtin_amdgcn_readfirstlane(pc.u + 1);
-        pc.end = pool_first_row<RAGGED>(m, pc.u + 1);
+        pc.end = first_row<RAGGED>(m, pc.u + 1);
     }
     const float K = -negk;
     if (pc.end >= row_g + 32) {               // whole group inside utterance pc.u: no masks
@@ -205,9 +282,9 @@ __device__ __forceinline__ void pool_group_impl(const TdnnArgs& a, const f32x16&
         return;
     }
     for (int u = pc.u; u < m.n_utts; u = __builtin_amdgcn_readfirstlane(u + 1)) {
-        const int64_t off = pool_first_row<RAGGED>(m, u);
+        const int64_t off = first_row<RAGGED>(m, u);
         if (off >= row_g + 32) break;
-        const int64_t end = pool_first_row<RAGGED>(m, u + 1);
+        const int64_t end = first_row<RAGGED>(m, u + 1);
         const int64_t lo_r = off > row_g ? off : row_g;
         const int64_t hi_r = end < row_g + 32 ? end : row_g + 32;
         if (hi_r <= lo_r) continue;

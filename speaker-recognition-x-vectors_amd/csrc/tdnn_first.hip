@@ -35,13 +35,6 @@ __device__ __forceinline__ u32x4 cvt8(const u32x4& lo, const u32x4& hi) {
     return o;
 }
 
-template <bool RAGGED>
-__device__ __forceinline__ int64_t first_row_of(const RowMap& m, int u) {
-    u = __builtin_amdgcn_readfirstlane(u);
-    if (RAGGED) return sload_i64(m.offsets + u) - (int64_t)u * m.cum;
-    return (int64_t)u * (m.fixed_T - m.cum);
-}
-
 // utterance cursor of a block: u = utterance of the group's first row, end = first output row of utterance u+1
 struct Cur {
     int u;
@@ -74,7 +67,7 @@ __device__ __forceinline__ void fetch8(const TdnnArgs& a, int64_t g, Cur& cu, in
     const int n_last = m.n_utts - 1;
     while (cu.end <= m0 && cu.u < n_last) {
         cu.u = __builtin_amdgcn_readfirstlane(cu.u + 1);
-        cu.end = first_row_of<RAGGED>(m, cu.u + 1);
+        cu.end = first_row<RAGGED>(m, cu.u + 1);
     }
     int c = 0;                             // boundaries inside the group: frame rr lies c utterances past cu.u
     {
@@ -83,7 +76,7 @@ __device__ __forceinline__ void fetch8(const TdnnArgs& a, int64_t g, Cur& cu, in
         while (nxt < m0 + 32 && u < n_last) {
             c += (m0 + rr >= nxt) ? 1 : 0;
             u = __builtin_amdgcn_readfirstlane(u + 1);
-            nxt = first_row_of<RAGGED>(m, u + 1);
+            nxt = first_row<RAGGED>(m, u + 1);
         }
     }
     // descriptor at the group's first input row (64-bit), bounded by the end of the caller's tensor: reads past it return
@@ -139,7 +132,7 @@ __global__ __launch_bounds__(512) void tdnn_first_kernel(const TdnnArgs a) {
     if (g_begin >= g_end) return;
     Cur cu;
     cu.u = __builtin_amdgcn_readfirstlane(utt_of_row(a.out_map, g_begin * 32));
-    cu.end = first_row_of<RAGGED>(a.out_map, cu.u + 1);
+    cu.end = first_row<RAGGED>(a.out_map, cu.u + 1);
     const int rr = tid >> 4, sk = tid & 15;        // staging: frame rr, half k-step sk (8 floats)
     // Two groups of look-ahead: loads and stores share the wave's in-order vmcnt counter, so waiting for loads
     // issued AFTER a group's stores would wait for those stores to be acknowledged by memory (several us at
@@ -211,7 +204,6 @@ __global__ __launch_bounds__(512) void tdnn_first_kernel(const TdnnArgs a) {
 namespace first3 {
 
 using first::Cur;
-using first::first_row_of;
 using first::kConstFloats;
 using first::kRowB;
 using first::kTileB;
@@ -227,7 +219,7 @@ __device__ __forceinline__ void fetch(const TdnnArgs& a, int64_t g, Cur& cu, int
     const int n_last = m.n_utts - 1;
     while (cu.end <= m0 && cu.u < n_last) {
         cu.u = __builtin_amdgcn_readfirstlane(cu.u + 1);
-        cu.end = first_row_of<RAGGED>(m, cu.u + 1);
+        cu.end = first_row<RAGGED>(m, cu.u + 1);
     }
     int c = 0;                             // boundaries inside the group: frame rr lies c utterances past cu.u
     {
@@ -236,7 +228,7 @@ __device__ __forceinline__ void fetch(const TdnnArgs& a, int64_t g, Cur& cu, int
         while (nxt < m0 + 32 && u < n_last) {
             c += (m0 + rr >= nxt) ? 1 : 0;
             u = __builtin_amdgcn_readfirstlane(u + 1);
-            nxt = first_row_of<RAGGED>(m, u + 1);
+            nxt = first_row<RAGGED>(m, u + 1);
         }
     }
     const int64_t row0 = m0 + (int64_t)cu.u * a.span;
@@ -305,7 +297,7 @@ __global__ __launch_bounds__(512) void tdnn_first3_kernel(const TdnnArgs a) {
     if (g_begin >= g_end) return;
     Cur cu;
     cu.u = __builtin_amdgcn_readfirstlane(utt_of_row(a.out_map, g_begin * 32));
-    cu.end = first_row_of<RAGGED>(a.out_map, cu.u + 1);
+    cu.end = first_row<RAGGED>(a.out_map, cu.u + 1);
     const int rr = tid >> 4, sk = tid & 15;        // staging: frame rr, half k-step sk
     Staged sa, sb;                                 // two groups of look-ahead (see tdnn_first_kernel)
     fetch<RAGGED>(a, g_begin, cu, rr, sk, sa);

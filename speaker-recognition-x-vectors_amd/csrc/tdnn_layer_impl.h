@@ -42,14 +42,6 @@ struct Ctx {
     int es;              // bytes per input element (4: fp32, 2: bf16)
 };
 
-__device__ __forceinline__ float4 buf_load16(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
-    // (whole-vector bit cast: __builtin_bit_cast on single elements of the result made hipcc
-    // 7.2 narrow the load to one dword and splat it)
-    const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0);
-    const f32x4 f = __builtin_bit_cast(f32x4, v);
-    return make_float4(f.x, f.y, f.z, f.w);
-}
-
 // eight fp32 values -> eight bf16 in the 16 bytes of a staging register (round to nearest even, as pack_rows)
 __device__ __forceinline__ float4 cvt8_bf16(const float4& lo, const float4& hi) {
     typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
@@ -378,21 +370,6 @@ struct Lane {
 //     32-channel column, hi | mid | lo), loaded one chunk ahead.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPlaneBytes = kBM * kBK * 2;   // one bf16 plane of a 128 x 32 chunk
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-// four fp32 values -> their hi, mid and lo bf16 pieces (8 bytes each)
-__device__ __forceinline__ void split3(const float4& v, u32x2& hi, u32x2& mid, u32x2& lo) {
-    typedef __bf16 bf16x4v __attribute__((ext_vector_type(4)));
-    const f32x4 x = {v.x, v.y, v.z, v.w};
-    const bf16x4v h = __builtin_convertvector(x, bf16x4v);
-    const f32x4 r1 = x - __builtin_convertvector(h, f32x4);
-    const bf16x4v m = __builtin_convertvector(r1, bf16x4v);
-    const f32x4 r2 = r1 - __builtin_convertvector(m, f32x4);
-    const bf16x4v l = __builtin_convertvector(r2, bf16x4v);
-    hi = __builtin_bit_cast(u32x2, h);
-    mid = __builtin_bit_cast(u32x2, m);
-    lo = __builtin_bit_cast(u32x2, l);
-}
 
 // staging registers of row group i (fp32, 16 bytes) -> the three planes of LDS buffer B
 __device__ __forceinline__ void s3_store(char* B, int st3, int i, const float4& v) {
@@ -420,13 +397,6 @@ __device__ __forceinline__ void s3_wld(const Ctx& cx, float4* w, int c, int n_ch
     if (c >= n_chunks) c -= n_chunks;
 #pragma unroll
     for (int j = 0; j < 6; ++j) w[j] = buf_load16(cx.wfrsrc, cx.wf_voff, (6 * c + j) * 1024);
-}
-
-__device__ __forceinline__ void s3_mfma6(f32x16& acc, const float4* x, const float4* w) {
-#define XV_S3M(xp_, wp_) \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x[xp_]), __builtin_bit_cast(bf16x8, w[wp_]), acc, 0, 0, 0);
-    XV_S3M(2, 0) XV_S3M(1, 1) XV_S3M(0, 2) XV_S3M(1, 0) XV_S3M(0, 1) XV_S3M(0, 0)
-#undef XV_S3M
 }
 
 // One K-chunk: chunk `it` is in LDS buffer P (weights in rg.w3[P]); staging set N holds chunk it + 1, which goes to
@@ -678,26 +648,8 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
     const int lid = xcd_remap(blockIdx.x, gridDim.x);
     const int j = lid % a.n_tiles;
     const int p = lid / a.n_tiles;
-    // Row range of this block.  G groups over P ranges: sizes differ by at most one.  With two
-    // blocks per CU the dispatcher places blocks b and b + grid/2 on the same CU (observed,
-    // profiles/diag/placement.hip; speed only): the ranges that get the extra group are chosen
-    // among the first-slot blocks first, so a CU's two blocks sum to the same work everywhere.
     int64_t g_begin, g_end;
-    if (a.pair_period > 0) {
-        const int P = a.blocks_per_col, PQ = a.pair_period, hq = PQ >> 1;
-        const int64_t base = a.groups_total / P;
-        const int rem = (int)(a.groups_total % P);
-        const int rem1 = rem < (P >> 1) ? rem : (P >> 1), rem2 = rem - rem1;
-        const int xq = p / PQ, w = p % PQ;
-        const int nf = xq * hq + (w < hq ? w : hq);          // first-slot ranges before p
-        const int ns = xq * hq + (w > hq ? w - hq : 0);      // second-slot ranges before p
-        g_begin = base * p + (nf < rem1 ? nf : rem1) + (ns < rem2 ? ns : rem2);
-        const bool extra = (w < hq) ? (nf < rem1) : (ns < rem2);
-        g_end = g_begin + base + (extra ? 1 : 0);
-    } else {
-        g_begin = a.groups_total * (int64_t)p / a.blocks_per_col;
-        g_end = a.groups_total * (int64_t)(p + 1) / a.blocks_per_col;
-    }
+    group_range(a, p, g_begin, g_end);
     const int n0 = j * kBN;
     const int n_chunks = a.n_taps * a.cpt;
 

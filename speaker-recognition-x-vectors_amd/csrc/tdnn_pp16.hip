@@ -52,10 +52,10 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void* lds_ptr;
 
 __device__ __forceinline__ i32x4 make_srd(const void* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned long long v = uniform64(reinterpret_cast<unsigned long long>(p));
     i32x4 d;
-    d.x = (int)__builtin_amdgcn_readfirstlane((unsigned)v);
-    d.y = (int)(__builtin_amdgcn_readfirstlane((unsigned)(v >> 32)) & 0xffffu);   // stride 0
+    d.x = (int)(unsigned)v;
+    d.y = (int)((unsigned)(v >> 32) & 0xffffu);   // stride 0
     d.z = 0x7fffffff;                                                            // num_records (bytes)
     d.w = 0x00020000;
     return d;
@@ -499,16 +499,6 @@ constexpr int kBlk16 = 16 * kRowB;                // 16 rows of a 32-row block: 
 // S1 = sum (r - K), S2 = sum (r - K)^2 of r = relu(z + bias), K = frame 0 of the group in which the segment's first rows fall
 // (tdnn_common.h, pool_group_impl: why a pivot) -- one v_max, one v_sub, one v_add and one v_fma per value.  Scale and shift of
 // the folded BatchNorm are applied by pool_finalize.
-// RAGGED is a template parameter and the utterance index is kept provably wave-uniform on purpose: with
-// a run-time "offsets ? load : multiply" hipcc emitted VECTOR loads of the offsets followed by
-// s_waitcnt vmcnt(0) -- on the fixed-length path too -- and every one of those waits drained the DMA
-// queue (the next tile's first K-tiles) in the middle of the epilogue.
-template <bool RAGGED>
-__device__ __forceinline__ int64_t first_row(const RowMap& m, int u) {
-    u = __builtin_amdgcn_readfirstlane(u);
-    if (RAGGED) return sload_i64(m.offsets + u) - (int64_t)u * m.cum;
-    return (int64_t)u * (m.fixed_T - m.cum);
-}
 // max(x, 0) as ONE instruction.  fmaxf() on a value hipcc cannot prove canonical (the accumulators come out of inline asm)
 // becomes v_max_f32 t, x, x; v_max_f32 r, 0, t -- a quieting pass plus the max, the second waiting for the first: twice
 // the instructions of the epilogues' ReLU, in dependent pairs.  (A NaN gives 0 here, as fmaxf does.)

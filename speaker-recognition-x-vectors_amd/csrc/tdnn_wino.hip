@@ -30,15 +30,13 @@
 namespace xvec {
 namespace wino {
 
-constexpr int kBMP = 64, kBN = 128;                 // pairs x channels of a tile
+constexpr int kBMP = kPairs;                        // pairs of a tile
 constexpr int kStage = (kBMP + kBN) * kBK;          // one LDS buffer (floats): V tile then U tile
-constexpr int kConst = 3 * kBN;                     // bias | scale | shift of the block's 128 channels
 constexpr int kLdsBytes = (2 * kStage + kConst + 2 * kTbl) * 4 + 2 * 8;   // + per parity the tile's output base row
-static_assert(kBMP == kPairs, "tile of tdnn_wino_rows.h");
 
 // Step the load stream to the next chunk (products innermost); after a tile's last chunk, to chunk 0 of the block's next
 // tile.  Past the block's last chunk it stays put (the look-ahead re-reads that chunk; the data is never used).
-__device__ __forceinline__ void advance(const WinoArgs& a, Ctx& cx, const Lane& ln, int* tbl, int64_t* tblh, int n_chunks) {
+__device__ __forceinline__ void advance(const TdnnArgs& a, Ctx& cx, const Lane& ln, int* tbl, int64_t* tblh, int n_chunks) {
     if (cx.itl + 1 < n_chunks) {
         ++cx.itl;
         if (++cx.kk == 4) {
@@ -87,14 +85,14 @@ __device__ __forceinline__ void advance(const WinoArgs& a, Ctx& cx, const Lane& 
 // the two input rows of V_k (KL_: the product of the chunk cx points at) for pair group i_ -> the staging set.  Rows x1,
 // x2 are x0 + d, x0 + 2d: the scalar offset carries the shift; x3 has a lane offset of its own (x1 in one-output tiles).
 #define WG_GLD_X(dst_, i_, M_)                                                                                 \
-    if constexpr (M_ == 3) dst_ = ld16(cx.xrsrc, cx.x3##i_, cx.kc * 128);                                      \
-    else dst_ = ld16(cx.xrsrc, cx.x0##i_, cx.kc * 128 + M_ * cx.drb);
+    if constexpr (M_ == 3) dst_ = buf_load16(cx.xrsrc, cx.x3##i_, cx.kc * 128);                                      \
+    else dst_ = buf_load16(cx.xrsrc, cx.x0##i_, cx.kc * 128 + M_ * cx.drb);
 #define WG_GLD_A(i_, KL_)                                                                                      \
     if constexpr (GL > i_) {                                                                                   \
         WG_GLD_X(rg.xa##i_, i_, (KL_ == 0 ? 0 : KL_ == 1 ? 1 : KL_ == 2 ? 2 : 1))                              \
         WG_GLD_X(rg.xb##i_, i_, (KL_ == 0 ? 2 : KL_ == 1 ? 2 : KL_ == 2 ? 1 : 3))                              \
     }
-#define WG_GLD_B(j_) rg.u##j_ = ld16(cx.wrsrc, cx.w_toff, (32 * j_ * a.k_pad + cx.itl * kBK) * 4);
+#define WG_GLD_B(j_) rg.u##j_ = buf_load16(cx.wrsrc, cx.w_toff, (32 * j_ * a.k_pad + cx.itl * kBK) * 4);
 // one MFMA (product K_, pair group i_, k component c_, fragment set f_) and the statement slotted behind it
 #define WG_MF(K_, i_, c_, f_, slot_)                                                                           \
     if constexpr (G > i_) {                                                                                    \
@@ -133,7 +131,7 @@ struct Regs {
 };
 
 // Once per block: chunk 0 of the first tile -> LDS buffer 0, its first fragments -> set 0, chunk 1 in flight.
-__device__ __forceinline__ void block_prologue(const WinoArgs& a, float* smem, int* tbl, int64_t* tblh, Ctx& cx, Regs& rg,
+__device__ __forceinline__ void block_prologue(const TdnnArgs& a, float* smem, int* tbl, int64_t* tblh, Ctx& cx, Regs& rg,
                                                const Lane& ln, int n_chunks) {
     constexpr int G = 2, GL = 2;
     const int h = ln.h, sw = ln.sw, a_rd = ln.a_rd, b_rd = ln.b_rd, st_off = ln.st_off;
@@ -151,7 +149,7 @@ __device__ __forceinline__ void block_prologue(const WinoArgs& a, float* smem, i
 // One tile of G pair groups (32 pairs each) x 128 channels at pair group g0; tp = its row-table parity.  On entry the
 // pipeline is primed for this tile (block_prologue or the previous tile's last chunks).
 template <int G>
-__device__ __forceinline__ void process_tile(const WinoArgs& a, float* smem, int* tbl, int64_t* tblh, Ctx& cx, Regs& rg,
+__device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, int* tbl, int64_t* tblh, Ctx& cx, Regs& rg,
                                              const Lane& ln, int n0, int tp, int n_chunks) {
     constexpr int GL = 2;     // the load stream always fetches both groups (rows of a short tile's absent group are valid)
     const int h = ln.h, sw = ln.sw, a_rd = ln.a_rd, b_rd = ln.b_rd, st_off = ln.st_off;
@@ -169,82 +167,27 @@ __device__ __forceinline__ void process_tile(const WinoArgs& a, float* smem, int
         WG_CHUNK(1, 0, 3, 0, 1)
     }
 
-    // ---- epilogue: y(t) = M0 + M1 + M2, y(t+d) = M1 - M2 - M3, then bias + ReLU + folded BatchNorm (tdnn_layer.py:30-39)
-    // accumulator element e of lane (r, h): pair = (e&3) + 8*(e>>2) + 4*h of the group, channel = r
-    const int col = ln.col;
-    const float* cst = smem + 2 * kStage + (col - n0);
-    const float bi = cst[0], sc = cst[kBN], sh = cst[2 * kBN];
-    const int64_t ob = tblh[tp];
-    const unsigned ob_lo = __builtin_amdgcn_readfirstlane((unsigned)ob), ob_hi = __builtin_amdgcn_readfirstlane((unsigned)(ob >> 32));
-    const int64_t obu = (int64_t)(((unsigned long long)ob_hi << 32) | ob_lo);
-    const __amdgpu_buffer_rsrc_t yrsrc = make_rsrc(a.Y + obu * a.ldy);
-    const int* t0 = tbl + tp * kTbl;
-    const int row_b = a.ldy * 4;
-#define WG_EPI(i_)                                                                                             \
-    if constexpr (G > i_) {                                                                                    \
-        _Pragma("unroll") for (int g4 = 0; g4 < 4; ++g4) {                                                     \
-            const int4 r0v = *reinterpret_cast<const int4*>(t0 + i_ * 32 + 8 * g4 + 4 * h);                    \
-            const int4 r1v = *reinterpret_cast<const int4*>(t0 + kBMP + i_ * 32 + 8 * g4 + 4 * h);             \
-            const int o0s[4] = {r0v.x, r0v.y, r0v.z, r0v.w};                                                   \
-            const int o1s[4] = {r1v.x, r1v.y, r1v.z, r1v.w};                                                   \
-            _Pragma("unroll") for (int e4 = 0; e4 < 4; ++e4) {                                                 \
-                const int e = 4 * g4 + e4;                                                                     \
-                const float m1 = acc1_##i_[e], m2 = acc2_##i_[e];                                              \
-                const float y0 = fmaf(fmaxf((acc0_##i_[e] + m1) + m2 + bi, 0.f), sc, sh);                      \
-                const float y1 = fmaf(fmaxf((m1 - m2) - acc3_##i_[e] + bi, 0.f), sc, sh);                      \
-                if (o0s[e4] >= 0) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y0), yrsrc, o0s[e4] * row_b + col * 4, 0, 0); \
-                if (o1s[e4] >= 0) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y1), yrsrc, o1s[e4] * row_b + col * 4, 0, 0); \
-            }                                                                                                  \
-        }                                                                                                      \
-    }
-    WG_EPI(0) WG_EPI(1)
-#undef WG_EPI
+    epilogue<G>(a, smem + 2 * kStage, tbl, tblh, ln, n0, tp, acc0_0, acc1_0, acc2_0, acc3_0, acc0_1, acc1_1, acc2_1, acc3_1);
 }
 
-__global__ __launch_bounds__(256, 2) void tdnn_wino_kernel(const WinoArgs a) {
+__global__ __launch_bounds__(256, 2) void tdnn_wino_kernel(const TdnnArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     int* tbl = reinterpret_cast<int*>(smem + 2 * kStage + kConst);
     int64_t* tblh = reinterpret_cast<int64_t*>(smem + 2 * kStage + kConst + 2 * kTbl);
-    // logical id -> (row range p, channel column j); the n_tiles columns of one range are consecutive ids on one XCD
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int j = lid % a.n_tiles;
-    const int p = lid / a.n_tiles;
-    // range of 32-pair groups of this block (the CU-pair-aware split of tdnn_layer.hip)
-    int64_t g_begin, g_end;
-    group_range(a, p, g_begin, g_end);
-    const int n0 = j * kBN;
-    const int n_chunks = 4 * a.cpt;
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    Ctx cx;
     Lane ln;
-    ln.h = lane >> 5;
-    const int r = lane & 31;
-    ln.c = tid & 7;
-    ln.r0 = tid >> 3;
+    const int n0 = block_setup(a, 7, cx, ln);
+    const int n_chunks = 4 * a.cpt;
+    const int64_t g_begin = cx.g_s, g_end = cx.g_end;     // (the load stream moves cx.g_s on)
+    const int wave = ln.wave, r = ln.r;
     ln.st_off = ln.r0 * kBK + ((ln.c ^ ((ln.r0 >> 1) & 7)) << 2);
     ln.sw = (r >> 1) & 7;
     ln.a_rd = r * kBK;
     ln.b_rd = kBMP * kBK + (wave * 32 + r) * kBK;
-    ln.col = n0 + wave * 32 + r;
-    if (tid < kBN) {
-        smem[2 * kStage + tid] = a.bias[n0 + tid];
-        smem[2 * kStage + kBN + tid] = a.scale[n0 + tid];
-        smem[2 * kStage + 2 * kBN + tid] = a.shift[n0 + tid];
-    }
-
-    Ctx cx;
-    cx.g_s = g_begin;
-    cx.g_end = g_end;
-    cx.q0 = g_begin * 32;
-    cx.wrsrc = make_rsrc(a.U + (int64_t)n0 * a.k_pad);
+    cx.wrsrc = make_rsrc(static_cast<const float*>(a.W) + (int64_t)n0 * a.k_pad);
     cx.w_toff = ln.r0 * a.k_pad * 4 + ln.c * 16;
-    first_utterance(a, cx);
-    cx.lp = 0;
-    set_rows(a, cx, ln, tbl, tblh);
-    cx.kk = 0;
-    cx.kc = 0;
-    cx.itl = 0;
+
+    stream_start(a, n0, smem + 2 * kStage, tbl, tblh, cx, ln);
 
     Regs rg;
     block_prologue(a, smem, tbl, tblh, cx, rg, ln, n_chunks);
@@ -261,8 +204,8 @@ bool tdnn_wino_applicable(const TdnnGeom& g, int ldx) {
            g.n_pad % wino::kBN == 0 && ldx % 4 == 0;
 }
 
-hipError_t launch_tdnn_wino(const WinoArgs& a, hipStream_t s) {
-    if (a.groups_total <= 0 || a.blocks_per_col <= 0 || a.blocks_per_col > a.groups_total || a.d < 1 || a.cpt < 1 ||
+hipError_t launch_tdnn_wino(const TdnnArgs& a, hipStream_t s) {
+    if (a.groups_total <= 0 || a.blocks_per_col <= 0 || a.blocks_per_col > a.groups_total || a.tap_rows < 1 || a.cpt < 1 ||
         (a.out_map.offsets == nullptr && a.p_fixed < 1))
         return hipErrorInvalidValue;
     const int grid = a.blocks_per_col * a.n_tiles;

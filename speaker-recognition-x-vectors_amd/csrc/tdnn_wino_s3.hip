@@ -1,8 +1,8 @@
 // fp32 frame-level layer with three equally spaced taps (layers 2 and 3) as Winograd F(2,3) along time (tdnn_wino.hip: the
-// math and the pair space) on bf16_split3 operands (tdnn_layer_impl.h: the split): the four products M_k = V_k . U_k^T
-// run on v_mfma_f32_32x32x16_bf16 with both operands split exactly into hi + mid + lo bf16 pieces, six products per
-// 16-wide k-step into one accumulator.  Matrix-pipe work: 0.667 (Winograd) x 0.375 (split3) = 0.25 of the
-// direct fp32 form.
+// math and the pair space) on bf16_split3 operands (tdnn_layer_impl.h: the form; tdnn_common.h: split3, s3_mfma6): the four
+// products M_k = V_k . U_k^T run on v_mfma_f32_32x32x16_bf16 with both operands split exactly into hi + mid + lo bf16 pieces,
+// six products per 16-wide k-step into one accumulator.  Matrix-pipe work: 0.667 (Winograd) x 0.375 (split3) =
+// 0.25 of the direct fp32 form.
 //
 // Tiling.  A tile is 64 pairs x 128 channels, four waves of 32 channels, 2 pair groups x 4 products = 8
 // accumulators per wave, as tdnn_wino.hip.  The K loop walks 16-wide chunks, each holding ALL FOUR products: a thread
@@ -13,22 +13,20 @@
 // by product as soon as the previous chunk's MFMAs of that product have issued).
 //   per block and chunk: 16 KiB of input rows + 48 KiB of U planes over 4 waves x 4 products x 2 groups x 6 = 192 MFMAs
 //   = 341 B per MFMA (the direct port of tdnn_wino.hip's tile: 427).
-#include "tdnn_layer_impl.h"
 #include "tdnn_wino_rows.h"
 
 namespace xvec {
 namespace wino {
 
 constexpr int kS3K = 16;                                  // k per chunk (one bf16 k-step)
-constexpr int kS3BN = 128;                                // channels of a tile
 constexpr int kS3Plane = kPairs * kS3K * 2;               // bytes of one (product, plane) block: 64 pairs x 32 B
 constexpr int kS3Stage = 4 * 3 * kS3Plane;                // one LDS buffer: 4 products x hi | mid | lo
-constexpr int kS3Const = 3 * kS3BN * 4;                   // bias | scale | shift of the tile's channels
+constexpr int kS3Const = kConst * 4;                      // bias | scale | shift of the tile's channels, bytes
 constexpr int kS3LdsBytes = 2 * kS3Stage + kS3Const + 2 * kTbl * 4 + 2 * 8;   // + row tables, per parity the base row
 
 // Step the load stream to the next chunk; after a tile's last chunk, to chunk 0 of the block's next tile.  Past the block's
 // last chunk it stays put (the look-ahead re-reads that chunk; the data is never used).
-__device__ __forceinline__ void s3_advance(const WinoArgs& a, Ctx& cx, const Lane& ln, int* tbl, int64_t* tblh, int n_chunks) {
+__device__ __forceinline__ void s3_advance(const TdnnArgs& a, Ctx& cx, const Lane& ln, int* tbl, int64_t* tblh, int n_chunks) {
     if (cx.kc + 1 < n_chunks) {
         ++cx.kc;
     } else {
@@ -53,10 +51,10 @@ struct S3Stage {
 __device__ __forceinline__ void s3_gld(const Ctx& cx, bool grp, S3Stage& s) {
     const int xo0 = grp ? cx.x01 : cx.x00, xo3 = grp ? cx.x31 : cx.x30;
     const int so = cx.kc * (kS3K * 4);
-    s.x0 = ld16(cx.xrsrc, xo0, so);
-    s.x1 = ld16(cx.xrsrc, xo0, so + cx.drb);
-    s.x2 = ld16(cx.xrsrc, xo0, so + 2 * cx.drb);
-    s.x3 = ld16(cx.xrsrc, xo3, so);
+    s.x0 = buf_load16(cx.xrsrc, xo0, so);
+    s.x1 = buf_load16(cx.xrsrc, xo0, so + cx.drb);
+    s.x2 = buf_load16(cx.xrsrc, xo0, so + 2 * cx.drb);
+    s.x3 = buf_load16(cx.xrsrc, xo3, so);
 }
 
 // V_k = x0-x2 | x1+x2 | x2-x1 | x1-x3 in fp32, each split into hi | mid | lo -> LDS buffer B (st: this thread's 8 bytes)
@@ -81,13 +79,13 @@ __device__ __forceinline__ void s3_vstore(char* B, int st, const S3Stage& s) {
 __device__ __forceinline__ void s3_uld(__amdgpu_buffer_rsrc_t rsrc, int voff, float4* w, int k, int c, int n_chunks) {
     if (c >= n_chunks) c -= n_chunks;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) w[p] = ld16(rsrc, voff, ((4 * c + k) * 3 + p) * 1024);
+    for (int p = 0; p < 3; ++p) w[p] = buf_load16(rsrc, voff, ((4 * c + k) * 3 + p) * 1024);
 }
 
 // One tile of G pair groups x 128 channels; tp = its row-table parity.  On entry chunk 0 of the tile is in LDS buffer 0,
 // the U planes of chunk 0 are in w, and the staging registers hold chunk 1 (block prologue or the previous tile's chunks).
 template <int G>
-__device__ __forceinline__ void s3_tile(const WinoArgs& a, char* lds, int* tbl, int64_t* tblh, Ctx& cx, const Lane& ln,
+__device__ __forceinline__ void s3_tile(const TdnnArgs& a, char* lds, int* tbl, int64_t* tblh, Ctx& cx, const Lane& ln,
                                         S3Stage& st, float4 (&w)[4][3], __amdgpu_buffer_rsrc_t ursrc, int n0, int tp,
                                         int n_chunks) {
     const bool grp = (threadIdx.x >> 2) & 1;
@@ -123,83 +121,32 @@ __device__ __forceinline__ void s3_tile(const WinoArgs& a, char* lds, int* tbl, 
         __syncthreads();   // chunk it + 1 complete in LDS; chunk it's buffer is free
     }
 
-    // ---- epilogue (tdnn_wino.hip): y(t) = M0 + M1 + M2, y(t+d) = M1 - M2 - M3, then bias + ReLU + folded BatchNorm
-    // accumulator element e of lane (r, h): pair = (e&3) + 8*(e>>2) + 4*h of the group, channel = r
-    const int h = ln.h, col = ln.col;
-    const float* cst = reinterpret_cast<const float*>(lds + 2 * kS3Stage) + (col - n0);
-    const float bi = cst[0], sc = cst[kS3BN], sh = cst[2 * kS3BN];
-    const int64_t ob = tblh[tp];
-    const unsigned ob_lo = __builtin_amdgcn_readfirstlane((unsigned)ob), ob_hi = __builtin_amdgcn_readfirstlane((unsigned)(ob >> 32));
-    const int64_t obu = (int64_t)(((unsigned long long)ob_hi << 32) | ob_lo);
-    const __amdgpu_buffer_rsrc_t yrsrc = make_rsrc(a.Y + obu * a.ldy);
-    const int* t0 = tbl + tp * kTbl;
-    const int row_b = a.ldy * 4;
-#define WS3_EPI(i_)                                                                                            \
-    if constexpr (G > i_) {                                                                                    \
-        _Pragma("unroll") for (int g4 = 0; g4 < 4; ++g4) {                                                     \
-            const int4 r0v = *reinterpret_cast<const int4*>(t0 + i_ * 32 + 8 * g4 + 4 * h);                    \
-            const int4 r1v = *reinterpret_cast<const int4*>(t0 + kPairs + i_ * 32 + 8 * g4 + 4 * h);           \
-            const int o0s[4] = {r0v.x, r0v.y, r0v.z, r0v.w};                                                   \
-            const int o1s[4] = {r1v.x, r1v.y, r1v.z, r1v.w};                                                   \
-            _Pragma("unroll") for (int e4 = 0; e4 < 4; ++e4) {                                                 \
-                const int e = 4 * g4 + e4;                                                                     \
-                const float m1 = acc1_##i_[e], m2 = acc2_##i_[e];                                              \
-                const float y0 = fmaf(fmaxf((acc0_##i_[e] + m1) + m2 + bi, 0.f), sc, sh);                      \
-                const float y1 = fmaf(fmaxf((m1 - m2) - acc3_##i_[e] + bi, 0.f), sc, sh);                      \
-                if (o0s[e4] >= 0) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y0), yrsrc, o0s[e4] * row_b + col * 4, 0, 0); \
-                if (o1s[e4] >= 0) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y1), yrsrc, o1s[e4] * row_b + col * 4, 0, 0); \
-            }                                                                                                  \
-        }                                                                                                      \
-    }
-    WS3_EPI(0) WS3_EPI(1)
-#undef WS3_EPI
+    epilogue<G>(a, reinterpret_cast<const float*>(lds + 2 * kS3Stage), tbl, tblh, ln, n0, tp, acc0_0, acc1_0, acc2_0, acc3_0, acc0_1,
+                acc1_1, acc2_1, acc3_1);
 }
 
-__global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const WinoArgs a) {
+__global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const TdnnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float* cst = reinterpret_cast<float*>(lds + 2 * kS3Stage);
-    int* tbl = reinterpret_cast<int*>(lds + 2 * kS3Stage + kS3Const);
-    int64_t* tblh = reinterpret_cast<int64_t*>(lds + 2 * kS3Stage + kS3Const + 2 * kTbl * 4);
-    // logical id -> (row range p, channel column j); the n_tiles columns of one range are consecutive ids on one XCD
-    const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int j = lid % a.n_tiles;
-    const int p = lid / a.n_tiles;
-    int64_t g_begin, g_end;
-    group_range(a, p, g_begin, g_end);
-    const int n0 = j * kS3BN;
-    const int n_chunks = 2 * a.cpt;        // 16-wide chunks per product (cpt counts 32-wide ones)
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
-    Lane ln;
-    ln.h = lane >> 5;
-    const int r = lane & 31;
+    int* tbl = reinterpret_cast<int*>(cst + kConst);
+    int64_t* tblh = reinterpret_cast<int64_t*>(tbl + 2 * kTbl);
     // staging map: thread (r0 = tid >> 3, c = tid & 7) -> pair r0 + 32 * (c >> 2) of the tile, k 4 (c & 3) .. +3 of the
     // chunk; set_rows takes the 16-byte column c & 3 and returns the input rows of both of r0's pairs
-    ln.c = tid & 3;
-    ln.r0 = tid >> 3;
+    Ctx cx;
+    Lane ln;
+    const int n0 = block_setup(a, 3, cx, ln);
+    const int n_chunks = 2 * a.cpt;        // 16-wide chunks per product (cpt counts 32-wide ones)
+    const int64_t g_begin = cx.g_s, g_end = cx.g_end;     // (the load stream moves cx.g_s on)
+    const int tid = threadIdx.x, lane = tid & 63, wave = ln.wave;
     ln.st_off = (ln.r0 + 32 * ((tid >> 2) & 1)) * (kS3K * 2) + (tid & 3) * 8;   // byte offset in a plane block
-    ln.a_rd = r * (kS3K * 2) + ln.h * 16;     // A fragment of lane (r, h): pair r of the group, k 8h .. 8h + 7
+    ln.a_rd = ln.r * (kS3K * 2) + ln.h * 16;     // A fragment of lane (r, h): pair r of the group, k 8h .. 8h + 7
     ln.b_rd = lane * 16;                      // U fragment: 16 bytes per lane of a 1 KiB block
-    ln.col = n0 + wave * 32 + r;
     ln.sw = 0;
-    if (tid < kS3BN) {
-        cst[tid] = a.bias[n0 + tid];
-        cst[kS3BN + tid] = a.scale[n0 + tid];
-        cst[2 * kS3BN + tid] = a.shift[n0 + tid];
-    }
     // U planes of this wave's 32-channel column: 12 KiB per chunk ((chunk, product, plane) blocks of 1 KiB)
     const int64_t ct = n0 / 32 + wave;
-    const __amdgpu_buffer_rsrc_t ursrc = make_rsrc(static_cast<const char*>(a.U3) + ct * (int64_t)n_chunks * 12288);
+    const __amdgpu_buffer_rsrc_t ursrc = make_rsrc(static_cast<const char*>(a.Wf) + ct * (int64_t)n_chunks * 12288);
 
-    Ctx cx;
-    cx.g_s = g_begin;
-    cx.g_end = g_end;
-    cx.q0 = g_begin * 32;
-    first_utterance(a, cx);
-    cx.lp = 0;
-    set_rows(a, cx, ln, tbl, tblh);
-    cx.kc = 0;
+    stream_start(a, n0, cst, tbl, tblh, cx, ln);
 
     // prologue: chunk 0 -> LDS buffer 0, the U planes of chunk 0 -> w, chunk 1 in the staging registers
     const bool grp = (tid >> 2) & 1;
@@ -222,12 +169,12 @@ __global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const WinoArgs a) 
 }  // namespace wino
 
 bool tdnn_wino_s3_applicable(const TdnnGeom& g, int ldx) {
-    return tdnn_wino_applicable(g, ldx) && g.n_pad % wino::kS3BN == 0 && (g.kpt_pad / wino::kS3K) % 2 == 0;
+    return tdnn_wino_applicable(g, ldx) && (g.kpt_pad / wino::kS3K) % 2 == 0;
 }
 
-hipError_t launch_tdnn_wino_s3(const WinoArgs& a, hipStream_t s) {
-    if (a.groups_total <= 0 || a.blocks_per_col <= 0 || a.blocks_per_col > a.groups_total || a.d < 1 || a.cpt < 1 ||
-        a.U3 == nullptr || (a.out_map.offsets == nullptr && a.p_fixed < 1))
+hipError_t launch_tdnn_wino_s3(const TdnnArgs& a, hipStream_t s) {
+    if (a.groups_total <= 0 || a.blocks_per_col <= 0 || a.blocks_per_col > a.groups_total || a.tap_rows < 1 || a.cpt < 1 ||
+        a.Wf == nullptr || (a.out_map.offsets == nullptr && a.p_fixed < 1))
         return hipErrorInvalidValue;
     const int grid = a.blocks_per_col * a.n_tiles;
     wino::tdnn_wino_s3_kernel<<<dim3(grid), dim3(256), wino::kS3LdsBytes, s>>>(a);

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "../../include/xvec_hip.h"
+#include "tdnn_common.h"   // wino_pair_count
 #include "xvec_internal.h"
 
 using namespace xvec;
@@ -264,7 +265,8 @@ int pp_blocks_per_col(const xvec_handle* h, int n_pad, int64_t rows_out) {
 }
 
 // Persistent grid of the 128x128 family (direct, bf16_split3, Winograd): blocks per 128-channel column, and the period of the
-// CU-pair-aware range sizes, which need the full 2-blocks-per-CU grid and whole XCD runs per half (0: off)
+// CU-pair-aware range sizes, which need the full 2-blocks-per-CU grid and whole XCD runs per half (0: off).  The kernels
+// split groups_total over these blocks with group_range (tdnn_common.h).
 void persistent_grid(const xvec_handle* h, int n_tiles, int64_t groups_total, int* blocks_per_col, int* pair_period) {
     const int per_col = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cu * h->pol.blocks_per_cu / n_tiles, groups_total));
     const int nwg = per_col * n_tiles;
@@ -298,8 +300,7 @@ struct LayerPlan {
     int kernel, form;         // XVEC_KERNEL_* / XVEC_FORM_* (xvec_get_dispatch / xvec_get_tdnn_form)
     int operands;             // XVEC_OPERANDS_* (xvec_get_tdnn_operands)
     TdnnMode mode;            // the call's; Src::kRows16 when bf16x3 layer 1 reads the split of its rows (the caller makes it)
-    TdnnArgs a;               // every launch but Winograd's
-    WinoArgs w;
+    TdnnArgs a;
     int64_t pool_units;       // tdnn_pp16.hip pooling: the geometry of its segment partials (finalize_pool)
     int pool_bpc;
 };
@@ -379,32 +380,20 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
         // same kernel family (persistent fp32, 128 x 128 output tiles)
         lp.launch = Launch::kWino;
         lp.form = XVEC_FORM_WINOGRAD_F23;
-        WinoArgs& w = lp.w;
-        w.X = static_cast<const float*>(c.X);
-        w.U = h->Wu[l];
-        w.bias = a.bias;
-        w.scale = a.scale;
-        w.shift = a.shift;
-        w.Y = static_cast<float*>(c.Y);
-        w.ldx = c.ldx;
-        w.ldy = a.ldy;
-        w.cpt = g.kpt_pad / kBK;
-        w.k_pad = 4 * g.kpt_pad;
-        w.n_tiles = a.n_tiles;
-        w.out_map = c.map;
-        w.span = a.span;
-        w.d = g.tap_rows;
-        w.p_fixed = c.map.offsets ? 0 : wino_pair_count(c.map.fixed_T - c.map.cum, w.d);
-        const int64_t pairs = c.map.offsets ? (c.rows_out >> 1) + (int64_t)c.map.n_utts * w.d     // pair_base(n_utts), tdnn_wino.hip
-                                            : (int64_t)c.map.n_utts * w.p_fixed;
-        w.groups_total = (pairs + 31) / 32;
-        persistent_grid(h, w.n_tiles, w.groups_total, &w.blocks_per_col, &w.pair_period);
+        a.W = h->Wu[l];
+        a.k_pad = 4 * g.kpt_pad;
+        // the pair axis (tdnn_wino.hip) instead of the frame axis: its length, with the holes of a ragged batch
+        a.p_fixed = c.map.offsets ? 0 : wino_pair_count(c.map.fixed_T - c.map.cum, g.tap_rows);
+        const int64_t pairs = c.map.offsets ? (c.rows_out >> 1) + (int64_t)c.map.n_utts * g.tap_rows     // pair_base(n_utts)
+                                            : (int64_t)c.map.n_utts * a.p_fixed;
+        a.groups_total = (pairs + 31) / 32;
+        persistent_grid(h, a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
         if (h->pol.wino_split3 && h->Wu3[l] && tdnn_wino_s3_applicable(g, c.ldx) &&
             c.rows_out >= (int64_t)h->pol.wino_s3_min_rows * h->num_cu) {
             // large batch: the same pairs and grid with bf16_split3 operands (tdnn_wino_s3.hip), 0.375 of the fp32 MFMA time
             lp.launch = Launch::kWinoS3;
             lp.operands = XVEC_OPERANDS_BF16_SPLIT3;
-            w.U3 = h->Wu3[l];
+            a.Wf = h->Wu3[l];
         }
     }
     const bool rows32 = lp.mode.src == Src::kRows32;
@@ -438,8 +427,8 @@ int launch_layer(xvec_handle* h, const LayerPlan& lp, hipStream_t s) {
         case Launch::kFirst: HIP_TRY(launch_tdnn_first(lp.a, h->num_cu, s)); break;
         case Launch::kFirst3: HIP_TRY(launch_tdnn_first3(lp.a, h->num_cu, s)); break;
         case Launch::kSplit3: HIP_TRY(launch_tdnn_split3(lp.a, pool, s)); break;
-        case Launch::kWino: HIP_TRY(launch_tdnn_wino(lp.w, s)); break;
-        case Launch::kWinoS3: HIP_TRY(launch_tdnn_wino_s3(lp.w, s)); break;
+        case Launch::kWino: HIP_TRY(launch_tdnn_wino(lp.a, s)); break;
+        case Launch::kWinoS3: HIP_TRY(launch_tdnn_wino_s3(lp.a, s)); break;
         case Launch::kDirect: HIP_TRY(launch_tdnn(lp.a, lp.mode, s)); break;
     }
     h->last_kernel[lp.layer] = lp.kernel;

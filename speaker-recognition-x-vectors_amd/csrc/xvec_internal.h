@@ -4,8 +4,6 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 namespace xvec {
 
 constexpr int kBK = 32;          // K-chunk (fp32 elements) staged per main-loop step
@@ -82,24 +80,27 @@ struct TdnnGeom {
     int terms;          // bf16x3 weight stream: 2 (per chunk: W_hi blocks, W_lo blocks), else 1
 };
 
+// Arguments of every frame-level kernel.  The 128x128 family (tdnn_layer.hip, tdnn_split3.hip) and tdnn_first.hip read them
+// as the field comments say; what tdnn_pp16.hip and the Winograd kernels read differently is noted at their launchers below.
 struct TdnnArgs {
     const void* X;      // [rows][ldx]  fp32 or bf16
-    const void* W;      // fp32: packed row-major [n_pad][k_pad]
-    const void* Wf;     // bf16: fragment-major packing of the same matrix (see pack.hip)
+    const void* W;      // fp32: packed row-major [n_pad][k_pad]   (Winograd: the U matrix of launch_pack_wino)
+    const void* Wf;     // bf16: fragment-major packing of the same matrix (see pack.hip)   (bf16_split3 forms: its hi | mid | lo planes)
     const float* bias;  // [n_pad]
     const float* scale; // [n_pad]  folded BatchNorm: y = relu(v)*scale + shift
     const float* shift; // [n_pad]
     void* Y;            // [m_pad][ldy]  fp32 or bf16
     int64_t x_rows;     // rows of X that may be read (guarded variant)
     int ldx, ldy;
-    int n_taps, tap_rows, kpt, cpt;   // cpt = chunks per tap = kpt_pad / kBK
+    int n_taps, tap_rows, kpt, cpt;   // tap_rows = dilation; cpt = chunks per tap = kpt_pad / kBK (Winograd: per product)
     int k_pad;
     int n_tiles;              // 128-channel columns
     int blocks_per_col;       // persistent blocks per column; grid = n_tiles * blocks_per_col
-    int64_t groups_total;     // 32-row groups of the flat frame axis (ceil(rows / 32))
-    int pair_period;          // >0: row ranges per XCD run; enables CU-pair-aware range sizes (see kernel)
+    int64_t groups_total;     // 32-row groups of the flat frame axis (ceil(rows / 32));  Winograd: 32-pair groups of the pair axis
+    int pair_period;          // >0: row ranges per XCD run; enables CU-pair-aware range sizes (group_range, tdnn_common.h)
     RowMap out_map;           // row layout of THIS layer's output
     int span;                 // frames this layer consumes (c[-1]-c[0]): input row = p + u(p)*span
+    int p_fixed;              // Winograd, fixed-length batches: pairs per utterance (wino_pair_count, tdnn_common.h)
     // fused statistics-pooling epilogue (layer 5)
     float* pool_part;         // [slots][3][n_pad]: pivot K | sum (r-K) | sum (r-K)^2, r = relu(z + bias), per (32-row group, utterance)
                               // (tdnn_pp16.hip: per (block of the column, utterance, frames half) -- see there)
@@ -152,34 +153,15 @@ hipError_t launch_pack_tdnn_rows_bf16x3(const float* W, const TdnnGeom& geo, voi
 
 // fp32 layer with three equally spaced taps as Winograd F(2,3) along time (tdnn_wino.hip): two outputs (t, t+d) of one
 // utterance per GEMM row ("pair"), four products V_k . U_k^T, K = cin each.  Epilogue as launch_tdnn's fp32 store variant.
-struct WinoArgs {
-    const float* X;           // [rows][ldx] fp32, the layer's input layout (RowMap of the output + u*span)
-    const float* U;           // [n_pad][k_pad]: U_0..U_3 with K in (chunk kc, product k) order (launch_pack_wino)
-    const void* U3;           // bf16_split3 operands (tdnn_wino_s3.hip): the same U_k as hi | mid | lo bf16 planes (launch_pack_wino_split3)
-    const float* bias;        // [n_pad]
-    const float* scale;       // [n_pad]
-    const float* shift;       // [n_pad]
-    float* Y;                 // [rows_out][ldy] fp32
-    int ldx, ldy;
-    int cpt;                  // 32-wide K chunks per product (cin / kBK)
-    int k_pad;                // 4 * cpt * kBK
-    int n_tiles;              // 128-channel columns
-    int blocks_per_col;
-    int64_t groups_total;     // 32-pair groups of the pair axis
-    int pair_period;          // as TdnnArgs
-    RowMap out_map;
-    int span;                 // 2d: frames the layer consumes
-    int d;                    // dilation
-    int p_fixed;              // fixed-length batches: pairs per utterance
-};
-// pairs of an utterance with T output frames, and the pair-axis length of a batch (ragged: with the holes of the
-// pair_base formula, tdnn_wino.hip)
-inline int wino_pair_count(int T, int d) { return d * (T / (2 * d)) + std::min(T % (2 * d), d); }
+// Reads TdnnArgs with X / Y fp32 rows, W = U_0..U_3 as [n_pad][k_pad] with K in (chunk kc, product k) order (launch_pack_wino),
+//   tap_rows = d, cpt = cin / kBK chunks per product, k_pad = 4 * cpt * kBK, groups_total = 32-pair groups of the pair axis
+//   (blocks_per_col, pair_period over those), p_fixed; bias, scale, shift, ldx, ldy, n_tiles, out_map, span as the 128x128 kernel.
 bool tdnn_wino_applicable(const TdnnGeom& g, int ldx);
-hipError_t launch_tdnn_wino(const WinoArgs& a, hipStream_t s);
-// ... on bf16_split3 operands (tdnn_wino_s3.hip): 16-wide chunks of all four products, six bf16 products per k-step
+hipError_t launch_tdnn_wino(const TdnnArgs& a, hipStream_t s);
+// ... on bf16_split3 operands (tdnn_wino_s3.hip): 16-wide chunks of all four products, six bf16 products per k-step;
+// Wf = the same U_k as hi | mid | lo bf16 planes (launch_pack_wino_split3), W is not read
 bool tdnn_wino_s3_applicable(const TdnnGeom& g, int ldx);
-hipError_t launch_tdnn_wino_s3(const WinoArgs& a, hipStream_t s);
+hipError_t launch_tdnn_wino_s3(const TdnnArgs& a, hipStream_t s);
 // U_0 = W_0, U_1 = (W_0+W_1+W_2)/2, U_2 = (W_0-W_1+W_2)/2, U_3 = W_2 of a 3-tap layer (fp64, rounded once) -> Wu [n_pad][4*kpt_pad]
 hipError_t launch_pack_wino(const float* W, const TdnnGeom& geo, float* Wu, hipStream_t s);
 // ... the same U_k (fp64, split into three bf16 pieces) for tdnn_wino_s3.hip: 1 KiB fragment-major blocks

@@ -42,7 +42,8 @@ def test_wino_s3_kernel_resources():
     assert r["vgprs"] + r.get("agprs", 0) <= 256, r
     assert r["occupancy"] >= 2, r
     src = open(os.path.join(CSRC, "tdnn_wino_s3.hip")).read()
-    assert "kS3LdsBytes = 2 * kS3Stage + kS3Const + 2 * kTbl * 4 + 2 * 8" in src
+    assert "kS3LdsBytes = 2 * kS3Stage + kS3Const + 2 * kTbl * 4 + 2 * 8" in src and "kS3Const = kConst * 4;" in src
+    assert "kConst = 3 * kBN;" in open(os.path.join(CSRC, "tdnn_wino_rows.h")).read()
     assert "__launch_bounds__(256, 2) void tdnn_wino_s3_kernel" in src
     assert PLANNED_LDS == 51728 and 2 * PLANNED_LDS <= 160 * 1024
 

@@ -42,5 +42,6 @@ def test_winograd_kernel_resources():
     # dynamic LDS: the launch size the kernel file declares is the planned one, and two blocks fit a CU's 160 KiB
     src = open(os.path.join(CSRC, "tdnn_wino.hip")).read()
     assert "kLdsBytes = (2 * kStage + kConst + 2 * kTbl) * 4 + 2 * 8" in src
-    assert "kBMP = 64, kBN = 128" in src
+    rows = open(os.path.join(CSRC, "tdnn_wino_rows.h")).read()
+    assert "kBMP = kPairs;" in src and "kPairs = 64;" in rows and "kBN = 128;" in rows and "kConst = 3 * kBN;" in rows
     assert PLANNED_LDS == 51728 and 2 * PLANNED_LDS <= 160 * 1024
