@@ -12,7 +12,7 @@ import pytest
 import torch
 
 from conftest import assert_parity, assert_parity_masked
-from test_large_batch_layers_gpu import _model, DEV
+from tdnn_support import DEV, make_model
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +32,7 @@ def _cases(n, seed):
 
 @pytest.fixture(scope="module")
 def engines(sd42):
-    return {p: (_model(sd42, p, pp=True), _model(sd42, p, pp=False)) for p in ("bf16", "bf16x3")}
+    return {p: (make_model(sd42, precision=p), make_model(sd42, {"XVEC_PP": "0"}, p)) for p in ("bf16", "bf16x3")}
 
 
 # (FUZZ_N / FUZZ_SEED: a longer walk by hand; FUZZ_N=80 FUZZ_SEED=7 and FUZZ_N=300 FUZZ_SEED=31337 ran clean in round 3:

@@ -3,17 +3,10 @@ count on (a `scratch_load` waits with vmcnt, i.e. for every DMA piece in flight)
 with 20 / 52 bytes per lane unnoticed.  hipcc reports per-kernel resources with -Rpass-analysis=kernel-resource-usage;
 this test compiles the frame-level and segment-level sources for gfx950 (device code only) and checks every kernel."""
 import concurrent.futures as cf
-import os
 import re
-import shutil
-import subprocess
 
-import pytest
+from hipcc_support import kernel_asm, kernel_resources, needs_hipcc, needs_hipcc_and_make
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 SOURCES = ["tdnn_layer.hip", "tdnn_pp16.hip", "tdnn_first.hip", "affine.hip", "pool.hip", "mfcc.hip", "score.hip"]
 # bytes of scratch a kernel may use.  The 128 x 128 fp64 score GEMM parks a dozen tile-invariant 64-bit addresses in scratch
 # OUTSIDE its K loop (stored once before the persistent loop, re-read in the epilogue and at a tile's first chunk; the loop
@@ -21,30 +14,10 @@ SOURCES = ["tdnn_layer.hip", "tdnn_pp16.hip", "tdnn_first.hip", "affine.hip", "p
 SCRATCH_OK = {"gemm_nt_f64_kernelILb1ELi4ELb0E": 128, "gemm_nt_f64_kernelILb0ELi4ELb0E": 128}
 
 
-def _resources(src):
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
-           "-Wno-pass-failed", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull]
-    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
-                         ("spill", r"VGPRs Spill: (\d+)"), ("agprs", r" AGPRs: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"), ("lds", r"LDS Size \[bytes/block\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return src, kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("make") is None, reason="needs hipcc")
+@needs_hipcc_and_make
 def test_no_kernel_uses_scratch():
     with cf.ThreadPoolExecutor(max_workers=4) as pool:
-        results = dict(pool.map(_resources, SOURCES))
+        results = dict(zip(SOURCES, pool.map(kernel_resources, SOURCES)))
     total = 0
     for src, kernels in results.items():
         assert kernels, f"{src}: no kernel reported"
@@ -65,16 +38,13 @@ def test_no_kernel_uses_scratch():
     assert total >= 41
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_score_gemm_k_loop_is_free_of_scratch():
     """The one kernel with a scratch allowance (SCRATCH_OK): its spills must stay outside the K loop -- the innermost loop around
     the MFMAs (label ... backward branch) holds no scratch_ instruction."""
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
-           "-Wno-pass-failed", "-Wno-inline-asm", "-S", "score.hip", "-o", "-"]
-    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
+    asm = kernel_asm("score.hip")
     checked = 0
-    for body in re.split(r"\n(?=_ZN\S*gemm_nt_f64_kernel\S*:)", out.stdout)[1:]:
+    for body in re.split(r"\n(?=_ZN\S*gemm_nt_f64_kernel\S*:)", asm)[1:]:
         name = body.split(":", 1)[0]
         lines = body.split("s_endpgm")[0].splitlines()
         mf = [i for i, l in enumerate(lines) if "v_mfma_f64" in l]
@@ -93,18 +63,15 @@ def test_score_gemm_k_loop_is_free_of_scratch():
     assert checked == 6
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_mfcc_sample_loads_are_waited_for_before_any_use():
     """fft512::mfcc512_kernel requests a pair of frames with 32 inline-asm loads and waits for them with an asm s_waitcnt that
     names their destinations (csrc/mfcc.hip, MF_REQUEST): hipcc's own wait-count pass sees neither.  On the assembly: between
     the first load of a burst and the s_waitcnt vmcnt(0) that ends it, no instruction reads or writes a register a load of the
     burst has been told to fill.  Both input types."""
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
-           "-Wno-pass-failed", "-Wno-inline-asm", "-S", "mfcc.hip", "-o", "-"]
-    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
+    asm = kernel_asm("mfcc.hip")
     bursts = 0
-    for body in re.split(r"\n(?=_ZN\S*mfcc512_kernel\S*:)", out.stdout)[1:]:
+    for body in re.split(r"\n(?=_ZN\S*mfcc512_kernel\S*:)", asm)[1:]:
         name = body.split(":", 1)[0]
         pending = None                       # destination registers of the burst in flight
         in_asm = False                       # (loads hipcc emits itself -- table fetches -- are tracked by its own wait counts)

@@ -17,68 +17,36 @@ Three references per layer, same input to all:
      whose rounding flips -- a corrupted element is tens of ulps away;
   3. repeat runs are bit-identical (a race shows up as run-to-run differences).
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import xvector_oracle as oracle
 from conftest import assert_parity, assert_parity_masked, float_params, nearly_off_channels
+from tdnn_support import DEV, make_model, oracle_layer
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 
 SHAPES = [(52, 300), (63, 300), (100, 300), (128, 300), (160, 300), (256, 300), (70, 517)]
 
 
-def _model(sd, precision, pp=True):
-    """bf16 model whose engine is created with the large-batch kernels on (default) or off (XVEC_PP=0 is read
-    once per handle in xvec_create)."""
-    import xvector_amd as xa
-    m = xa.XVectorModel(precision=precision)
-    m.load_state_dict(sd)
-    m = m.to(DEV)
-    old = os.environ.get("XVEC_PP")
-    try:
-        if pp:
-            os.environ.pop("XVEC_PP", None)
-        else:
-            os.environ["XVEC_PP"] = "0"
-        m._engine(torch.device(DEV))          # creates the handle now, under this environment
-    finally:
-        if old is None:
-            os.environ.pop("XVEC_PP", None)
-        else:
-            os.environ["XVEC_PP"] = old
-    return m
-
-
 @pytest.fixture(scope="module")
 def models(sd42):
-    return _model(sd42, "bf16", pp=True), _model(sd42, "bf16", pp=False)
+    """bf16 models whose engines are created with the large-batch kernels on (default) and off (XVEC_PP=0)."""
+    return make_model(sd42, precision="bf16"), make_model(sd42, {"XVEC_PP": "0"}, "bf16")
 
 
 _ORACLE_CACHE = {}
 
 
-def _oracle_layer(x_cpu, p64, layer, chunk=32, key=None):
-    """fp64 oracle of one layer on fp32 input, a few utterances at a time (memory).  `key`: the tests of the three
-    arithmetics walk the same (seed, shape) chains of fp32 layer inputs; the CPU oracle of a chain link is computed once."""
-    if key is not None and (key, layer) in _ORACLE_CACHE:
-        return _ORACLE_CACHE[(key, layer)]
-    out = _oracle_layer_uncached(x_cpu, p64, layer, chunk)
-    if key is not None:
-        _ORACLE_CACHE[(key, layer)] = out
-    return out
-
-
-def _oracle_layer_uncached(x_cpu, p64, layer, chunk=32):
-    outs = []
-    for lo in range(0, x_cpu.shape[0], chunk):
-        outs.append(oracle.tdnn_layer(x_cpu[lo:lo + chunk].double(), p64, f"time_context_layers.{layer}.",
-                                      oracle.CONTEXTS[layer]).float())
-    return torch.cat(outs)
+def _oracle_layer(x_cpu, p64, layer, key=None):
+    """fp64 oracle of one layer on fp32 input, as fp32.  `key`: the tests of the three arithmetics walk the same
+    (seed, shape) chains of fp32 layer inputs; the CPU oracle of a chain link is computed once."""
+    if key is None:
+        return oracle_layer(x_cpu, p64, layer).float()
+    if (key, layer) not in _ORACLE_CACHE:
+        _ORACLE_CACHE[(key, layer)] = oracle_layer(x_cpu, p64, layer).float()
+    return _ORACLE_CACHE[(key, layer)]
 
 
 def _pre_bn(y, sd, layer):
@@ -159,7 +127,7 @@ X3_SHAPES = [(52, 300), (63, 300), (128, 300), (256, 300), (70, 517)]
 
 @pytest.fixture(scope="module")
 def models_x3(sd42):
-    return _model(sd42, "bf16x3", pp=True), _model(sd42, "bf16x3", pp=False)
+    return make_model(sd42, precision="bf16x3"), make_model(sd42, {"XVEC_PP": "0"}, "bf16x3")
 
 
 @pytest.mark.parametrize("B,T", X3_SHAPES)
@@ -220,7 +188,7 @@ def test_bf16x3_whole_path_on_the_large_batch_kernels(gpu_model, sd42, synth, mo
 def test_fused_pooling_layer_vs_oracle(sd42, synth, gpu_model, precision, tol):
     """The fp32 / bf16x3 pooling epilogue (tdnn_layer.hip) alone, every utterance against the fp64 oracle,
     mean half and std half separately (the std half is 5x smaller in norm and would hide behind the means)."""
-    m = gpu_model if precision == "fp32" else _model(sd42, precision)
+    m = gpu_model if precision == "fp32" else make_model(sd42, precision=precision)
     p64 = oracle.cast_params(float_params(sd42), torch.float64)
     h = torch.as_tensor(synth.make_mfcc(24, 300, seed=77)).to(DEV)
     for i in range(4):
@@ -248,7 +216,7 @@ def test_ill_conditioned_pooling_through_the_fused_path(sd42, synth, precision, 
     statistics AND the x-vectors against the fp64 oracle.  Round 2's raw fp32 sums (sum r, sum r^2) lose
     1e-7*(mean/std)^2 of the variance -- everything, here."""
     sd = _ill_conditioned_sd(sd42)
-    m = _model(sd, precision)
+    m = make_model(sd, precision=precision)
     p64 = oracle.cast_params(float_params(sd), torch.float64)
     x = torch.as_tensor(synth.make_mfcc(B, 300, seed=5))
     idx = list(range(B)) if B <= 12 else sorted({0, 1, B // 2, B - 1})
@@ -291,7 +259,7 @@ def test_pooling_pivot_taken_from_a_neighbouring_utterance(sd42, precision, B, t
     W[c, (c + 1) % 512] = 77.0 / 256.0
     sd["time_context_layers.4.linear.weight"] = W
     sd["time_context_layers.4.linear.bias"].zero_()
-    m = _model(sd, precision)
+    m = make_model(sd, precision=precision)
     rng = np.random.default_rng(B)
     T = 300
     level = 12 * rng.choice([-1, 1], size=(B, 1, 512))                     # per (utterance, channel): +-12 steps of 2^-7

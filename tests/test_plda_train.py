@@ -1,19 +1,13 @@
 """PLDA training, CPU half: the package's host EM (xvector_amd.plda.host_em) against the literal restatement of
 speechbrain's loop (tests/plda_em_ref.py, unpinned), the speechbrain-shaped surface, the C ABI's argument checks and the
 kernels' resources.  The device half is tests/test_plda_train_gpu.py."""
-import os
 import pickle
-import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import plda_em_ref as ref
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+from hipcc_support import kernel_resources, needs_hipcc
 
 
 def numpy_products(sums_centred, counts):
@@ -112,23 +106,9 @@ def test_plda_abi_argument_errors_without_gpu():
     assert lib.xvec_plda_em_workspace_bytes(0, 4) == 0 and lib.xvec_plda_em_workspace_bytes(10, 4) > 0
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+@needs_hipcc
 def test_plda_kernels_use_no_scratch():
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
-           "-Wno-pass-failed", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", "-c", "plda_train.hip", "-o", os.devnull]
-    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
-                         ("spill", r"VGPRs Spill: (\d+)"), ("agprs", r" AGPRs: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
+    kernels = kernel_resources("plda_train.hip")
     assert len(kernels) == 10, sorted(kernels)    # class sums x2, mean, centre, scatter x4, reduce, E-step scale
     for k, r in kernels.items():
         assert r.get("scratch", 0) == 0 and r.get("spill", 0) == 0, f"{k}: {r}"

@@ -7,62 +7,21 @@ under XVEC_SPLIT3=0 (read once per handle in xvec_create), which runs layers 4 a
     both forms at the fp32 bar; the split form's worst-frame norm-wise error no more than 1.5x the direct form's;
   * determinism, graph replay, a ragged batch with NaN-poisoned padding, the reported forms on both sides of the threshold.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import xvector_oracle as oracle
 from conftest import assert_parity, float_params
+from tdnn_support import DEV, make_model, oracle_layer, p64, worst_rel  # noqa: F401 (p64: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 SPLIT_LAYERS = (3, 4)         # time_context_layers.3 / .4: the one-tap layers (contexts [0])
-
-
-def _model(sd, split=True):
-    import xvector_amd as xa
-    m = xa.XVectorModel()
-    m.load_state_dict(sd)
-    m = m.to(DEV).eval()
-    old = os.environ.get("XVEC_SPLIT3")
-    try:
-        if split:
-            os.environ.pop("XVEC_SPLIT3", None)
-        else:
-            os.environ["XVEC_SPLIT3"] = "0"
-        m._engine(torch.device(DEV))          # the handle is created now, under this environment
-    finally:
-        if old is None:
-            os.environ.pop("XVEC_SPLIT3", None)
-        else:
-            os.environ["XVEC_SPLIT3"] = old
-    return m
 
 
 @pytest.fixture(scope="module")
 def models(sd42):
-    return _model(sd42, True), _model(sd42, False)
-
-
-@pytest.fixture(scope="module")
-def p64(sd42):
-    return oracle.cast_params(float_params(sd42), torch.float64)
-
-
-def _oracle_layer(x_cpu, p64, layer, chunk=32):
-    outs = []
-    for lo in range(0, x_cpu.shape[0], chunk):
-        outs.append(oracle.tdnn_layer(x_cpu[lo:lo + chunk].double(), p64, f"time_context_layers.{layer}.",
-                                      oracle.CONTEXTS[layer]))
-    return torch.cat(outs)
-
-
-def _worst_rel(got, ref64):
-    g = got.double().cpu().reshape(-1, got.shape[-1])
-    r = ref64.reshape(-1, ref64.shape[-1])
-    return ((g - r).norm(dim=1) / r.norm(dim=1).clamp_min(1e-30)).max().item()
+    return make_model(sd42), make_model(sd42, {"XVEC_SPLIT3": "0"})
 
 
 def test_bench_size_every_element_both_forms(models, p64, sd42, synth):
@@ -72,14 +31,14 @@ def test_bench_size_every_element_both_forms(models, p64, sd42, synth):
     for i in range(3):
         h = md.time_context_layers[i](h)
     for layer in SPLIT_LAYERS:
-        ref = _oracle_layer(h.cpu(), p64, layer)
+        ref = oracle_layer(h.cpu(), p64, layer)
         gs = ms.time_context_layers[layer](h)
         assert ms.last_forms()[layer] == "bf16_split3" and ms.last_dispatch()[layer] == "tile128"
         gd = md.time_context_layers[layer](h)
         assert md.last_forms()[layer] == "direct" and md.last_dispatch()[layer] == "tile128"
         assert_parity(gs, ref.float(), 1e-4, f"layer {layer} split3 B=256 vs oracle")
         assert_parity(gd, ref.float(), 1e-4, f"layer {layer} direct B=256 vs oracle")
-        es, ed = _worst_rel(gs, ref), _worst_rel(gd, ref)
+        es, ed = worst_rel(gs, ref), worst_rel(gd, ref)
         print(f"layer {layer}: worst-frame error split3 {es:.3e}, direct {ed:.3e} ({es / ed:.2f}x)")
         assert es <= 1.5 * ed, f"layer {layer}: split3 {es:.3e} vs direct {ed:.3e}"
         assert torch.equal(gs, ms.time_context_layers[layer](h)), f"layer {layer}: repeat run differs"
@@ -88,7 +47,7 @@ def test_bench_size_every_element_both_forms(models, p64, sd42, synth):
     # layer 5 with the fused pooling epilogue (the path's own launch), both forms
     # (the stds against the oracle element by element, with the ill-conditioned ones masked, are the existing bench-size test's,
     # which runs the default form; here: row-wise against the oracle, and against the direct form on the same input)
-    frames = _oracle_layer(h.cpu(), p64, 4).double()
+    frames = oracle_layer(h.cpu(), p64, 4).double()
     ref = oracle.stat_pool(frames)
     pooled = {}
     for m, name in ((ms, "split3"), (md, "direct")):

@@ -7,17 +7,11 @@
     three planes of a chunk fit the LDS buffers the kernel already plans.
 """
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-from conftest import ROOT
+from hipcc_support import CSRC, kernel_resources, needs_hipcc_and_make
 
-CSRC = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 
 
 def bf16_rn(x):
@@ -139,29 +133,9 @@ def test_packed_planes_where_the_kernel_reads_them():
     assert (pieces[:, cout:, :] == 0).all() and (pieces[:, :, cin:] == 0).all()
 
 
-def _resources(src):
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
-           "-Wno-pass-failed", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", os.devnull]
-    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
-                         ("agprs", r" AGPRs: (\d+)"), ("spill", r"VGPRs Spill: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
-    return kernels
-
-
-@pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("make") is None, reason="needs hipcc")
+@needs_hipcc_and_make
 def test_split3_kernel_resources():
-    kernels = _resources("tdnn_split3.hip")
+    kernels = kernel_resources("tdnn_split3.hip")
     # tdnn_split3_kernel<POOL, STORE>: the split form of the store (layer 4) and pooling (layer 5) variants
     s3 = {k: v for k, v in kernels.items() if "tdnn_split3_kernel" in k}
     assert len(s3) == 2, list(kernels)

@@ -10,7 +10,6 @@ x_vector_size, num_classes and batch_norm are constructor arguments), against th
      scale every layer's frames, the pooled statistics and the x-vector by exactly 2^k in every kernel family.
 """
 import ctypes
-import os
 
 import numpy as np
 import pytest
@@ -18,10 +17,9 @@ import torch
 
 import xvector_oracle as oracle
 from conftest import assert_parity, assert_parity_masked, float_params
+from tdnn_support import DEV, make_model, oracle_layer, worst_rel
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-KNOBS = ("XVEC_SPLIT3", "XVEC_SPLIT3_MIN_ROWS", "XVEC_WINOGRAD", "XVEC_WINO_SPLIT3", "XVEC_WINO_SPLIT3_MIN_ROWS", "XVEC_PP")
 
 # (input_size, hidden_size, batch_norm, x_vector_size, num_classes)
 ARCHS = {
@@ -54,25 +52,9 @@ def _sd(arch, batch_norm=None, seed=None):
 
 def _model(arch, sd, precision="fp32", env=None, batch_norm=None):
     """A model of `arch` whose handle is created now, under `env` (the knobs are read once per handle in xvec_create)."""
-    import xvector_amd as xa
     cin, hid, bn, xv, nc = ARCHS[arch]
-    m = xa.XVectorModel(input_size=cin, hidden_size=hid, num_classes=nc, x_vector_size=xv,
-                        batch_norm=bn if batch_norm is None else batch_norm, precision=precision)
-    m.load_state_dict(sd)
-    m = m.to(DEV).eval()
-    old = {k: os.environ.get(k) for k in KNOBS}
-    try:
-        for k in KNOBS:
-            os.environ.pop(k, None)
-        os.environ.update(env or {})
-        m._engine(torch.device(DEV))
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return m
+    return make_model(sd, env, precision, input_size=cin, hidden_size=hid, num_classes=nc, x_vector_size=xv,
+                      batch_norm=bn if batch_norm is None else batch_norm)
 
 
 _ARCH_CACHE = {}
@@ -90,20 +72,6 @@ def _arch(name):
 def _mfcc(arch, B, T, seed):
     import xvector_amd as xa
     return xa.synth.make_mfcc(B, T, input_size=ARCHS[arch][0], seed=seed)
-
-
-def _oracle_layer(x_cpu, p64, layer, bn, chunk=32):
-    outs = []
-    for lo in range(0, x_cpu.shape[0], chunk):
-        outs.append(oracle.tdnn_layer(x_cpu[lo:lo + chunk].double(), p64, f"time_context_layers.{layer}.",
-                                      oracle.CONTEXTS[layer], bn))
-    return torch.cat(outs)
-
-
-def _worst_rel(got, ref64):
-    g = got.double().cpu().reshape(-1, got.shape[-1])
-    r = ref64.reshape(-1, ref64.shape[-1])
-    return ((g - r).norm(dim=1) / r.norm(dim=1).clamp_min(1e-30)).max().item()
 
 
 def _num_cu(m):
@@ -166,7 +134,7 @@ def test_every_layer_every_form(arch, B, T):
     ms, mw, md, p64, bn = a["split"], a["wino"], a["direct"], a["p64"], a["bn"]
     h = torch.as_tensor(_mfcc(arch, B, T, seed=SEEDS[arch] * 100 + B * 7 + T)).to(DEV)
     for layer in range(5):
-        ref = _oracle_layer(h.cpu(), p64, layer, bn)
+        ref = oracle_layer(h.cpu(), p64, layer, bn)
         gs = ms.time_context_layers[layer](h)
         assert ms.last_forms()[layer] == SPLIT_FORMS[layer] and ms.last_operands()[layer] == SPLIT_OPERANDS[layer], \
             (arch, layer, ms.last_forms(), ms.last_operands())
@@ -181,7 +149,7 @@ def test_every_layer_every_form(arch, B, T):
         assert_parity(gs, gd, 1e-5, f"{what}: split vs direct")
         if (B, T) == MID and layer > 0:
             # the check that sees a split that drops its lo piece (~2^-17 per operand: under the 1e-4 bar, over this ratio)
-            es, ed = _worst_rel(gs, ref), _worst_rel(gd, ref)
+            es, ed = worst_rel(gs, ref), worst_rel(gd, ref)
             print(f"{arch} layer {layer}: worst-frame error split {es:.3e}, direct {ed:.3e} ({es / ed:.2f}x)")
             assert es <= 1.5 * ed, f"{what}: split {es:.3e} vs direct {ed:.3e}"
         if layer == 4:

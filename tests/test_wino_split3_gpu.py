@@ -7,78 +7,29 @@ Engines on the same weights, each created under its own environment (read once p
   * "direct": XVEC_WINOGRAD=0;
   * "s3all": XVEC_WINO_SPLIT3_MIN_ROWS=0, the split operands at every size (the tails).
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import xvector_oracle as oracle
 from conftest import assert_parity, float_params
+from tdnn_support import DEV, layer_input, make_model, oracle_layer, p64, worst_rel  # noqa: F401 (p64: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 WINO_LAYERS = (1, 2)          # time_context_layers.1 / .2: contexts [-2, 0, 2] and [-3, 0, 3]
-KNOBS = ("XVEC_WINOGRAD", "XVEC_WINO_SPLIT3", "XVEC_WINO_SPLIT3_MIN_ROWS")
-
-
-def _model(sd, env):
-    import xvector_amd as xa
-    m = xa.XVectorModel()
-    m.load_state_dict(sd)
-    m = m.to(DEV).eval()
-    old = {k: os.environ.get(k) for k in KNOBS}
-    try:
-        for k in KNOBS:
-            os.environ.pop(k, None)
-        os.environ.update(env)
-        m._engine(torch.device(DEV))          # the handle is created now, under this environment
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return m
 
 
 @pytest.fixture(scope="module")
 def models(sd42):
-    return {"s3": _model(sd42, {}), "f32": _model(sd42, {"XVEC_WINO_SPLIT3": "0"}),
-            "direct": _model(sd42, {"XVEC_WINOGRAD": "0"}), "s3all": _model(sd42, {"XVEC_WINO_SPLIT3_MIN_ROWS": "0"})}
-
-
-@pytest.fixture(scope="module")
-def p64(sd42):
-    return oracle.cast_params(float_params(sd42), torch.float64)
-
-
-def _oracle_layer(x_cpu, p64, layer, chunk=32):
-    outs = []
-    for lo in range(0, x_cpu.shape[0], chunk):
-        outs.append(oracle.tdnn_layer(x_cpu[lo:lo + chunk].double(), p64, f"time_context_layers.{layer}.",
-                                      oracle.CONTEXTS[layer]))
-    return torch.cat(outs)
-
-
-def _worst_rel(got, ref64):
-    g = got.double().cpu().reshape(-1, got.shape[-1])
-    r = ref64.reshape(-1, ref64.shape[-1])
-    return ((g - r).norm(dim=1) / r.norm(dim=1).clamp_min(1e-30)).max().item()
-
-
-def _layer_input(m, synth, B, T, layer, seed):
-    h = torch.as_tensor(synth.make_mfcc(B, T, seed=seed)).to(DEV)
-    for i in range(layer):
-        h = m.time_context_layers[i](h)
-    return h
+    return {"s3": make_model(sd42), "f32": make_model(sd42, {"XVEC_WINO_SPLIT3": "0"}),
+            "direct": make_model(sd42, {"XVEC_WINOGRAD": "0"}), "s3all": make_model(sd42, {"XVEC_WINO_SPLIT3_MIN_ROWS": "0"})}
 
 
 def test_bench_size_every_element_and_error_ratios(models, p64, synth):
     ms, mf, md = models["s3"], models["f32"], models["direct"]
-    h = _layer_input(md, synth, 256, 300, 1, seed=9001)
+    h = layer_input(md, synth, 256, 300, 1, seed=9001)
     for layer in WINO_LAYERS:
-        ref = _oracle_layer(h.cpu(), p64, layer)
+        ref = oracle_layer(h.cpu(), p64, layer)
         gs = ms.time_context_layers[layer](h)
         assert ms.last_forms()[layer] == "winograd_f23" and ms.last_dispatch()[layer] == "tile128"
         assert ms.last_operands()[layer] == "bf16_split3"
@@ -87,7 +38,7 @@ def test_bench_size_every_element_and_error_ratios(models, p64, synth):
         gd = md.time_context_layers[layer](h)
         assert md.last_forms()[layer] == "direct" and md.last_operands()[layer] == "fp32"
         assert_parity(gs, ref.float(), 1e-4, f"layer {layer} winograd split3 B=256 vs oracle")
-        es, ef, ed = _worst_rel(gs, ref), _worst_rel(gf, ref), _worst_rel(gd, ref)
+        es, ef, ed = worst_rel(gs, ref), worst_rel(gf, ref), worst_rel(gd, ref)
         print(f"layer {layer}: worst-frame error split3 {es:.3e}, fp32 winograd {ef:.3e} ({es / ef:.2f}x), "
               f"direct {ed:.3e} ({es / ed:.2f}x)")
         assert es <= 1.5 * ed, f"layer {layer}: split3 {es:.3e} vs direct {ed:.3e}"
@@ -102,12 +53,12 @@ SHAPES = [(1, 15), (3, 15), (5, 24), (7, 25), (9, 26), (11, 27), (13, 28), (1, 2
 @pytest.mark.parametrize("B,T", SHAPES)
 def test_shapes_and_tails(models, p64, synth, B, T):
     m0, md = models["s3all"], models["direct"]
-    h = _layer_input(md, synth, B, T, 1, seed=9100 + B * 31 + T)
+    h = layer_input(md, synth, B, T, 1, seed=9100 + B * 31 + T)
     for layer in WINO_LAYERS:
         g = m0.time_context_layers[layer](h)
         assert m0.last_forms()[layer] == "winograd_f23" and m0.last_operands()[layer] == "bf16_split3"
         gd = md.time_context_layers[layer](h)
-        assert_parity(g, _oracle_layer(h.cpu(), p64, layer).float(), 1e-4, f"layer {layer} B={B} T={T}")
+        assert_parity(g, oracle_layer(h.cpu(), p64, layer).float(), 1e-4, f"layer {layer} B={B} T={T}")
         assert_parity(g, gd, 1e-5, f"layer {layer} B={B} T={T}: split3 winograd vs direct")
         h = gd
 
@@ -133,7 +84,7 @@ def test_ragged_nan_padding_whole_path(models, sd42, synth):
 
 def test_position_independence_and_determinism(models, synth):
     m0 = models["s3all"]
-    h = _layer_input(m0, synth, 40, 300, 1, seed=9300)
+    h = layer_input(m0, synth, 40, 300, 1, seed=9300)
     probe = h[5].clone()
     outs = []
     for pos in (0, 17, 39):

@@ -4,38 +4,17 @@ buffers of 4 products x 3 bf16 planes x 64 pairs x 16 k, the epilogue constants,
 small enough for the two blocks per CU.  And the split of the U planes (csrc/pack.hip, pack_wino_split3_kernel), restated
 on the host: three bf16 pieces that carry U_k to about 2^-25 relative."""
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
-import pytest
 
-from conftest import ROOT
+from hipcc_support import CSRC, kernel_resources, needs_hipcc_and_make
 
-CSRC = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 PLANNED_LDS = 2 * (4 * 3 * 64 * 16 * 2) + 3 * 128 * 4 + 2 * 2 * 64 * 4 + 2 * 8
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("make") is None, reason="needs hipcc")
+@needs_hipcc_and_make
 def test_wino_s3_kernel_resources():
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
-           "-Wno-pass-failed", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", "-c", "tdnn_wino_s3.hip", "-o", os.devnull]
-    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
-                         ("agprs", r" AGPRs: (\d+)"), ("spill", r"VGPRs Spill: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
+    kernels = kernel_resources("tdnn_wino_s3.hip")
     assert len(kernels) == 1 and "tdnn_wino_s3_kernel" in next(iter(kernels)), kernels
     r = next(iter(kernels.values()))
     assert r["scratch"] == 0 and r.get("spill", 0) == 0, r

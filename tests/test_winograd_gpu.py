@@ -8,84 +8,35 @@ XVEC_WINOGRAD=0 (read once per handle in xvec_create), which runs every layer in
     utterance; ragged batches with NaN-poisoned padding through the whole path;
   * position and determinism, dispatch / form reporting, graph replay.
 """
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import xvector_oracle as oracle
 from conftest import assert_parity, float_params
+from tdnn_support import DEV, layer_input, make_model, oracle_layer, p64, worst_rel  # noqa: F401 (p64: a fixture)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 WINO_LAYERS = (1, 2)          # time_context_layers.1 / .2: contexts [-2, 0, 2] and [-3, 0, 3]
-
-
-def _model(sd, wino=True):
-    import xvector_amd as xa
-    m = xa.XVectorModel()
-    m.load_state_dict(sd)
-    m = m.to(DEV).eval()
-    old = os.environ.get("XVEC_WINOGRAD")
-    try:
-        if wino:
-            os.environ.pop("XVEC_WINOGRAD", None)
-        else:
-            os.environ["XVEC_WINOGRAD"] = "0"
-        m._engine(torch.device(DEV))          # the handle is created now, under this environment
-    finally:
-        if old is None:
-            os.environ.pop("XVEC_WINOGRAD", None)
-        else:
-            os.environ["XVEC_WINOGRAD"] = old
-    return m
 
 
 @pytest.fixture(scope="module")
 def models(sd42):
-    return _model(sd42, True), _model(sd42, False)
-
-
-@pytest.fixture(scope="module")
-def p64(sd42):
-    return oracle.cast_params(float_params(sd42), torch.float64)
-
-
-def _oracle_layer(x_cpu, p64, layer, chunk=32):
-    outs = []
-    for lo in range(0, x_cpu.shape[0], chunk):
-        outs.append(oracle.tdnn_layer(x_cpu[lo:lo + chunk].double(), p64, f"time_context_layers.{layer}.",
-                                      oracle.CONTEXTS[layer]))
-    return torch.cat(outs)
-
-
-def _worst_rel(got, ref64):
-    g = got.double().cpu().reshape(-1, got.shape[-1])
-    r = ref64.reshape(-1, ref64.shape[-1])
-    return ((g - r).norm(dim=1) / r.norm(dim=1).clamp_min(1e-30)).max().item()
-
-
-def _layer_input(mw, synth, B, T, layer, seed):
-    """fp32 input of `layer` (the direct-form chain of layers before it, on the GPU)."""
-    h = torch.as_tensor(synth.make_mfcc(B, T, seed=seed)).to(DEV)
-    for i in range(layer):
-        h = mw.time_context_layers[i](h)
-    return h
+    return make_model(sd42), make_model(sd42, {"XVEC_WINOGRAD": "0"})
 
 
 def test_bench_size_every_element_both_forms(models, p64, synth):
     mw, md = models
-    h = _layer_input(md, synth, 256, 300, 1, seed=7001)
+    h = layer_input(md, synth, 256, 300, 1, seed=7001)
     for layer in WINO_LAYERS:
-        ref = _oracle_layer(h.cpu(), p64, layer)
+        ref = oracle_layer(h.cpu(), p64, layer)
         gw = mw.time_context_layers[layer](h)
         assert mw.last_forms()[layer] == "winograd_f23" and mw.last_dispatch()[layer] == "tile128"
         gd = md.time_context_layers[layer](h)
         assert md.last_forms()[layer] == "direct"
         assert_parity(gw, ref.float(), 1e-4, f"layer {layer} winograd B=256 vs oracle")
         assert_parity(gd, ref.float(), 1e-4, f"layer {layer} direct B=256 vs oracle")
-        ew, ed = _worst_rel(gw, ref), _worst_rel(gd, ref)
+        ew, ed = worst_rel(gw, ref), worst_rel(gd, ref)
         print(f"layer {layer}: worst-frame error winograd {ew:.3e}, direct {ed:.3e} ({ew / ed:.2f}x)")
         assert ew <= 1.5 * ed, f"layer {layer}: winograd {ew:.3e} vs direct {ed:.3e}"
         assert torch.equal(gw, mw.time_context_layers[layer](h)), f"layer {layer}: repeat run differs"
@@ -100,12 +51,12 @@ SHAPES = [(1, 15), (3, 15), (5, 24), (7, 25), (9, 26), (11, 27), (13, 28), (1, 2
 @pytest.mark.parametrize("B,T", SHAPES)
 def test_shapes_and_tails(models, p64, synth, B, T):
     mw, md = models
-    h = _layer_input(md, synth, B, T, 1, seed=7100 + B * 31 + T)
+    h = layer_input(md, synth, B, T, 1, seed=7100 + B * 31 + T)
     for layer in WINO_LAYERS:
         gw = mw.time_context_layers[layer](h)
         assert mw.last_forms()[layer] == "winograd_f23"
         gd = md.time_context_layers[layer](h)
-        assert_parity(gw, _oracle_layer(h.cpu(), p64, layer).float(), 1e-4, f"layer {layer} B={B} T={T}")
+        assert_parity(gw, oracle_layer(h.cpu(), p64, layer).float(), 1e-4, f"layer {layer} B={B} T={T}")
         assert_parity(gw, gd, 1e-5, f"layer {layer} B={B} T={T}: winograd vs direct")
         h = gd
 
@@ -134,7 +85,7 @@ def test_position_independence_and_determinism(models, synth):
     """One utterance at several batch positions gives bit-identical layer-2/3 rows; repeat runs are bit-identical."""
     mw, _ = models
     B, T = 40, 300
-    h = _layer_input(mw, synth, B, T, 1, seed=7300)
+    h = layer_input(mw, synth, B, T, 1, seed=7300)
     probe = h[5].clone()
     outs = []
     for pos in (0, 17, 39):

@@ -3,37 +3,15 @@
 of (64 pairs + 128 channels) x 32 floats, the block's epilogue constants and two 64-pair row tables -- small enough for the
 two blocks per CU."""
 import os
-import re
-import shutil
-import subprocess
 
-import pytest
+from hipcc_support import CSRC, kernel_resources, needs_hipcc_and_make
 
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
 PLANNED_LDS = (2 * (64 + 128) * 32 + 3 * 128 + 2 * 2 * 64) * 4 + 2 * 8
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("make") is None, reason="needs hipcc")
+@needs_hipcc_and_make
 def test_winograd_kernel_resources():
-    cmd = [HIPCC, "-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
-           "-Wno-pass-failed", "-Wno-inline-asm", "-Rpass-analysis=kernel-resource-usage", "-c", "tdnn_wino.hip", "-o", os.devnull]
-    out = subprocess.run(cmd, cwd=CSRC, capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key, pat in (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"),
-                         ("agprs", r" AGPRs: (\d+)"), ("spill", r"VGPRs Spill: (\d+)"),
-                         ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and name:
-                kernels[name][key] = int(m.group(1))
+    kernels = kernel_resources("tdnn_wino.hip")
     assert len(kernels) == 1 and "tdnn_wino_kernel" in next(iter(kernels)), kernels
     r = next(iter(kernels.values()))
     assert r["scratch"] == 0 and r.get("spill", 0) == 0, r
