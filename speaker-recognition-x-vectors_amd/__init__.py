@@ -7,7 +7,8 @@ hand-written gfx950 HIP kernels behind the C-ABI in include/xvec_hip.h.
 from . import synth  # noqa: F401  (numpy only)
 
 __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontEnd", "PldaScorer", "hip", "extract",
-           "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject"]
+           "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject", "evaluate", "TrialList", "TrialResult",
+           "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object"]
 
 
 def __getattr__(name):
@@ -24,7 +25,10 @@ def __getattr__(name):
     if name in ("PldaStats", "PLDA", "StatObject"):
         from . import plda
         return getattr(plda, name)
-    if name in ("hip", "model", "extract", "frontend", "scoring", "plda"):
+    if name in ("TrialList", "TrialResult", "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object"):
+        from . import evaluate
+        return getattr(evaluate, name)
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -1,0 +1,693 @@
+// Trial-list evaluation: EER and minDCF from scores that stay on the device.
+//   reference: plda_score_stat.py:36-97 -> speechbrain 0.5.12 utils.metric_stats EER / minDCF (float32 tensors)
+// C ABI and the algorithm: include/xvec_eval.h.  Stages, one kernel each:
+//   gather + key   trial score -> fp32 (RNE) -> order-preserving 32-bit key, target bit next to it
+//   sort           stable LSD radix sort, 4 passes of 8 bits: per-tile digit histogram, scan of the histograms, scatter that
+//                  ranks inside the tile with wave ballots and reorders through LDS
+//   prefix sum     of the target bit: per-tile counts, scan of the counts; the last phase runs inside the sweep
+//   sweep          at the last element of every run of equal keys: both arg-min objectives; block partials
+//   final          one block reduces the partials and writes xvec_eval_result
+// Counters are integer counts (order does not matter); nothing else goes through an atomic on global memory.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <limits>
+
+#include "../../include/xvec_eval.h"
+#include "../../include/xvec_hip.h"
+
+namespace xvec {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kItems = 16;
+constexpr int kTile = kThreads * kItems;      // elements a block owns in every stage
+constexpr int kWaves = kThreads / 64;
+constexpr int kRadix = 256;                   // 8-bit digits
+constexpr uint8_t kBitVoid = 2;               // a trial left out (NaN, bad index, skipped diagonal): key 0xffffffff, sorts last
+constexpr uint32_t kKeyVoid = 0xffffffffu;    // above the key of +inf (0xff800000); no finite score or infinity maps to it
+
+// counters in the workspace (uint64 each)
+enum { kCntNan = 0, kCntBad = 1, kCntSkipped = 2, kCntTargets = 3, kCounters = 4 };
+
+// ---------------------------------------------------------------- helpers
+
+// fp64 score -> fp32 (round to nearest even) -> key with key(a) < key(b) iff a < b; -0.0 and +0.0 share 0x80000000
+__device__ __forceinline__ uint32_t score_key(double s) {
+    uint32_t u = __float_as_uint(__double2float_rn(s));
+    if ((u << 1) == 0u) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ double key_score(uint32_t k) {
+    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+    return (double)__uint_as_float(u);
+}
+
+// Exclusive scan of one value per thread over the block's 256 threads (thread order); *total (if given) receives the sum in
+// every thread.  wtot: kWaves words of LDS.  Every thread of the block must call it.
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    if (lane == 63) wtot[wave] = x;
+    __syncthreads();
+    uint32_t add = 0, t = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+        const uint32_t s = wtot[w];
+        if (w < wave) add += s;
+        t += s;
+    }
+    if (total) *total = t;
+    __syncthreads();
+    return add + x - v;
+}
+
+// ---------------------------------------------------------------- stage 1: gather and key
+
+struct GatherArgs {
+    const double* scores;
+    int64_t ld, n_rows, n_cols, n;
+    const int32_t* a;          // row_idx | row_class
+    const int32_t* b;          // col_idx | col_class
+    const uint8_t* is_target;  // trial list only
+    int skip_diagonal;         // all pairs only
+    uint32_t* keys;
+    uint8_t* bits;
+    unsigned long long* counters;
+};
+
+template <bool ALL_PAIRS>
+__global__ __launch_bounds__(kThreads) void eval_gather_kernel(const GatherArgs g) {
+    __shared__ uint32_t cnt[3];
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * kTile;
+    uint32_t n_nan = 0, n_bad = 0, n_skip = 0;
+#pragma unroll 4
+    for (int k = 0; k < kItems; ++k) {
+        const int64_t t = base + k * kThreads + threadIdx.x;
+        if (t >= g.n) break;
+        int64_t row, col;
+        bool target, use = true;
+        if (ALL_PAIRS) {
+            row = (int64_t)((uint32_t)t / (uint32_t)g.n_cols);       // t < 2^31, n_cols < 2^31
+            col = t - row * g.n_cols;
+            target = g.a[row] == g.b[col];
+            if (g.skip_diagonal && row == col) {
+                use = false;
+                ++n_skip;
+            }
+        } else {
+            row = g.a ? (int64_t)g.a[t] : 0;
+            col = g.b ? (int64_t)g.b[t] : t;
+            target = g.is_target[t] != 0;
+            if (row < 0 || row >= g.n_rows || col < 0 || col >= g.n_cols) {      // never dereferenced
+                use = false;
+                ++n_bad;
+            }
+        }
+        uint32_t key = kKeyVoid;
+        uint8_t bit = kBitVoid;
+        if (use) {
+            const double s = g.scores[row * g.ld + col];
+            if (s != s) {
+                ++n_nan;
+            } else {
+                key = score_key(s);
+                bit = target ? 1 : 0;
+            }
+        }
+        g.keys[t] = key;
+        g.bits[t] = bit;
+    }
+    if (n_nan) atomicAdd(&cnt[0], n_nan);
+    if (n_bad) atomicAdd(&cnt[1], n_bad);
+    if (n_skip) atomicAdd(&cnt[2], n_skip);
+    __syncthreads();
+    if (threadIdx.x < 3 && cnt[threadIdx.x])
+        atomicAdd(&g.counters[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);      // kCntNan, kCntBad, kCntSkipped
+}
+
+// ---------------------------------------------------------------- stage 2: radix sort
+
+// hist[digit * num_tiles + tile] = elements of the tile with that digit (digit-major: one scan of the whole table gives every
+// (digit, tile) its first output position)
+__global__ __launch_bounds__(kThreads) void eval_hist_kernel(const uint32_t* __restrict__ keys, int64_t n, int shift,
+                                                             uint32_t* __restrict__ hist, int num_tiles) {
+    __shared__ uint32_t h[kRadix];
+    h[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * kTile;
+#pragma unroll 4
+    for (int k = 0; k < kItems; ++k) {
+        const int64_t i = base + k * kThreads + threadIdx.x;
+        if (i < n) atomicAdd(&h[(keys[i] >> shift) & (kRadix - 1)], 1u);
+    }
+    __syncthreads();
+    hist[(size_t)threadIdx.x * num_tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// In-place exclusive scan of a uint32 array of any length, three launches: chunk sums, scan of the chunk sums (one block),
+// scan of every chunk with its offset.  A chunk is kTile elements.
+__global__ __launch_bounds__(kThreads) void eval_scan_sums_kernel(const uint32_t* __restrict__ v, int64_t len,
+                                                                  uint32_t* __restrict__ sums) {
+    __shared__ uint32_t wtot[kWaves];
+    const int64_t base = (int64_t)blockIdx.x * kTile;
+    uint32_t s = 0;
+#pragma unroll 4
+    for (int k = 0; k < kItems; ++k) {
+        const int64_t i = base + k * kThreads + threadIdx.x;
+        if (i < len) s += v[i];
+    }
+    uint32_t total;
+    block_excl_scan(s, wtot, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kThreads) void eval_scan_top_kernel(uint32_t* __restrict__ sums, int64_t n_sums,
+                                                                 unsigned long long* __restrict__ total_out) {
+    __shared__ uint32_t wtot[kWaves];
+    uint32_t carry = 0;
+    for (int64_t c0 = 0; c0 < n_sums; c0 += kThreads) {
+        const int64_t i = c0 + threadIdx.x;
+        const uint32_t v = i < n_sums ? sums[i] : 0u;
+        uint32_t total;
+        const uint32_t e = block_excl_scan(v, wtot, &total);
+        if (i < n_sums) sums[i] = carry + e;
+        carry += total;
+    }
+    if (total_out && threadIdx.x == 0) *total_out = carry;
+}
+
+__global__ __launch_bounds__(kThreads) void eval_scan_apply_kernel(uint32_t* __restrict__ v, int64_t len,
+                                                                   const uint32_t* __restrict__ sums) {
+    __shared__ uint32_t wtot[kWaves];
+    const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
+    uint32_t x[kItems], s = 0;
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        x[k] = base + k < len ? v[base + k] : 0u;
+        s += x[k];
+    }
+    uint32_t run = block_excl_scan(s, wtot, nullptr) + sums[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        if (base + k < len) v[base + k] = run;
+        run += x[k];
+    }
+}
+
+// One pass: the tile's elements, in input order, go to offs[digit][tile] + (rank among the tile's elements of that digit).
+// Wave w owns the elements [w * 1024, (w + 1) * 1024) of the tile, 64 at a time: the lanes with the same digit find each other
+// with eight ballots, rank = that wave's count of the digit so far + lanes below.  The tile is then laid out in digit order in
+// LDS and written from there, so that neighbouring threads write neighbouring addresses within each digit's run.
+__global__ __launch_bounds__(kThreads) void eval_scatter_kernel(const uint32_t* __restrict__ kin,
+                                                                const uint8_t* __restrict__ bin,
+                                                                uint32_t* __restrict__ kout, uint8_t* __restrict__ bout,
+                                                                int64_t n, int shift, const uint32_t* __restrict__ offs,
+                                                                int num_tiles) {
+    __shared__ uint32_t wcnt[kWaves][kRadix];     // per wave: running count of each digit, then the wave's base inside the digit
+    __shared__ uint32_t dstart[kRadix];           // first tile-local position of each digit
+    __shared__ uint32_t goff[kRadix];             // first output position of each digit of this tile
+    __shared__ uint32_t wtot[kWaves];
+    __shared__ uint32_t skey[kTile];
+    __shared__ uint8_t sbit[kTile];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) wcnt[w][tid] = 0;
+    __syncthreads();
+    const int64_t base = (int64_t)blockIdx.x * kTile;
+    const int cnt = (int)std::min<int64_t>(kTile, n - base);
+    const uint64_t below_mask = (1ull << lane) - 1ull;
+
+    uint32_t key[kItems], rank[kItems];
+    uint8_t bit[kItems];
+#pragma unroll
+    for (int r = 0; r < kItems; ++r) {
+        const int li = wave * (64 * kItems) + r * 64 + lane;
+        const bool active = li < cnt;
+        key[r] = active ? kin[base + li] : 0u;
+        bit[r] = active ? bin[base + li] : (uint8_t)0;
+        const uint32_t d = (key[r] >> shift) & (kRadix - 1);
+        uint64_t peers = __ballot(active);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const bool set = (d >> b) & 1u;
+            const uint64_t bal = __ballot(set);
+            peers &= set ? bal : ~bal;
+        }
+        const uint32_t below = (uint32_t)__popcll(peers & below_mask);
+        const uint32_t prev = active ? wcnt[wave][d] : 0u;
+        __builtin_amdgcn_wave_barrier();
+        if (active && below == 0) wcnt[wave][d] = prev + (uint32_t)__popcll(peers);     // the lowest lane of each digit
+        __builtin_amdgcn_wave_barrier();
+        rank[r] = prev + below;
+    }
+    __syncthreads();
+    {   // thread = digit: the waves' counts -> each wave's base inside the digit; digit totals -> tile-local starts
+        uint32_t run = 0;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) {
+            const uint32_t c = wcnt[w][tid];
+            wcnt[w][tid] = run;
+            run += c;
+        }
+        dstart[tid] = block_excl_scan(run, wtot, nullptr);
+        goff[tid] = offs[(size_t)tid * num_tiles + blockIdx.x];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < kItems; ++r) {
+        const int li = wave * (64 * kItems) + r * 64 + lane;
+        if (li < cnt) {
+            const uint32_t d = (key[r] >> shift) & (kRadix - 1);
+            const uint32_t p = dstart[d] + wcnt[wave][d] + rank[r];
+            if (p < (uint32_t)kTile) {      // always true: a bound, not a branch taken
+                skey[p] = key[r];
+                sbit[p] = bit[r];
+            }
+        }
+    }
+    __syncthreads();
+#pragma unroll 4
+    for (int k = 0; k < kItems; ++k) {
+        const int p = k * kThreads + tid;
+        if (p < cnt) {
+            const uint32_t kk = skey[p];
+            const uint32_t d = (kk >> shift) & (kRadix - 1);
+            const int64_t pos = (int64_t)goff[d] + (int64_t)(p - (int)dstart[d]);
+            if (pos >= 0 && pos < n) {      // always true when offs is the scan of this pass's histogram
+                kout[pos] = kk;
+                bout[pos] = sbit[p];
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------- stage 3: target counts per tile
+
+__global__ __launch_bounds__(kThreads) void eval_bit_sums_kernel(const uint8_t* __restrict__ bits, int64_t n,
+                                                                 uint32_t* __restrict__ sums) {
+    __shared__ uint32_t wtot[kWaves];
+    const int64_t base = (int64_t)blockIdx.x * kTile;
+    uint32_t s = 0;
+#pragma unroll 4
+    for (int k = 0; k < kItems; ++k) {
+        const int64_t i = base + k * kThreads + threadIdx.x;
+        if (i < n) s += bits[i] == 1;
+    }
+    uint32_t total;
+    block_excl_scan(s, wtot, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// ---------------------------------------------------------------- stage 4: sweep
+
+// A candidate threshold: objective, sorted index, targets at or below it.  Order: smaller objective, then smaller index --
+// a total order, so the reduction gives the same winner whatever its shape.
+struct EerCand {
+    int64_t val, idx, tp;
+};
+struct DcfCand {
+    double val;
+    int64_t idx, tp;
+};
+__device__ __forceinline__ bool better(const EerCand& a, const EerCand& b) {
+    return a.val < b.val || (a.val == b.val && a.idx < b.idx);
+}
+__device__ __forceinline__ bool better(const DcfCand& a, const DcfCand& b) {
+    return a.val < b.val || (a.val == b.val && a.idx < b.idx);
+}
+constexpr int64_t kNoIdx = std::numeric_limits<int64_t>::max();
+
+template <typename C>
+__device__ __forceinline__ C block_best(C mine, C* sh) {
+    sh[threadIdx.x] = mine;
+    __syncthreads();
+#pragma unroll
+    for (int half = kThreads / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half && better(sh[threadIdx.x + half], sh[threadIdx.x])) sh[threadIdx.x] = sh[threadIdx.x + half];
+        __syncthreads();
+    }
+    return sh[0];
+}
+
+struct SweepArgs {
+    const uint32_t* keys;
+    const uint8_t* bits;
+    int64_t n;
+    const unsigned long long* counters;
+    const uint32_t* tile_off;      // targets in front of each tile (scanned per-tile counts)
+    double c_miss, c_fa, p_target;
+    EerCand* eer_part;
+    DcfCand* dcf_part;
+};
+
+__global__ __launch_bounds__(kThreads) void eval_sweep_kernel(const SweepArgs g) {
+    __shared__ uint32_t wtot[kWaves];
+    __shared__ EerCand s_eer[kThreads];
+    __shared__ DcfCand s_dcf[kThreads];
+    const int64_t m = g.n - (int64_t)(g.counters[kCntNan] + g.counters[kCntBad] + g.counters[kCntSkipped]);   // trials kept: the sorted prefix
+    const int64_t P = (int64_t)g.counters[kCntTargets], N = m - P;
+    const int64_t base = (int64_t)blockIdx.x * kTile + (int64_t)threadIdx.x * kItems;
+    uint32_t key[kItems + 1];
+    uint8_t bit[kItems];
+    uint32_t mine = 0;
+#pragma unroll
+    for (int k = 0; k < kItems; ++k) {
+        const bool in = base + k < m;
+        key[k] = in ? g.keys[base + k] : 0u;
+        bit[k] = in ? g.bits[base + k] : (uint8_t)0;
+        mine += bit[k] == 1;
+    }
+    key[kItems] = base + kItems < m ? g.keys[base + kItems] : 0u;
+    int64_t tp = (int64_t)block_excl_scan(mine, wtot, nullptr) + (int64_t)g.tile_off[blockIdx.x];
+    EerCand be{kNoIdx, kNoIdx, 0};
+    DcfCand bd{std::numeric_limits<double>::infinity(), kNoIdx, 0};
+    if (P > 0 && N > 0) {
+#pragma unroll
+        for (int k = 0; k < kItems; ++k) {
+            const int64_t i = base + k;
+            if (i >= m) break;
+            tp += bit[k] == 1;
+            if (i + 1 < m && key[k + 1] == key[k]) continue;      // inside a run of equal scores
+            const int64_t fa = N - ((i + 1) - tp);                // non-targets above the threshold
+            const int64_t diff = fa * P - tp * N;                 // |.| < 2^62
+            const EerCand ce{diff < 0 ? -diff : diff, i, tp};
+            if (better(ce, be)) be = ce;
+            const double frr = (double)tp / (double)P, far = (double)fa / (double)N;
+            const DcfCand cd{g.c_miss * frr * g.p_target + g.c_fa * far * (1.0 - g.p_target), i, tp};
+            if (better(cd, bd)) bd = cd;
+        }
+    }
+    be = block_best(be, s_eer);
+    bd = block_best(bd, s_dcf);
+    if (threadIdx.x == 0) {
+        g.eer_part[blockIdx.x] = be;
+        g.dcf_part[blockIdx.x] = bd;
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void eval_final_kernel(const SweepArgs g, int num_tiles, xvec_eval_result* out) {
+    __shared__ EerCand s_eer[kThreads];
+    __shared__ DcfCand s_dcf[kThreads];
+    EerCand be{kNoIdx, kNoIdx, 0};
+    DcfCand bd{std::numeric_limits<double>::infinity(), kNoIdx, 0};
+    for (int t = threadIdx.x; t < num_tiles; t += kThreads) {
+        const EerCand ce = g.eer_part[t];
+        const DcfCand cd = g.dcf_part[t];
+        if (better(ce, be)) be = ce;
+        if (better(cd, bd)) bd = cd;
+    }
+    be = block_best(be, s_eer);
+    bd = block_best(bd, s_dcf);
+    if (threadIdx.x != 0) return;
+    const int64_t n_nan = (int64_t)g.counters[kCntNan], n_bad = (int64_t)g.counters[kCntBad];
+    const int64_t m = g.n - n_nan - n_bad - (int64_t)g.counters[kCntSkipped];
+    const int64_t P = (int64_t)g.counters[kCntTargets], N = m - P;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    xvec_eval_result r;
+    r.eer = r.eer_threshold = r.far = r.frr = r.min_dcf = r.min_dcf_threshold = nan;
+    r.n_target = P;
+    r.n_nontarget = N;
+    r.n_nan = n_nan;
+    r.n_bad_index = n_bad;
+    if (be.idx != kNoIdx && bd.idx != kNoIdx && be.idx < m && bd.idx < m) {
+        const int64_t fa = N - ((be.idx + 1) - be.tp);
+        r.far = (double)fa / (double)N;
+        r.frr = (double)be.tp / (double)P;
+        r.eer = (r.far + r.frr) / 2.0;
+        r.eer_threshold = key_score(g.keys[be.idx]);
+        r.min_dcf = bd.val;
+        r.min_dcf_threshold = key_score(g.keys[bd.idx]);
+    }
+    *out = r;
+}
+
+// ---------------------------------------------------------------- host side
+
+thread_local char g_eerr[384] = "";
+
+int efail(int code, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_eerr, sizeof(g_eerr), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+int elaunch(const char* what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return efail(XVEC_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
+    return XVEC_OK;
+}
+
+inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+inline int64_t chunks(int64_t len) { return (len + kTile - 1) / kTile; }
+
+struct EvalPlan {
+    int64_t n, tiles, hist_len, hist_chunks, tile_chunks;
+    size_t off_keys[2], off_bits[2], off_hist, off_hist_sums, off_tile_sums, off_tile_top, off_counters, off_eer, off_dcf, total;
+};
+
+EvalPlan make_plan(int64_t n) {
+    EvalPlan p{};
+    p.n = n;
+    p.tiles = chunks(n);
+    p.hist_len = p.tiles * kRadix;
+    p.hist_chunks = chunks(p.hist_len);
+    p.tile_chunks = chunks(p.tiles);
+    size_t o = 0;
+    auto take = [&](size_t bytes) {
+        const size_t at = o;
+        o += align256(bytes);
+        return at;
+    };
+    for (int i = 0; i < 2; ++i) p.off_keys[i] = take((size_t)n * sizeof(uint32_t));
+    for (int i = 0; i < 2; ++i) p.off_bits[i] = take((size_t)n);
+    p.off_hist = take((size_t)p.hist_len * sizeof(uint32_t));
+    p.off_hist_sums = take((size_t)p.hist_chunks * sizeof(uint32_t));
+    p.off_tile_sums = take((size_t)p.tiles * sizeof(uint32_t));
+    p.off_tile_top = take((size_t)p.tile_chunks * sizeof(uint32_t));
+    p.off_counters = take(kCounters * sizeof(unsigned long long));
+    p.off_eer = take((size_t)p.tiles * sizeof(EerCand));
+    p.off_dcf = take((size_t)p.tiles * sizeof(DcfCand));
+    p.total = o;
+    return p;
+}
+
+bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffff; }
+
+struct Buffers {
+    uint32_t* keys[2];
+    uint8_t* bits[2];
+    uint32_t *hist, *hist_sums, *tile_sums, *tile_top;
+    unsigned long long* counters;
+    EerCand* eer;
+    DcfCand* dcf;
+};
+
+Buffers carve(void* workspace, const EvalPlan& p) {
+    char* ws = static_cast<char*>(workspace);
+    Buffers b;
+    for (int i = 0; i < 2; ++i) {
+        b.keys[i] = reinterpret_cast<uint32_t*>(ws + p.off_keys[i]);
+        b.bits[i] = reinterpret_cast<uint8_t*>(ws + p.off_bits[i]);
+    }
+    b.hist = reinterpret_cast<uint32_t*>(ws + p.off_hist);
+    b.hist_sums = reinterpret_cast<uint32_t*>(ws + p.off_hist_sums);
+    b.tile_sums = reinterpret_cast<uint32_t*>(ws + p.off_tile_sums);
+    b.tile_top = reinterpret_cast<uint32_t*>(ws + p.off_tile_top);
+    b.counters = reinterpret_cast<unsigned long long*>(ws + p.off_counters);
+    b.eer = reinterpret_cast<EerCand*>(ws + p.off_eer);
+    b.dcf = reinterpret_cast<DcfCand*>(ws + p.off_dcf);
+    return b;
+}
+
+// v[0 .. len) <- its exclusive scan; *total_out (device, may be null) <- the sum
+int scan_in_place(uint32_t* v, int64_t len, uint32_t* sums, unsigned long long* total_out, hipStream_t s) {
+    const int64_t nc = chunks(len);
+    int rc;
+    eval_scan_sums_kernel<<<(unsigned)nc, kThreads, 0, s>>>(v, len, sums);
+    if ((rc = elaunch("eval_scan_sums_kernel"))) return rc;
+    eval_scan_top_kernel<<<1, kThreads, 0, s>>>(sums, nc, total_out);
+    if ((rc = elaunch("eval_scan_top_kernel"))) return rc;
+    eval_scan_apply_kernel<<<(unsigned)nc, kThreads, 0, s>>>(v, len, sums);
+    return elaunch("eval_scan_apply_kernel");
+}
+
+// stages 1 and 2: afterwards keys[0] / bits[0] hold the sorted pairs
+int gather_and_sort(const GatherArgs& ga, bool all_pairs, const EvalPlan& p, const Buffers& b, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(b.counters, 0, kCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return efail(XVEC_ERR_HIP, "clearing the counters failed: %s", hipGetErrorString(e));
+    const unsigned grid = (unsigned)p.tiles;
+    int rc;
+    if (all_pairs) eval_gather_kernel<true><<<grid, kThreads, 0, s>>>(ga);
+    else eval_gather_kernel<false><<<grid, kThreads, 0, s>>>(ga);
+    if ((rc = elaunch("eval_gather_kernel"))) return rc;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int src = pass & 1, dst = src ^ 1, shift = 8 * pass;
+        eval_hist_kernel<<<grid, kThreads, 0, s>>>(b.keys[src], p.n, shift, b.hist, (int)p.tiles);
+        if ((rc = elaunch("eval_hist_kernel"))) return rc;
+        if ((rc = scan_in_place(b.hist, p.hist_len, b.hist_sums, nullptr, s))) return rc;
+        eval_scatter_kernel<<<grid, kThreads, 0, s>>>(b.keys[src], b.bits[src], b.keys[dst], b.bits[dst], p.n, shift, b.hist,
+                                                      (int)p.tiles);
+        if ((rc = elaunch("eval_scatter_kernel"))) return rc;
+    }
+    return XVEC_OK;
+}
+
+int sweep(const EvalPlan& p, const Buffers& b, double c_miss, double c_fa, double p_target, xvec_eval_result* out,
+          hipStream_t s) {
+    const unsigned grid = (unsigned)p.tiles;
+    int rc;
+    eval_bit_sums_kernel<<<grid, kThreads, 0, s>>>(b.bits[0], p.n, b.tile_sums);
+    if ((rc = elaunch("eval_bit_sums_kernel"))) return rc;
+    if ((rc = scan_in_place(b.tile_sums, p.tiles, b.tile_top, b.counters + kCntTargets, s))) return rc;
+    SweepArgs g{};
+    g.keys = b.keys[0];
+    g.bits = b.bits[0];
+    g.n = p.n;
+    g.counters = b.counters;
+    g.tile_off = b.tile_sums;
+    g.c_miss = c_miss;
+    g.c_fa = c_fa;
+    g.p_target = p_target;
+    g.eer_part = b.eer;
+    g.dcf_part = b.dcf;
+    eval_sweep_kernel<<<grid, kThreads, 0, s>>>(g);
+    if ((rc = elaunch("eval_sweep_kernel"))) return rc;
+    eval_final_kernel<<<1, kThreads, 0, s>>>(g, (int)p.tiles, out);
+    return elaunch("eval_final_kernel");
+}
+
+int check_matrix(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols) {
+    if (!scores) return efail(XVEC_ERR_ARG, "null pointer: scores");
+    if (n_rows < 1 || n_cols < 1 || n_rows > 0x7fffffff || n_cols > 0x7fffffff)
+        return efail(XVEC_ERR_ARG, "score matrix [%lld, %lld]: both sizes must be in 1 .. 2^31 - 1", (long long)n_rows,
+                     (long long)n_cols);
+    if (ld < n_cols) return efail(XVEC_ERR_ARG, "ld = %lld is smaller than n_cols = %lld", (long long)ld, (long long)n_cols);
+    return XVEC_OK;
+}
+
+int check_costs(double c_miss, double c_fa, double p_target) {
+    if (!(c_miss >= 0.0) || !(c_fa >= 0.0) || !(p_target >= 0.0 && p_target <= 1.0) || c_miss > 1e300 || c_fa > 1e300)
+        return efail(XVEC_ERR_ARG, "c_miss = %g and c_fa = %g must be finite and >= 0, p_target = %g in [0, 1]", c_miss, c_fa,
+                     p_target);
+    return XVEC_OK;
+}
+
+int check_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
+                 const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, void* workspace, size_t workspace_bytes,
+                 EvalPlan* plan) {
+    if (n_trials < 1) return efail(XVEC_ERR_ARG, "n_trials = %lld: need at least one trial", (long long)n_trials);
+    if (n_trials > 0x7fffffff) return efail(XVEC_ERR_TOO_LARGE, "n_trials = %lld exceeds 2^31 - 1", (long long)n_trials);
+    int rc;
+    if ((rc = check_matrix(scores, ld, n_rows, n_cols))) return rc;
+    if (!is_target || !workspace) return efail(XVEC_ERR_ARG, "null pointer");
+    if ((row_idx == nullptr) != (col_idx == nullptr))
+        return efail(XVEC_ERR_ARG, "row_idx and col_idx must both be given or both be null");
+    if (!row_idx && (n_rows != 1 || n_cols < n_trials))
+        return efail(XVEC_ERR_ARG, "without index arrays the scores are a vector: n_rows = 1 and n_cols >= n_trials "
+                                   "(got [%lld, %lld] for %lld trials)", (long long)n_rows, (long long)n_cols, (long long)n_trials);
+    *plan = make_plan(n_trials);
+    if (workspace_bytes < plan->total)
+        return efail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, plan->total);
+    return XVEC_OK;
+}
+
+GatherArgs trial_args(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
+                      const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, const Buffers& b) {
+    GatherArgs ga{};
+    ga.scores = scores;
+    ga.ld = ld;
+    ga.n_rows = n_rows;
+    ga.n_cols = n_cols;
+    ga.n = n_trials;
+    ga.a = row_idx;
+    ga.b = col_idx;
+    ga.is_target = is_target;
+    ga.keys = b.keys[0];
+    ga.bits = b.bits[0];
+    ga.counters = b.counters;
+    return ga;
+}
+
+}  // namespace
+}  // namespace xvec
+
+using namespace xvec;
+
+extern "C" {
+
+const char* xvec_eval_last_error(void) { return g_eerr; }
+
+size_t xvec_eval_workspace_bytes(int64_t n_trials) {
+    if (!count_ok(n_trials)) return 0;
+    return make_plan(n_trials).total;
+}
+
+int xvec_eval_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
+                     const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, double c_miss, double c_fa,
+                     double p_target, xvec_eval_result* out, void* workspace, size_t workspace_bytes, xvec_stream stream) {
+    EvalPlan p;
+    int rc;
+    if ((rc = check_trials(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, workspace, workspace_bytes, &p)))
+        return rc;
+    if (!out) return efail(XVEC_ERR_ARG, "null pointer: out");
+    if ((rc = check_costs(c_miss, c_fa, p_target))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Buffers b = carve(workspace, p);
+    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, b), false, p, b, s)))
+        return rc;
+    return sweep(p, b, c_miss, c_fa, p_target, out, s);
+}
+
+int xvec_eval_all_pairs(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_class,
+                        const int32_t* col_class, int32_t skip_diagonal, double c_miss, double c_fa, double p_target,
+                        xvec_eval_result* out, void* workspace, size_t workspace_bytes, xvec_stream stream) {
+    int rc;
+    if ((rc = check_matrix(scores, ld, n_rows, n_cols))) return rc;
+    if (!row_class || !col_class || !out || !workspace) return efail(XVEC_ERR_ARG, "null pointer");
+    const int64_t n = n_rows * n_cols;      // both < 2^31: no overflow
+    if (n > 0x7fffffff)
+        return efail(XVEC_ERR_TOO_LARGE, "%lld x %lld cells exceed 2^31 - 1 trials", (long long)n_rows, (long long)n_cols);
+    if ((rc = check_costs(c_miss, c_fa, p_target))) return rc;
+    const EvalPlan p = make_plan(n);
+    if (workspace_bytes < p.total)
+        return efail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Buffers b = carve(workspace, p);
+    GatherArgs ga = trial_args(scores, ld, n_rows, n_cols, row_class, col_class, nullptr, n, b);
+    ga.skip_diagonal = skip_diagonal != 0;
+    if ((rc = gather_and_sort(ga, true, p, b, s))) return rc;
+    return sweep(p, b, c_miss, c_fa, p_target, out, s);
+}
+
+int xvec_eval_sorted_keys(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
+                          const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, uint32_t* keys_out,
+                          uint8_t* bits_out, void* workspace, size_t workspace_bytes, xvec_stream stream) {
+    EvalPlan p;
+    int rc;
+    if ((rc = check_trials(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, workspace, workspace_bytes, &p)))
+        return rc;
+    if (!keys_out || !bits_out) return efail(XVEC_ERR_ARG, "null pointer: keys_out / bits_out");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Buffers b = carve(workspace, p);
+    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, b), false, p, b, s)))
+        return rc;
+    hipError_t e = hipMemcpyAsync(keys_out, b.keys[0], (size_t)n_trials * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(bits_out, b.bits[0], (size_t)n_trials, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return efail(XVEC_ERR_HIP, "copying the sorted pairs failed: %s", hipGetErrorString(e));
+    return XVEC_OK;
+}
+
+}  // extern "C"

@@ -117,6 +117,14 @@ _SIGS = {
                                   _vp, _vp, C.c_size_t, _vp]),
     "xvec_plda_em_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "xvec_plda_em_products": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, C.c_size_t, _vp]),
+    # include/xvec_eval.h
+    "xvec_eval_last_error": (C.c_char_p, []),
+    "xvec_eval_workspace_bytes": (C.c_size_t, [_i64]),
+    "xvec_eval_trials": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                   C.c_size_t, _vp]),
+    "xvec_eval_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                      C.c_size_t, _vp]),
+    "xvec_eval_sorted_keys": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 for _name, (_res, _args) in _SIGS.items():
