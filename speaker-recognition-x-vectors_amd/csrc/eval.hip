@@ -11,12 +11,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <limits>
 
 #include "../../include/xvec_eval.h"
 #include "../../include/xvec_hip.h"
+#include "host_support.h"
 
 namespace xvec {
 namespace {
@@ -434,178 +434,134 @@ __global__ __launch_bounds__(kThreads) void eval_final_kernel(const SweepArgs g,
 
 // ---------------------------------------------------------------- host side
 
-thread_local char g_eerr[384] = "";
+thread_local ErrorChannel g_eerr;
 
-int efail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_eerr, sizeof(g_eerr), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int elaunch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return efail(XVEC_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return XVEC_OK;
-}
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline int64_t chunks(int64_t len) { return (len + kTile - 1) / kTile; }
 
+// The sizes of one evaluation and its workspace buffers (null, all of them, when the plan is made over a null workspace)
 struct EvalPlan {
-    int64_t n, tiles, hist_len, hist_chunks, tile_chunks;
-    size_t off_keys[2], off_bits[2], off_hist, off_hist_sums, off_tile_sums, off_tile_top, off_counters, off_eer, off_dcf, total;
-};
-
-EvalPlan make_plan(int64_t n) {
-    EvalPlan p{};
-    p.n = n;
-    p.tiles = chunks(n);
-    p.hist_len = p.tiles * kRadix;
-    p.hist_chunks = chunks(p.hist_len);
-    p.tile_chunks = chunks(p.tiles);
-    size_t o = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = o;
-        o += align256(bytes);
-        return at;
-    };
-    for (int i = 0; i < 2; ++i) p.off_keys[i] = take((size_t)n * sizeof(uint32_t));
-    for (int i = 0; i < 2; ++i) p.off_bits[i] = take((size_t)n);
-    p.off_hist = take((size_t)p.hist_len * sizeof(uint32_t));
-    p.off_hist_sums = take((size_t)p.hist_chunks * sizeof(uint32_t));
-    p.off_tile_sums = take((size_t)p.tiles * sizeof(uint32_t));
-    p.off_tile_top = take((size_t)p.tile_chunks * sizeof(uint32_t));
-    p.off_counters = take(kCounters * sizeof(unsigned long long));
-    p.off_eer = take((size_t)p.tiles * sizeof(EerCand));
-    p.off_dcf = take((size_t)p.tiles * sizeof(DcfCand));
-    p.total = o;
-    return p;
-}
-
-bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffff; }
-
-struct Buffers {
+    int64_t n, tiles, hist_len;
     uint32_t* keys[2];
     uint8_t* bits[2];
     uint32_t *hist, *hist_sums, *tile_sums, *tile_top;
     unsigned long long* counters;
     EerCand* eer;
     DcfCand* dcf;
+    size_t total;
 };
 
-Buffers carve(void* workspace, const EvalPlan& p) {
-    char* ws = static_cast<char*>(workspace);
-    Buffers b;
-    for (int i = 0; i < 2; ++i) {
-        b.keys[i] = reinterpret_cast<uint32_t*>(ws + p.off_keys[i]);
-        b.bits[i] = reinterpret_cast<uint8_t*>(ws + p.off_bits[i]);
-    }
-    b.hist = reinterpret_cast<uint32_t*>(ws + p.off_hist);
-    b.hist_sums = reinterpret_cast<uint32_t*>(ws + p.off_hist_sums);
-    b.tile_sums = reinterpret_cast<uint32_t*>(ws + p.off_tile_sums);
-    b.tile_top = reinterpret_cast<uint32_t*>(ws + p.off_tile_top);
-    b.counters = reinterpret_cast<unsigned long long*>(ws + p.off_counters);
-    b.eer = reinterpret_cast<EerCand*>(ws + p.off_eer);
-    b.dcf = reinterpret_cast<DcfCand*>(ws + p.off_dcf);
-    return b;
+EvalPlan make_plan(void* workspace, int64_t n) {
+    EvalPlan p{};
+    p.n = n;
+    p.tiles = chunks(n);
+    p.hist_len = p.tiles * kRadix;
+    Carver c(workspace);
+    for (int i = 0; i < 2; ++i) p.keys[i] = c.take<uint32_t>((size_t)n);
+    for (int i = 0; i < 2; ++i) p.bits[i] = c.take<uint8_t>((size_t)n);
+    p.hist = c.take<uint32_t>((size_t)p.hist_len);
+    p.hist_sums = c.take<uint32_t>((size_t)chunks(p.hist_len));
+    p.tile_sums = c.take<uint32_t>((size_t)p.tiles);
+    p.tile_top = c.take<uint32_t>((size_t)chunks(p.tiles));
+    p.counters = c.take<unsigned long long>(kCounters);
+    p.eer = c.take<EerCand>((size_t)p.tiles);
+    p.dcf = c.take<DcfCand>((size_t)p.tiles);
+    p.total = c.total();
+    return p;
 }
+
+bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffff; }
 
 // v[0 .. len) <- its exclusive scan; *total_out (device, may be null) <- the sum
 int scan_in_place(uint32_t* v, int64_t len, uint32_t* sums, unsigned long long* total_out, hipStream_t s) {
     const int64_t nc = chunks(len);
     int rc;
     eval_scan_sums_kernel<<<(unsigned)nc, kThreads, 0, s>>>(v, len, sums);
-    if ((rc = elaunch("eval_scan_sums_kernel"))) return rc;
+    if ((rc = g_eerr.launch_ok("eval_scan_sums_kernel"))) return rc;
     eval_scan_top_kernel<<<1, kThreads, 0, s>>>(sums, nc, total_out);
-    if ((rc = elaunch("eval_scan_top_kernel"))) return rc;
+    if ((rc = g_eerr.launch_ok("eval_scan_top_kernel"))) return rc;
     eval_scan_apply_kernel<<<(unsigned)nc, kThreads, 0, s>>>(v, len, sums);
-    return elaunch("eval_scan_apply_kernel");
+    return g_eerr.launch_ok("eval_scan_apply_kernel");
 }
 
 // stages 1 and 2: afterwards keys[0] / bits[0] hold the sorted pairs
-int gather_and_sort(const GatherArgs& ga, bool all_pairs, const EvalPlan& p, const Buffers& b, hipStream_t s) {
-    const hipError_t e = hipMemsetAsync(b.counters, 0, kCounters * sizeof(unsigned long long), s);
-    if (e != hipSuccess) return efail(XVEC_ERR_HIP, "clearing the counters failed: %s", hipGetErrorString(e));
+int gather_and_sort(const GatherArgs& ga, bool all_pairs, const EvalPlan& p, hipStream_t s) {
+    const hipError_t e = hipMemsetAsync(p.counters, 0, kCounters * sizeof(unsigned long long), s);
+    if (e != hipSuccess) return g_eerr.fail(XVEC_ERR_HIP, "clearing the counters failed: %s", hipGetErrorString(e));
     const unsigned grid = (unsigned)p.tiles;
     int rc;
     if (all_pairs) eval_gather_kernel<true><<<grid, kThreads, 0, s>>>(ga);
     else eval_gather_kernel<false><<<grid, kThreads, 0, s>>>(ga);
-    if ((rc = elaunch("eval_gather_kernel"))) return rc;
+    if ((rc = g_eerr.launch_ok("eval_gather_kernel"))) return rc;
     for (int pass = 0; pass < 4; ++pass) {
         const int src = pass & 1, dst = src ^ 1, shift = 8 * pass;
-        eval_hist_kernel<<<grid, kThreads, 0, s>>>(b.keys[src], p.n, shift, b.hist, (int)p.tiles);
-        if ((rc = elaunch("eval_hist_kernel"))) return rc;
-        if ((rc = scan_in_place(b.hist, p.hist_len, b.hist_sums, nullptr, s))) return rc;
-        eval_scatter_kernel<<<grid, kThreads, 0, s>>>(b.keys[src], b.bits[src], b.keys[dst], b.bits[dst], p.n, shift, b.hist,
+        eval_hist_kernel<<<grid, kThreads, 0, s>>>(p.keys[src], p.n, shift, p.hist, (int)p.tiles);
+        if ((rc = g_eerr.launch_ok("eval_hist_kernel"))) return rc;
+        if ((rc = scan_in_place(p.hist, p.hist_len, p.hist_sums, nullptr, s))) return rc;
+        eval_scatter_kernel<<<grid, kThreads, 0, s>>>(p.keys[src], p.bits[src], p.keys[dst], p.bits[dst], p.n, shift, p.hist,
                                                       (int)p.tiles);
-        if ((rc = elaunch("eval_scatter_kernel"))) return rc;
+        if ((rc = g_eerr.launch_ok("eval_scatter_kernel"))) return rc;
     }
     return XVEC_OK;
 }
 
-int sweep(const EvalPlan& p, const Buffers& b, double c_miss, double c_fa, double p_target, xvec_eval_result* out,
-          hipStream_t s) {
+int sweep(const EvalPlan& p, double c_miss, double c_fa, double p_target, xvec_eval_result* out, hipStream_t s) {
     const unsigned grid = (unsigned)p.tiles;
     int rc;
-    eval_bit_sums_kernel<<<grid, kThreads, 0, s>>>(b.bits[0], p.n, b.tile_sums);
-    if ((rc = elaunch("eval_bit_sums_kernel"))) return rc;
-    if ((rc = scan_in_place(b.tile_sums, p.tiles, b.tile_top, b.counters + kCntTargets, s))) return rc;
+    eval_bit_sums_kernel<<<grid, kThreads, 0, s>>>(p.bits[0], p.n, p.tile_sums);
+    if ((rc = g_eerr.launch_ok("eval_bit_sums_kernel"))) return rc;
+    if ((rc = scan_in_place(p.tile_sums, p.tiles, p.tile_top, p.counters + kCntTargets, s))) return rc;
     SweepArgs g{};
-    g.keys = b.keys[0];
-    g.bits = b.bits[0];
+    g.keys = p.keys[0];
+    g.bits = p.bits[0];
     g.n = p.n;
-    g.counters = b.counters;
-    g.tile_off = b.tile_sums;
+    g.counters = p.counters;
+    g.tile_off = p.tile_sums;
     g.c_miss = c_miss;
     g.c_fa = c_fa;
     g.p_target = p_target;
-    g.eer_part = b.eer;
-    g.dcf_part = b.dcf;
+    g.eer_part = p.eer;
+    g.dcf_part = p.dcf;
     eval_sweep_kernel<<<grid, kThreads, 0, s>>>(g);
-    if ((rc = elaunch("eval_sweep_kernel"))) return rc;
+    if ((rc = g_eerr.launch_ok("eval_sweep_kernel"))) return rc;
     eval_final_kernel<<<1, kThreads, 0, s>>>(g, (int)p.tiles, out);
-    return elaunch("eval_final_kernel");
+    return g_eerr.launch_ok("eval_final_kernel");
 }
 
 int check_matrix(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols) {
-    if (!scores) return efail(XVEC_ERR_ARG, "null pointer: scores");
+    if (!scores) return g_eerr.fail(XVEC_ERR_ARG, "null pointer: scores");
     if (n_rows < 1 || n_cols < 1 || n_rows > 0x7fffffff || n_cols > 0x7fffffff)
-        return efail(XVEC_ERR_ARG, "score matrix [%lld, %lld]: both sizes must be in 1 .. 2^31 - 1", (long long)n_rows,
-                     (long long)n_cols);
-    if (ld < n_cols) return efail(XVEC_ERR_ARG, "ld = %lld is smaller than n_cols = %lld", (long long)ld, (long long)n_cols);
+        return g_eerr.fail(XVEC_ERR_ARG, "score matrix [%lld, %lld]: both sizes must be in 1 .. 2^31 - 1", (long long)n_rows,
+                           (long long)n_cols);
+    if (ld < n_cols) return g_eerr.fail(XVEC_ERR_ARG, "ld = %lld is smaller than n_cols = %lld", (long long)ld, (long long)n_cols);
     return XVEC_OK;
 }
 
 int check_costs(double c_miss, double c_fa, double p_target) {
     if (!(c_miss >= 0.0) || !(c_fa >= 0.0) || !(p_target >= 0.0 && p_target <= 1.0) || c_miss > 1e300 || c_fa > 1e300)
-        return efail(XVEC_ERR_ARG, "c_miss = %g and c_fa = %g must be finite and >= 0, p_target = %g in [0, 1]", c_miss, c_fa,
-                     p_target);
+        return g_eerr.fail(XVEC_ERR_ARG, "c_miss = %g and c_fa = %g must be finite and >= 0, p_target = %g in [0, 1]", c_miss, c_fa,
+                           p_target);
     return XVEC_OK;
 }
 
 int check_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
                  const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, void* workspace, size_t workspace_bytes,
                  EvalPlan* plan) {
-    if (n_trials < 1) return efail(XVEC_ERR_ARG, "n_trials = %lld: need at least one trial", (long long)n_trials);
-    if (n_trials > 0x7fffffff) return efail(XVEC_ERR_TOO_LARGE, "n_trials = %lld exceeds 2^31 - 1", (long long)n_trials);
+    if (n_trials < 1) return g_eerr.fail(XVEC_ERR_ARG, "n_trials = %lld: need at least one trial", (long long)n_trials);
+    if (n_trials > 0x7fffffff) return g_eerr.fail(XVEC_ERR_TOO_LARGE, "n_trials = %lld exceeds 2^31 - 1", (long long)n_trials);
     int rc;
     if ((rc = check_matrix(scores, ld, n_rows, n_cols))) return rc;
-    if (!is_target || !workspace) return efail(XVEC_ERR_ARG, "null pointer");
+    if (!is_target || !workspace) return g_eerr.fail(XVEC_ERR_ARG, "null pointer");
     if ((row_idx == nullptr) != (col_idx == nullptr))
-        return efail(XVEC_ERR_ARG, "row_idx and col_idx must both be given or both be null");
+        return g_eerr.fail(XVEC_ERR_ARG, "row_idx and col_idx must both be given or both be null");
     if (!row_idx && (n_rows != 1 || n_cols < n_trials))
-        return efail(XVEC_ERR_ARG, "without index arrays the scores are a vector: n_rows = 1 and n_cols >= n_trials "
-                                   "(got [%lld, %lld] for %lld trials)", (long long)n_rows, (long long)n_cols, (long long)n_trials);
-    *plan = make_plan(n_trials);
-    if (workspace_bytes < plan->total)
-        return efail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, plan->total);
-    return XVEC_OK;
+        return g_eerr.fail(XVEC_ERR_ARG, "without index arrays the scores are a vector: n_rows = 1 and n_cols >= n_trials "
+                           "(got [%lld, %lld] for %lld trials)", (long long)n_rows, (long long)n_cols, (long long)n_trials);
+    *plan = make_plan(workspace, n_trials);
+    return workspace_ok(workspace_bytes, plan->total, g_eerr);
 }
 
 GatherArgs trial_args(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
-                      const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, const Buffers& b) {
+                      const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, const EvalPlan& p) {
     GatherArgs ga{};
     ga.scores = scores;
     ga.ld = ld;
@@ -615,9 +571,9 @@ GatherArgs trial_args(const double* scores, int64_t ld, int64_t n_rows, int64_t 
     ga.a = row_idx;
     ga.b = col_idx;
     ga.is_target = is_target;
-    ga.keys = b.keys[0];
-    ga.bits = b.bits[0];
-    ga.counters = b.counters;
+    ga.keys = p.keys[0];
+    ga.bits = p.bits[0];
+    ga.counters = p.counters;
     return ga;
 }
 
@@ -628,11 +584,11 @@ using namespace xvec;
 
 extern "C" {
 
-const char* xvec_eval_last_error(void) { return g_eerr; }
+const char* xvec_eval_last_error(void) { return g_eerr.c_str(); }
 
 size_t xvec_eval_workspace_bytes(int64_t n_trials) {
     if (!count_ok(n_trials)) return 0;
-    return make_plan(n_trials).total;
+    return make_plan(nullptr, n_trials).total;
 }
 
 int xvec_eval_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
@@ -642,13 +598,12 @@ int xvec_eval_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n
     int rc;
     if ((rc = check_trials(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, workspace, workspace_bytes, &p)))
         return rc;
-    if (!out) return efail(XVEC_ERR_ARG, "null pointer: out");
+    if (!out) return g_eerr.fail(XVEC_ERR_ARG, "null pointer: out");
     if ((rc = check_costs(c_miss, c_fa, p_target))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Buffers b = carve(workspace, p);
-    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, b), false, p, b, s)))
+    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, p), false, p, s)))
         return rc;
-    return sweep(p, b, c_miss, c_fa, p_target, out, s);
+    return sweep(p, c_miss, c_fa, p_target, out, s);
 }
 
 int xvec_eval_all_pairs(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_class,
@@ -656,20 +611,18 @@ int xvec_eval_all_pairs(const double* scores, int64_t ld, int64_t n_rows, int64_
                         xvec_eval_result* out, void* workspace, size_t workspace_bytes, xvec_stream stream) {
     int rc;
     if ((rc = check_matrix(scores, ld, n_rows, n_cols))) return rc;
-    if (!row_class || !col_class || !out || !workspace) return efail(XVEC_ERR_ARG, "null pointer");
+    if (!row_class || !col_class || !out || !workspace) return g_eerr.fail(XVEC_ERR_ARG, "null pointer");
     const int64_t n = n_rows * n_cols;      // both < 2^31: no overflow
     if (n > 0x7fffffff)
-        return efail(XVEC_ERR_TOO_LARGE, "%lld x %lld cells exceed 2^31 - 1 trials", (long long)n_rows, (long long)n_cols);
+        return g_eerr.fail(XVEC_ERR_TOO_LARGE, "%lld x %lld cells exceed 2^31 - 1 trials", (long long)n_rows, (long long)n_cols);
     if ((rc = check_costs(c_miss, c_fa, p_target))) return rc;
-    const EvalPlan p = make_plan(n);
-    if (workspace_bytes < p.total)
-        return efail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    const EvalPlan p = make_plan(workspace, n);
+    if ((rc = workspace_ok(workspace_bytes, p.total, g_eerr))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Buffers b = carve(workspace, p);
-    GatherArgs ga = trial_args(scores, ld, n_rows, n_cols, row_class, col_class, nullptr, n, b);
+    GatherArgs ga = trial_args(scores, ld, n_rows, n_cols, row_class, col_class, nullptr, n, p);
     ga.skip_diagonal = skip_diagonal != 0;
-    if ((rc = gather_and_sort(ga, true, p, b, s))) return rc;
-    return sweep(p, b, c_miss, c_fa, p_target, out, s);
+    if ((rc = gather_and_sort(ga, true, p, s))) return rc;
+    return sweep(p, c_miss, c_fa, p_target, out, s);
 }
 
 int xvec_eval_sorted_keys(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
@@ -679,14 +632,13 @@ int xvec_eval_sorted_keys(const double* scores, int64_t ld, int64_t n_rows, int6
     int rc;
     if ((rc = check_trials(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, workspace, workspace_bytes, &p)))
         return rc;
-    if (!keys_out || !bits_out) return efail(XVEC_ERR_ARG, "null pointer: keys_out / bits_out");
+    if (!keys_out || !bits_out) return g_eerr.fail(XVEC_ERR_ARG, "null pointer: keys_out / bits_out");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const Buffers b = carve(workspace, p);
-    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, b), false, p, b, s)))
+    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, p), false, p, s)))
         return rc;
-    hipError_t e = hipMemcpyAsync(keys_out, b.keys[0], (size_t)n_trials * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(bits_out, b.bits[0], (size_t)n_trials, hipMemcpyDeviceToDevice, s);
-    if (e != hipSuccess) return efail(XVEC_ERR_HIP, "copying the sorted pairs failed: %s", hipGetErrorString(e));
+    hipError_t e = hipMemcpyAsync(keys_out, p.keys[0], (size_t)n_trials * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(bits_out, p.bits[0], (size_t)n_trials, hipMemcpyDeviceToDevice, s);
+    if (e != hipSuccess) return g_eerr.fail(XVEC_ERR_HIP, "copying the sorted pairs failed: %s", hipGetErrorString(e));
     return XVEC_OK;
 }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/xvec_hip.h"
+#include "host_support.h"
 #include "xvec_internal.h"
 
 namespace {
@@ -802,11 +803,7 @@ __global__ __launch_bounds__(256, 5) void mfcc512_kernel(const void* __restrict_
 
 }  // namespace fft512
 
-thread_local char g_merr[256] = "";
-int mfail(int code, const char* msg) {
-    snprintf(g_merr, sizeof(g_merr), "%s", msg);
-    return code;
-}
+thread_local xvec::ErrorChannel g_merr;
 
 int round_half_up(double v) { return (int)std::floor(v + 0.5); }   // sigproc.round_half_up for v >= 0
 
@@ -822,21 +819,21 @@ struct xvec_mfcc_plan {
 
 extern "C" {
 
-const char* xvec_mfcc_last_error(void) { return g_merr; }
+const char* xvec_mfcc_last_error(void) { return g_merr.c_str(); }
 
 int xvec_mfcc_create(const xvec_mfcc_cfg* cfg, xvec_mfcc_plan** out) {
-    if (!cfg || !out) return mfail(XVEC_ERR_ARG, "null argument");
+    if (!cfg || !out) return g_merr.fail(XVEC_ERR_ARG, "null argument");
     const int nfft = cfg->nfft;
     int log2n = 0;
     while ((1 << log2n) < nfft) ++log2n;
-    if (nfft < 64 || nfft > kMaxNfft || (1 << log2n) != nfft) return mfail(XVEC_ERR_ARG, "nfft must be a power of two in [64, 4096]");
+    if (nfft < 64 || nfft > kMaxNfft || (1 << log2n) != nfft) return g_merr.fail(XVEC_ERR_ARG, "nfft must be a power of two in [64, 4096]");
     if (cfg->samplerate < 1 || cfg->nfilt < 1 || cfg->nfilt > kThreads || cfg->nfilt > nfft / 2 + 1 ||
         cfg->numcep < 1 || cfg->numcep > cfg->nfilt)
-        return mfail(XVEC_ERR_ARG, "need 1 <= numcep <= nfilt <= min(256, nfft/2+1) and a positive sample rate");
+        return g_merr.fail(XVEC_ERR_ARG, "need 1 <= numcep <= nfilt <= min(256, nfft/2+1) and a positive sample rate");
     const int frame_len = round_half_up((double)cfg->winlen * cfg->samplerate);
     const int frame_step = round_half_up((double)cfg->winstep * cfg->samplerate);
-    if (frame_len < 1 || frame_step < 1) return mfail(XVEC_ERR_ARG, "window length/step too small");
-    if (hipSetDevice(cfg->device) != hipSuccess) return mfail(XVEC_ERR_HIP, "hipSetDevice failed");
+    if (frame_len < 1 || frame_step < 1) return g_merr.fail(XVEC_ERR_ARG, "window length/step too small");
+    if (hipSetDevice(cfg->device) != hipSuccess) return g_merr.fail(XVEC_ERR_HIP, "hipSetDevice failed");
 
     const int nbins = nfft / 2 + 1, nfilt = cfg->nfilt, numcep = cfg->numcep;
     // python_speech_features.base.get_filterbanks, in double
@@ -889,7 +886,7 @@ int xvec_mfcc_create(const xvec_mfcc_cfg* cfg, xvec_mfcc_plan** out) {
         for (int j = 0; j < nfft / 2; ++j) push_w(j, nfft);
 
     xvec_mfcc_plan* p = new (std::nothrow) xvec_mfcc_plan();
-    if (!p) return mfail(XVEC_ERR_STATE, "out of host memory");
+    if (!p) return g_merr.fail(XVEC_ERR_STATE, "out of host memory");
     memset(p, 0, sizeof(*p));
     p->cfg = *cfg;
     // one blob: twiddle | dctl | fb_w | fb_lo | fb_off (ints stored bit-for-bit in the float array)
@@ -1054,12 +1051,12 @@ int xvec_mfcc_create(const xvec_mfcc_cfg* cfg, xvec_mfcc_plan** out) {
     }
     if (hipMalloc(&p->blob, blob.size() * 4) != hipSuccess) {
         delete p;
-        return mfail(XVEC_ERR_HIP, "hipMalloc failed");
+        return g_merr.fail(XVEC_ERR_HIP, "hipMalloc failed");
     }
     if (hipMemcpy(p->blob, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(p->blob);
         delete p;
-        return mfail(XVEC_ERR_HIP, "hipMemcpy failed");
+        return g_merr.fail(XVEC_ERR_HIP, "hipMemcpy failed");
     }
     p->dev.tables = static_cast<const float*>(p->blob);
     p->dev.f_tw1 = p->dev.tables + f_tw1;
@@ -1077,10 +1074,7 @@ int xvec_mfcc_create(const xvec_mfcc_cfg* cfg, xvec_mfcc_plan** out) {
     p->dev.numcep = numcep;
     p->dev.append_energy = cfg->append_energy;
     p->dev.preemph = cfg->preemph;
-    {
-        hipDeviceProp_t prop;
-        p->num_cu = hipGetDeviceProperties(&prop, cfg->device) == hipSuccess ? prop.multiProcessorCount : 256;
-    }
+    p->num_cu = xvec::device_cu_count();     // (cfg->device is the current one: hipSetDevice above)
     *out = p;
     return XVEC_OK;
 }
@@ -1104,8 +1098,8 @@ int32_t xvec_mfcc_frames(const xvec_mfcc_plan* p, int64_t n_samples) {
 
 static int mfcc_run(xvec_mfcc_plan* p, const void* signal, bool i16, float in_scale, int32_t B, int64_t n_samples, float* out,
                     xvec_stream stream) {
-    if (!p || !signal || !out) return mfail(XVEC_ERR_ARG, "null argument");
-    if (B < 1 || B > 65535 || n_samples < 1) return mfail(XVEC_ERR_ARG, "need 1 <= B <= 65535 and n_samples >= 1");
+    if (!p || !signal || !out) return g_merr.fail(XVEC_ERR_ARG, "null argument");
+    if (B < 1 || B > 65535 || n_samples < 1) return g_merr.fail(XVEC_ERR_ARG, "need 1 <= B <= 65535 and n_samples >= 1");
     const int n_frames = xvec_mfcc_frames(p, n_samples);
     const int64_t total_frames = (int64_t)B * n_frames;
     MfccDev dv = p->dev;
@@ -1122,22 +1116,20 @@ static int mfcc_run(xvec_mfcc_plan* p, const void* signal, bool i16, float in_sc
         else if (i16) fft512::mfcc512_kernel<true, false><<<grid, 256, 0, hs>>>(signal, n_samples, n_frames, total_frames, n_tiles, dv, out);
         else if (band) fft512::mfcc512_kernel<false, true><<<grid, 256, 0, hs>>>(signal, n_samples, n_frames, total_frames, n_tiles, dv, out);
         else fft512::mfcc512_kernel<false, false><<<grid, 256, 0, hs>>>(signal, n_samples, n_frames, total_frames, n_tiles, dv, out);
-        if (hipGetLastError() != hipSuccess) return mfail(XVEC_ERR_HIP, "mfcc kernel launch failed");
-        return XVEC_OK;
+        return g_merr.launch_ok("mfcc kernel");
     }
     const int per_wave = wave_floats(p->dev.nfft, p->dev.nbins);
     const size_t lds = ((size_t)per_wave * kWavesPerBlock + p->dev.table_floats) * 4;
     if (lds > 64 * 1024) {   // nfft 4096: opt in to the larger dynamic LDS once
         static xvec::LdsOptIn opt;
         if (opt.ensure(reinterpret_cast<const void*>(mfcc_kernel<0>), 160 * 1024) != hipSuccess)
-            return mfail(XVEC_ERR_HIP, "hipFuncSetAttribute failed");
+            return g_merr.fail(XVEC_ERR_HIP, "hipFuncSetAttribute failed");
     }
     const int grid_x = (n_frames + 2 * kWavesPerBlock - 1) / (2 * kWavesPerBlock);
     const dim3 grid(grid_x, B);
     if (p->dev.log2n == 9) mfcc_kernel<9><<<grid, kThreads, lds, hs>>>(signal, i16 ? 1 : 0, n_samples, n_frames, dv, out);
     else mfcc_kernel<0><<<grid, kThreads, lds, hs>>>(signal, i16 ? 1 : 0, n_samples, n_frames, dv, out);
-    if (hipGetLastError() != hipSuccess) return mfail(XVEC_ERR_HIP, "mfcc kernel launch failed");
-    return XVEC_OK;
+    return g_merr.launch_ok("mfcc kernel");
 }
 
 int xvec_mfcc(xvec_mfcc_plan* p, const float* signal, int32_t B, int64_t n_samples, float* out, xvec_stream stream) {

@@ -5,12 +5,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../include/xvec_hip.h"
 #include "../../include/xvec_plda.h"
 #include "../../include/xvec_score.h"
+#include "host_support.h"
 #include "tdnn_common.h"
 
 namespace xvec {
@@ -280,31 +280,17 @@ __global__ __launch_bounds__(256) void plda_em_scale_kernel(const double* __rest
 
 // ---------------------------------------------------------------- host side
 
-thread_local char g_perr[384] = "";
-
-int pfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_perr, sizeof(g_perr), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int plaunch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return pfail(XVEC_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return XVEC_OK;
-}
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+thread_local ErrorChannel g_perr;
 
 struct StatsPlan {
     int tiles, n_tri, slices;
     int64_t rows_per_slice;
-    size_t off_cstart, off_slab, total;
+    int64_t* cstart;      // device copy of class_start
+    double* slab;         // scatter partials, one kTS x kTS tile per (slice, triangle tile)
+    size_t total;
 };
 
-StatsPlan make_stats_plan(int64_t n, int dim, int n_classes) {
+StatsPlan make_stats_plan(void* ws, int64_t n, int dim, int n_classes) {
     StatsPlan p{};
     p.tiles = (dim + kTS - 1) / kTS;
     p.n_tri = p.tiles * (p.tiles + 1) / 2;
@@ -312,10 +298,32 @@ StatsPlan make_stats_plan(int64_t n, int dim, int n_classes) {
     const int64_t by_rows = std::max<int64_t>(1, (n + 255) / 256);         // at least 256 rows a slice
     p.slices = (int)std::min(by_blocks, by_rows);
     p.rows_per_slice = ((n + p.slices - 1) / p.slices + kKC - 1) / kKC * kKC;
-    p.off_cstart = 0;
-    p.off_slab = align256((size_t)(n_classes + 1) * sizeof(int64_t));
-    p.total = p.off_slab + align256((size_t)p.slices * p.n_tri * kTS * kTS * sizeof(double));
+    Carver c(ws);
+    p.cstart = c.take<int64_t>((size_t)n_classes + 1);
+    p.slab = c.take<double>((size_t)p.slices * p.n_tri * kTS * kTS);
+    p.total = c.total();
     return p;
+}
+
+struct EmPlan {
+    double *yt, *hh;      // Y^T [rank, C];  [H^T ; (n H)^T] [2 rank, C]
+    size_t total;
+};
+
+EmPlan make_em_plan(void* ws, int n_classes, int rank) {
+    EmPlan p{};
+    Carver c(ws);
+    p.yt = c.take<double>((size_t)rank * n_classes);
+    p.hh = c.take<double>((size_t)2 * rank * n_classes);
+    p.total = c.total();
+    return p;
+}
+
+// one product through the public scorer entry; its message moves into this module's channel
+int product(const char* what, const double* A, int64_t lda, const double* B, int64_t ldb, int64_t M, int64_t N, int K, double* C,
+            int64_t ldc, xvec_stream stream) {
+    const int rc = xvec_gemm_nt_f64(A, lda, B, ldb, M, N, K, nullptr, nullptr, 0.0, 1.0, C, ldc, stream);
+    return rc ? g_perr.fail(rc, "%s: %s", what, xvec_score_last_error()) : XVEC_OK;
 }
 
 bool stats_args_ok(int64_t n, int dim, int n_classes) {
@@ -329,11 +337,11 @@ using namespace xvec;
 
 extern "C" {
 
-const char* xvec_plda_last_error(void) { return g_perr; }
+const char* xvec_plda_last_error(void) { return g_perr.c_str(); }
 
 size_t xvec_plda_stats_workspace_bytes(int64_t n, int32_t dim, int32_t n_classes) {
     if (!stats_args_ok(n, dim, n_classes)) return 0;
-    return make_stats_plan(n, dim, n_classes).total;
+    return make_stats_plan(nullptr, n, dim, n_classes).total;
 }
 
 // Launches: class sums (one block per class), mean, centring (+ transpose), scatter partials, scatter reduce.
@@ -341,47 +349,43 @@ int xvec_plda_stats(const void* x, int32_t x_dtype, int64_t n, int32_t dim, cons
                     const int64_t* class_start_host, int32_t n_classes, double scaling_factor, double* mean,
                     double* counts, double* class_sums, double* class_sums_t, double* sigma_obs, void* workspace,
                     size_t workspace_bytes, xvec_stream stream) {
-    if (n < 2) return pfail(XVEC_ERR_ARG, "need at least two training vectors (n = %lld)", (long long)n);
-    if (n > 0x7fffffff) return pfail(XVEC_ERR_TOO_LARGE, "n = %lld: row indices are int32", (long long)n);
-    if (dim < 1 || n_classes < 1) return pfail(XVEC_ERR_ARG, "dim = %d and n_classes = %d must be >= 1", dim, n_classes);
-    if (n_classes > n) return pfail(XVEC_ERR_ARG, "more classes (%d) than vectors (%lld)", n_classes, (long long)n);
-    if (x_dtype != XVEC_PLDA_X_F32 && x_dtype != XVEC_PLDA_X_F64) return pfail(XVEC_ERR_ARG, "x_dtype %d unknown", x_dtype);
+    if (n < 2) return g_perr.fail(XVEC_ERR_ARG, "need at least two training vectors (n = %lld)", (long long)n);
+    if (n > 0x7fffffff) return g_perr.fail(XVEC_ERR_TOO_LARGE, "n = %lld: row indices are int32", (long long)n);
+    if (dim < 1 || n_classes < 1) return g_perr.fail(XVEC_ERR_ARG, "dim = %d and n_classes = %d must be >= 1", dim, n_classes);
+    if (n_classes > n) return g_perr.fail(XVEC_ERR_ARG, "more classes (%d) than vectors (%lld)", n_classes, (long long)n);
+    if (x_dtype != XVEC_PLDA_X_F32 && x_dtype != XVEC_PLDA_X_F64) return g_perr.fail(XVEC_ERR_ARG, "x_dtype %d unknown", x_dtype);
     if (!x || !order || !class_start_host || !mean || !counts || !class_sums || !sigma_obs || !workspace)
-        return pfail(XVEC_ERR_ARG, "null pointer");
+        return g_perr.fail(XVEC_ERR_ARG, "null pointer");
     if (class_start_host[0] != 0 || class_start_host[n_classes] != n)
-        return pfail(XVEC_ERR_ARG, "class_start must run from 0 to n = %lld (got %lld .. %lld)", (long long)n,
-                     (long long)class_start_host[0], (long long)class_start_host[n_classes]);
+        return g_perr.fail(XVEC_ERR_ARG, "class_start must run from 0 to n = %lld (got %lld .. %lld)", (long long)n,
+                           (long long)class_start_host[0], (long long)class_start_host[n_classes]);
     for (int c = 0; c < n_classes; ++c)
         if (class_start_host[c + 1] < class_start_host[c])
-            return pfail(XVEC_ERR_ARG, "class_start decreases at class %d", c);
-    const StatsPlan p = make_stats_plan(n, dim, n_classes);
-    if (workspace_bytes < p.total)
-        return pfail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    char* ws = static_cast<char*>(workspace);
-    int64_t* cstart = reinterpret_cast<int64_t*>(ws + p.off_cstart);
-    double* slab = reinterpret_cast<double*>(ws + p.off_slab);
-    hipError_t e = hipMemcpyAsync(cstart, class_start_host, (size_t)(n_classes + 1) * sizeof(int64_t),
-                                  hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return pfail(XVEC_ERR_HIP, "class_start copy failed: %s", hipGetErrorString(e));
+            return g_perr.fail(XVEC_ERR_ARG, "class_start decreases at class %d", c);
+    const StatsPlan p = make_stats_plan(workspace, n, dim, n_classes);
     int rc;
+    if ((rc = workspace_ok(workspace_bytes, p.total, g_perr))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    hipError_t e = hipMemcpyAsync(p.cstart, class_start_host, (size_t)(n_classes + 1) * sizeof(int64_t),
+                                  hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return g_perr.fail(XVEC_ERR_HIP, "class_start copy failed: %s", hipGetErrorString(e));
     if (x_dtype == XVEC_PLDA_X_F32)
-        plda_class_sum_kernel<float><<<n_classes, 256, 0, s>>>(static_cast<const float*>(x), n, dim, order, cstart,
+        plda_class_sum_kernel<float><<<n_classes, 256, 0, s>>>(static_cast<const float*>(x), n, dim, order, p.cstart,
                                                                 scaling_factor, class_sums, counts);
     else
-        plda_class_sum_kernel<double><<<n_classes, 256, 0, s>>>(static_cast<const double*>(x), n, dim, order, cstart,
+        plda_class_sum_kernel<double><<<n_classes, 256, 0, s>>>(static_cast<const double*>(x), n, dim, order, p.cstart,
                                                                  scaling_factor, class_sums, counts);
-    if ((rc = plaunch("plda_class_sum_kernel"))) return rc;
+    if ((rc = g_perr.launch_ok("plda_class_sum_kernel"))) return rc;
     plda_mean_kernel<<<(dim + kMeanCols - 1) / kMeanCols, 256, 0, s>>>(class_sums, n_classes, dim, n, mean);
-    if ((rc = plaunch("plda_mean_kernel"))) return rc;
+    if ((rc = g_perr.launch_ok("plda_mean_kernel"))) return rc;
     const int64_t cd = (int64_t)n_classes * dim;
     plda_centre_kernel<<<(unsigned)((cd + 255) / 256), 256, 0, s>>>(class_sums, class_sums_t, counts, mean, n_classes, dim,
                                                                    scaling_factor);
-    if ((rc = plaunch("plda_centre_kernel"))) return rc;
+    if ((rc = g_perr.launch_ok("plda_centre_kernel"))) return rc;
     ScatterArgs g{};
     g.x = x;
     g.mean = mean;
-    g.slab = slab;
+    g.slab = p.slab;
     g.n = n;
     g.rows_per_slice = p.rows_per_slice;
     g.dim = dim;
@@ -396,15 +400,15 @@ int xvec_plda_stats(const void* x, int32_t x_dtype, int64_t n, int32_t dim, cons
         if (vec) plda_scatter_kernel<double, true><<<grid, 256, 0, s>>>(g);
         else plda_scatter_kernel<double, false><<<grid, 256, 0, s>>>(g);
     }
-    if ((rc = plaunch("plda_scatter_kernel"))) return rc;
-    plda_scatter_reduce_kernel<<<dim3((dim + 255) / 256, dim), 256, 0, s>>>(slab, p.slices, p.n_tri, p.tiles, dim, n,
+    if ((rc = g_perr.launch_ok("plda_scatter_kernel"))) return rc;
+    plda_scatter_reduce_kernel<<<dim3((dim + 255) / 256, dim), 256, 0, s>>>(p.slab, p.slices, p.n_tri, p.tiles, dim, n,
                                                                            sigma_obs);
-    return plaunch("plda_scatter_reduce_kernel");
+    return g_perr.launch_ok("plda_scatter_reduce_kernel");
 }
 
 size_t xvec_plda_em_workspace_bytes(int32_t n_classes, int32_t rank) {
     if (n_classes < 1 || rank < 1) return 0;
-    return align256((size_t)rank * n_classes * sizeof(double)) + align256((size_t)2 * rank * n_classes * sizeof(double));
+    return make_em_plan(nullptr, n_classes, rank).total;
 }
 
 // Launches: Y^T = pq_t S^T (xvec_gemm_nt_f64), the scaling into [H^T ; (n H)^T], then [H^T H | H^T diag(n) H] and H^T S
@@ -413,28 +417,21 @@ int xvec_plda_em_products(const double* pq_t, const double* class_sums, const do
                           const double* counts, const double* lam, int32_t n_classes, int32_t dim, int32_t rank,
                           double* out, void* workspace, size_t workspace_bytes, xvec_stream stream) {
     if (n_classes < 1 || dim < 1 || rank < 1)
-        return pfail(XVEC_ERR_ARG, "n_classes = %d, dim = %d and rank = %d must be >= 1", n_classes, dim, rank);
-    if (rank > dim) return pfail(XVEC_ERR_ARG, "rank_f = %d exceeds dim = %d", rank, dim);
+        return g_perr.fail(XVEC_ERR_ARG, "n_classes = %d, dim = %d and rank = %d must be >= 1", n_classes, dim, rank);
+    if (rank > dim) return g_perr.fail(XVEC_ERR_ARG, "rank_f = %d exceeds dim = %d", rank, dim);
     if (!pq_t || !class_sums || !class_sums_t || !counts || !lam || !out || !workspace)
-        return pfail(XVEC_ERR_ARG, "null pointer");
-    const size_t need = xvec_plda_em_workspace_bytes(n_classes, rank);
-    if (workspace_bytes < need) return pfail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    double* yt = static_cast<double*>(workspace);
-    double* hh = reinterpret_cast<double*>(static_cast<char*>(workspace) + align256((size_t)rank * n_classes * sizeof(double)));
-    const int64_t C = n_classes, R = rank, ldo = 2 * R + dim;
+        return g_perr.fail(XVEC_ERR_ARG, "null pointer");
+    const EmPlan p = make_em_plan(workspace, n_classes, rank);
     int rc;
-    if ((rc = xvec_gemm_nt_f64(pq_t, dim, class_sums, dim, R, C, dim, nullptr, nullptr, 0.0, 1.0, yt, C, stream)))
-        return pfail(rc, "Y product: %s", xvec_score_last_error());
+    if ((rc = workspace_ok(workspace_bytes, p.total, g_perr))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int64_t C = n_classes, R = rank, ldo = 2 * R + dim;
+    if ((rc = product("Y product", pq_t, dim, class_sums, dim, R, C, dim, p.yt, C, stream))) return rc;
     const int64_t rc_total = R * C;
-    plda_em_scale_kernel<<<(unsigned)((rc_total + 255) / 256), 256, 0, s>>>(yt, counts, lam, rank, n_classes, hh);
-    if ((rc = plaunch("plda_em_scale_kernel"))) return rc;
-    if ((rc = xvec_gemm_nt_f64(hh, C, hh, C, R, 2 * R, n_classes, nullptr, nullptr, 0.0, 1.0, out, ldo, stream)))
-        return pfail(rc, "H products: %s", xvec_score_last_error());
-    if ((rc = xvec_gemm_nt_f64(hh, C, class_sums_t, C, R, dim, n_classes, nullptr, nullptr, 0.0, 1.0, out + 2 * R, ldo,
-                               stream)))
-        return pfail(rc, "H^T S product: %s", xvec_score_last_error());
-    return XVEC_OK;
+    plda_em_scale_kernel<<<(unsigned)((rc_total + 255) / 256), 256, 0, s>>>(p.yt, counts, lam, rank, n_classes, p.hh);
+    if ((rc = g_perr.launch_ok("plda_em_scale_kernel"))) return rc;
+    if ((rc = product("H products", p.hh, C, p.hh, C, R, 2 * R, n_classes, out, ldo, stream))) return rc;
+    return product("H^T S product", p.hh, C, class_sums_t, C, R, dim, n_classes, out + 2 * R, ldo, stream);
 }
 
 }  // extern "C"

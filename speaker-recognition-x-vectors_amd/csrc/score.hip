@@ -5,11 +5,11 @@
 #include <cstdlib>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 
 #include "../../include/xvec_hip.h"
 #include "../../include/xvec_score.h"
+#include "host_support.h"
 #include "tdnn_common.h"
 
 namespace xvec {
@@ -346,21 +346,7 @@ __global__ void normalize_rows_kernel(const double* __restrict__ x, int64_t n, i
     for (int d = lane; d < dim; d += 64) out[row * dim + d] = x[row * dim + d] * inv;
 }
 
-thread_local char g_serr[384] = "";
-
-int sfail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_serr, sizeof(g_serr), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-int check_launch(const char* what) {
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sfail(XVEC_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
-    return XVEC_OK;
-}
+thread_local ErrorChannel g_serr;
 
 // the scorers' fused forms of one product (see GemmArgs)
 struct GemmExtra {
@@ -380,17 +366,9 @@ int gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t 
             const double* rowv, const double* colv, double cst, double scale, double* C, int64_t ldc, hipStream_t s,
             const GemmExtra* ex = nullptr) {
     if (M == 0 || N == 0) return XVEC_OK;
-    static int num_cu_cache[64] = {};          // per device: two persistent blocks per CU
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return sfail(XVEC_ERR_HIP, "hipGetDevice failed");
-    int num_cu = (dev >= 0 && dev < 64) ? num_cu_cache[dev] : 0;
-    if (num_cu == 0) {
-        hipDeviceProp_t prop;
-        num_cu = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        if (dev >= 0 && dev < 64) num_cu_cache[dev] = num_cu;
-    }
+    const int num_cu = device_cu_count();      // two persistent blocks per CU
     const bool sym = ex && ex->sym, pre = ex && ex->pre;
-    if (sym && M != N) return sfail(XVEC_ERR_ARG, "symmetric walk needs a square score matrix");
+    if (sym && M != N) return g_serr.fail(XVEC_ERR_ARG, "symmetric walk needs a square score matrix");
     // Two tilings (a symmetric walk visits only the tiles on or above the diagonal):
     //   128 x 128, two blocks per CU (255 registers);  64 x 64, FOUR blocks per CU (121 registers, 32 KiB of LDS each).
     // Per CU the two finish the same work in the same time within a few per cent (a round of four 64 x 64 tiles against a round
@@ -411,7 +389,7 @@ int gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t 
     const int ts = small ? 64 : 128;
     const int64_t tm = (M + ts - 1) / ts, tn = (N + ts - 1) / ts;
     const int64_t n_tiles = count(ts);
-    if (n_tiles > 0x7fffffff) return sfail(XVEC_ERR_ARG, "score matrix too large for one launch");
+    if (n_tiles > 0x7fffffff) return g_serr.fail(XVEC_ERR_ARG, "score matrix too large for one launch");
     GemmArgs g{};
     g.A = A; g.B = B; g.rowv = rowv; g.colv = colv; g.C = C;
     g.lda = lda; g.ldb = ldb; g.ldc = ldc; g.M = M; g.N = N;
@@ -425,7 +403,7 @@ int gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t 
         if (pre && g.dot_out) {
             const int wcols = ts / 2;                       // columns of one wave: 16 WT
             const int parts = (int)((N + wcols - 1) / wcols - g.dot_col0 / wcols);
-            if (parts > g.dot_ld) return sfail(XVEC_ERR_ARG, "row-dot partials do not fit their rows");
+            if (parts > g.dot_ld) return g_serr.fail(XVEC_ERR_ARG, "row-dot partials do not fit their rows");
             if (ex->parts_out) *ex->parts_out = parts;
         }
     }
@@ -437,16 +415,14 @@ int gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t 
     {                                                                                                                     \
         static LdsOptIn opt;                                                                                              \
         const hipError_t ea = opt.ensure(reinterpret_cast<const void*>(&gemm_nt_f64_kernel<VEC_, WT_, PRE_>), (int)lds);  \
-        if (ea != hipSuccess) return sfail(XVEC_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));        \
+        if (ea != hipSuccess) return g_serr.fail(XVEC_ERR_HIP, "hipFuncSetAttribute failed: %s", hipGetErrorString(ea));  \
         gemm_nt_f64_kernel<VEC_, WT_, PRE_><<<grid, 256, lds, s>>>(g);                                                    \
     }
     if (vec) { if (pre) SCORE_LAUNCH(true, 2, true) else if (small) SCORE_LAUNCH(true, 2, false) else SCORE_LAUNCH(true, 4, false) }
     else { if (pre) SCORE_LAUNCH(false, 2, true) else if (small) SCORE_LAUNCH(false, 2, false) else SCORE_LAUNCH(false, 4, false) }
 #undef SCORE_LAUNCH
-    return check_launch("gemm_nt_f64_kernel");
+    return g_serr.launch_ok("gemm_nt_f64_kernel");
 }
-
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 struct ScorePlan {
     double *ec, *tc, *uv, *w, *mp, *sp;
@@ -455,20 +431,14 @@ struct ScorePlan {
 
 ScorePlan make_score_plan(void* ws, int64_t ne, int64_t nt, int dim) {
     ScorePlan p{};
-    char* base = static_cast<char*>(ws);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        double* ptr = reinterpret_cast<double*>(base + off);
-        off += align256(bytes);
-        return ptr;
-    };
-    p.ec = take((size_t)ne * dim * 8);        // centred (PLDA) / normalised (cosine) enrol vectors
-    p.tc = take((size_t)nt * dim * 8);        // ... test vectors
-    p.uv = take((size_t)ne * 2 * dim * 8);    // rows of [ e Psi | the row's model_part partials (e Phi itself is never written) ]
-    p.w = take((size_t)nt * dim * 8);         // rows of the test vectors' seg_part partials (t Phi is never written)
-    p.mp = take((size_t)ne * 8);              // (unused since round 6; kept so that the workspace size does not change)
-    p.sp = take((size_t)nt * 8);
-    p.total = off;
+    Carver c(ws);
+    p.ec = c.take<double>((size_t)ne * dim);        // centred (PLDA) / normalised (cosine) enrol vectors
+    p.tc = c.take<double>((size_t)nt * dim);        // ... test vectors
+    p.uv = c.take<double>((size_t)ne * 2 * dim);    // rows of [ e Psi | the row's model_part partials (e Phi itself is never written) ]
+    p.w = c.take<double>((size_t)nt * dim);         // rows of the test vectors' seg_part partials (t Phi is never written)
+    p.mp = c.take<double>((size_t)ne);              // (unused since round 6; kept so that the workspace size does not change)
+    p.sp = c.take<double>((size_t)nt);
+    p.total = c.total();
     return p;
 }
 
@@ -479,14 +449,14 @@ using namespace xvec;
 
 extern "C" {
 
-const char* xvec_score_last_error(void) { return g_serr; }
+const char* xvec_score_last_error(void) { return g_serr.c_str(); }
 
 int xvec_gemm_nt_f64(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t M, int64_t N, int32_t K,
                      const double* rowv, const double* colv, double cst, double scale, double* C, int64_t ldc,
                      xvec_stream stream) {
-    if (M < 0 || N < 0 || K < 1) return sfail(XVEC_ERR_ARG, "bad GEMM shape M=%lld N=%lld K=%d", (long long)M, (long long)N, K);
-    if ((M && !A) || (N && !B) || (M && N && !C)) return sfail(XVEC_ERR_ARG, "null matrix pointer");
-    if (lda < K || ldb < K || ldc < N) return sfail(XVEC_ERR_ARG, "row stride smaller than the row");
+    if (M < 0 || N < 0 || K < 1) return g_serr.fail(XVEC_ERR_ARG, "bad GEMM shape M=%lld N=%lld K=%d", (long long)M, (long long)N, K);
+    if ((M && !A) || (N && !B) || (M && N && !C)) return g_serr.fail(XVEC_ERR_ARG, "null matrix pointer");
+    if (lda < K || ldb < K || ldc < N) return g_serr.fail(XVEC_ERR_ARG, "row stride smaller than the row");
     return gemm_nt(A, lda, B, ldb, M, N, K, rowv, colv, cst, scale, C, ldc, static_cast<hipStream_t>(stream));
 }
 
@@ -510,11 +480,10 @@ int xvec_plda_score(const double* enroll, int64_t n_enroll, const double* test, 
                     xvec_stream stream) {
     const bool self = (test == nullptr);
     if (self) n_test = n_enroll;
-    if (n_enroll < 1 || n_test < 1 || dim < 1) return sfail(XVEC_ERR_ARG, "empty enrol/test set or dim < 1");
-    if (!enroll || !mean || !psi_t || !phi_t || !scores || !workspace) return sfail(XVEC_ERR_ARG, "null pointer");
+    if (n_enroll < 1 || n_test < 1 || dim < 1) return g_serr.fail(XVEC_ERR_ARG, "empty enrol/test set or dim < 1");
+    if (!enroll || !mean || !psi_t || !phi_t || !scores || !workspace) return g_serr.fail(XVEC_ERR_ARG, "null pointer");
     const ScorePlan p = make_score_plan(workspace, n_enroll, self ? 0 : n_test, dim);
-    if (workspace_bytes < p.total)
-        return sfail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    if (int rc = workspace_ok(workspace_bytes, p.total, g_serr)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc;
     int parts_e = 0, parts_t = 0;
@@ -581,11 +550,10 @@ int xvec_plda_score_lowrank(const double* enroll, int64_t n_enroll, const double
     const bool self = (test == nullptr);
     if (self) n_test = n_enroll;
     if (n_enroll < 1 || n_test < 1 || dim < 1 || rank < 1 || rank > dim)
-        return sfail(XVEC_ERR_ARG, "empty enrol/test set, dim < 1 or rank outside [1, dim]");
-    if (!enroll || !mean || !l_t || !wz_t || !scores || !workspace) return sfail(XVEC_ERR_ARG, "null pointer");
+        return g_serr.fail(XVEC_ERR_ARG, "empty enrol/test set, dim < 1 or rank outside [1, dim]");
+    if (!enroll || !mean || !l_t || !wz_t || !scores || !workspace) return g_serr.fail(XVEC_ERR_ARG, "null pointer");
     const ScorePlan p = make_score_plan(workspace, n_enroll, self ? 0 : n_test, dim);
-    if (workspace_bytes < p.total)
-        return sfail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    if (int rc = workspace_ok(workspace_bytes, p.total, g_serr)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int64_t R = rank;
     int rc;
@@ -634,19 +602,18 @@ int xvec_cosine_score(const double* enroll, int64_t n_enroll, const double* test
                       double* scores, void* workspace, size_t workspace_bytes, xvec_stream stream) {
     const bool self = (test == nullptr);
     if (self) n_test = n_enroll;
-    if (n_enroll < 1 || n_test < 1 || dim < 1) return sfail(XVEC_ERR_ARG, "empty enrol/test set or dim < 1");
-    if (!enroll || !scores || !workspace) return sfail(XVEC_ERR_ARG, "null pointer");
+    if (n_enroll < 1 || n_test < 1 || dim < 1) return g_serr.fail(XVEC_ERR_ARG, "empty enrol/test set or dim < 1");
+    if (!enroll || !scores || !workspace) return g_serr.fail(XVEC_ERR_ARG, "null pointer");
     const ScorePlan p = make_score_plan(workspace, n_enroll, self ? 0 : n_test, dim);
-    if (workspace_bytes < p.total)
-        return sfail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, p.total);
+    if (int rc = workspace_ok(workspace_bytes, p.total, g_serr)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     int rc;
     normalize_rows_kernel<<<(unsigned)((n_enroll + 3) / 4), 256, 0, s>>>(enroll, n_enroll, dim, p.ec);
-    if ((rc = check_launch("normalize_rows_kernel"))) return rc;
+    if ((rc = g_serr.launch_ok("normalize_rows_kernel"))) return rc;
     const double* tc = p.ec;
     if (!self) {
         normalize_rows_kernel<<<(unsigned)((n_test + 3) / 4), 256, 0, s>>>(test, n_test, dim, p.tc);
-        if ((rc = check_launch("normalize_rows_kernel"))) return rc;
+        if ((rc = g_serr.launch_ok("normalize_rows_kernel"))) return rc;
         tc = p.tc;
     }
     GemmExtra ex;

@@ -3,13 +3,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 
 #include "../../include/xvec_hip.h"
+#include "host_support.h"
 #include "tdnn_common.h"   // wino_pair_count
 #include "xvec_internal.h"
 
@@ -17,22 +17,14 @@ using namespace xvec;
 
 namespace {
 
-thread_local char g_err[512] = "";
-
-int fail(int code, const char* fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
+thread_local ErrorChannel g_err;
 
 #define HIP_TRY(expr)                                                                         \
     do {                                                                                      \
         hipError_t e_ = (expr);                                                               \
         if (e_ != hipSuccess)                                                                 \
-            return fail(XVEC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),  \
-                        __FILE__, __LINE__);                                                  \
+            return g_err.fail(XVEC_ERR_HIP, "%s failed: %s (%s:%d)", #expr,                   \
+                              hipGetErrorString(e_), __FILE__, __LINE__);                     \
     } while (0)
 
 // reference main.py:38-44
@@ -150,7 +142,6 @@ struct Plan {
     int64_t part_slots;
 };
 
-size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
 Plan make_plan(const xvec_handle* h, int64_t total, int B) {
     Plan p;
@@ -159,19 +150,19 @@ Plan make_plan(const xvec_handle* h, int64_t total, int B) {
     p.rows_alloc = p.m_pad + kRowPadTail;
     const int nh = h->geo[0].n_pad, n5 = h->geo[4].n_pad;
     size_t o = 0;
-    p.xpad = o;   o += align_up((size_t)p.rows_alloc * h->cin_pad * 4);
-    p.x16 = o;    o += align_up((size_t)p.rows_alloc * h->cin_pad * 2 * 2);   // bf16 rows; bf16x3: hi and lo planes
-    p.actA = o;   o += align_up((size_t)p.rows_alloc * nh * 4);
-    p.actB = o;   o += align_up((size_t)p.rows_alloc * nh * 4);
-    p.act5 = o;   o += align_up((size_t)p.rows_alloc * (n5 > nh ? n5 : nh) * 4);   // also the fp32 output of xvec_tdnn_layer
+    p.xpad = o;   o += align256((size_t)p.rows_alloc * h->cin_pad * 4);
+    p.x16 = o;    o += align256((size_t)p.rows_alloc * h->cin_pad * 2 * 2);   // bf16 rows; bf16x3: hi and lo planes
+    p.actA = o;   o += align256((size_t)p.rows_alloc * nh * 4);
+    p.actB = o;   o += align256((size_t)p.rows_alloc * nh * 4);
+    p.act5 = o;   o += align256((size_t)p.rows_alloc * (n5 > nh ? n5 : nh) * 4);   // also the fp32 output of xvec_tdnn_layer
     // pooling partials: one per (32-row group, utterance) -- or, tdnn_pp16.hip, two per (block of a column, utterance)
     p.part_slots = std::max<int64_t>(p.m_pad / 32 + B + 1, 2 * ((int64_t)h->num_cu + B) + 2);
-    p.part = o;   o += align_up((size_t)p.part_slots * 3 * n5 * 4);   // (addressed with 32-bit offsets: plan_layer checks < 2 GiB)
-    p.part_cnt = o; o += align_up((size_t)2 * (h->num_cu + B + 2) * 4);     // tdnn_pp16.hip: frames behind each segment partial
-    p.pooled = o; o += align_up((size_t)B * 2 * XVEC_POOL_CHANNELS * 4);
-    p.seg6 = o;   o += align_up((size_t)B * h->cfg.x_vector_size * 4);
-    p.seg7 = o;   o += align_up((size_t)B * h->cfg.x_vector_size * 4);
-    p.offs = o;   o += align_up((size_t)(B + 1) * 8);
+    p.part = o;   o += align256((size_t)p.part_slots * 3 * n5 * 4);   // (addressed with 32-bit offsets: plan_layer checks < 2 GiB)
+    p.part_cnt = o; o += align256((size_t)2 * (h->num_cu + B + 2) * 4);     // tdnn_pp16.hip: frames behind each segment partial
+    p.pooled = o; o += align256((size_t)B * 2 * XVEC_POOL_CHANNELS * 4);
+    p.seg6 = o;   o += align256((size_t)B * h->cfg.x_vector_size * 4);
+    p.seg7 = o;   o += align256((size_t)B * h->cfg.x_vector_size * 4);
+    p.offs = o;   o += align256((size_t)(B + 1) * 8);
     p.bytes = o;
     return p;
 }
@@ -364,7 +355,7 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
         if (!x3) a.Wf = h->Wp16b;
     } else if (x3 && c.mode.src == Src::kRows32) {
         // no other kernel reads bf16x3 layer 1 from fp32 rows: the 128x128 kernel reads their hi / lo split
-        if (!c.X16) return fail(XVEC_ERR_STATE, "internal: bf16x3 layer 1 from fp32 rows needs the streaming kernel's shapes");
+        if (!c.X16) return g_err.fail(XVEC_ERR_STATE, "internal: bf16x3 layer 1 from fp32 rows needs the streaming kernel's shapes");
         lp.mode.src = Src::kRows16;
         a.X = c.X16;
     } else if (!bf && from_act && h->pol.split3 && h->Wp3[l] && c.rows_out >= (int64_t)h->pol.split3_min_rows * h->num_cu) {
@@ -406,15 +397,15 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
     // (rows of a tile + look-ahead + u*span re-basing) * row bytes (+ the lo plane)
     const int64_t es = (bf && !rows32) ? 2 : 4;   // element size of the rows READ
     if (((int64_t)c.map.n_utts * a.span + kRowPadTail) * c.ldx * es + x_plane > 0x7fffffff)
-        return fail(XVEC_ERR_TOO_LARGE, "layer %d: %d utterances x %d channels exceed 32-bit row offsets; split the batch",
-                    l, c.map.n_utts, c.ldx);
+        return g_err.fail(XVEC_ERR_TOO_LARGE, "layer %d: %d utterances x %d channels exceed 32-bit row offsets; split the batch",
+                          l, c.map.n_utts, c.ldx);
     if (x3 && (x_plane > 0x3fffffff || c.y_plane > 0x3fffffff))
-        return fail(XVEC_ERR_TOO_LARGE, "batch too large for bf16x3 (plane offsets must fit 30 bits); split it");
+        return g_err.fail(XVEC_ERR_TOO_LARGE, "batch too large for bf16x3 (plane offsets must fit 30 bits); split it");
     // pooling partials of the 128x128 kernels: one slot per (32-row group, utterance), addressed with 32-bit offsets
     // (tdnn_pp16.hip's segment partials take a 64-bit base per slot and have no such limit)
     if (pool && lp.launch != Launch::kPp16 &&
         (size_t)((c.rows_out + 31) / 32 + c.map.n_utts + 1) * 3 * g.n_pad * 4 > 0x7fffffffull)
-        return fail(XVEC_ERR_TOO_LARGE, "batch too large: pooling partials exceed 2 GiB; split it");
+        return g_err.fail(XVEC_ERR_TOO_LARGE, "batch too large: pooling partials exceed 2 GiB; split it");
     return XVEC_OK;
 }
 
@@ -464,14 +455,14 @@ int refold(xvec_handle* h, int layer, hipStream_t s) {
 
 int check_loaded(const xvec_handle* h, int mode) {
     for (int i = 0; i < XVEC_NUM_TDNN; ++i)
-        if (!h->tdnn_loaded[i]) return fail(XVEC_ERR_STATE, "time_context_layers.%d weights not loaded", i);
+        if (!h->tdnn_loaded[i]) return g_err.fail(XVEC_ERR_STATE, "time_context_layers.%d weights not loaded", i);
     for (int i = 0; i < XVEC_NUM_TDNN; ++i)
-        if (!h->folded[i]) return fail(XVEC_ERR_STATE, "internal: time_context_layers.%d not folded", i);
+        if (!h->folded[i]) return g_err.fail(XVEC_ERR_STATE, "internal: time_context_layers.%d not folded", i);
     if (mode == XVEC_MODE_POOLED) return XVEC_OK;
-    if (!h->aff_loaded[0]) return fail(XVEC_ERR_STATE, "segment_layer6 weights not loaded");
+    if (!h->aff_loaded[0]) return g_err.fail(XVEC_ERR_STATE, "segment_layer6 weights not loaded");
     if ((mode == XVEC_MODE_XVEC7 || mode == XVEC_MODE_LOGITS) && !h->aff_loaded[1])
-        return fail(XVEC_ERR_STATE, "segment_layer7 weights not loaded");
-    if (mode == XVEC_MODE_LOGITS && !h->aff_loaded[2]) return fail(XVEC_ERR_STATE, "output weights not loaded");
+        return g_err.fail(XVEC_ERR_STATE, "segment_layer7 weights not loaded");
+    if (mode == XVEC_MODE_LOGITS && !h->aff_loaded[2]) return g_err.fail(XVEC_ERR_STATE, "output weights not loaded");
     return XVEC_OK;
 }
 
@@ -504,7 +495,7 @@ int finalize_pool(xvec_handle* h, const LayerPlan& l5, float* pooled, hipStream_
 int plan_stack(const xvec_handle* h, const float* x_rows, int ldx, const int64_t* offs_dev, int B, int fixed_T, const Plan& p,
                int dtype, char* ws, LayerPlan (&lp)[XVEC_NUM_TDNN]) {
     const Prec prec = dtype == XVEC_F32 ? Prec::kF32 : dtype == XVEC_BF16 ? Prec::kBf16 : Prec::kBf16x3;
-    if (prec != Prec::kF32 && p.total > 0x7fffffff) return fail(XVEC_ERR_TOO_LARGE, "too many frames for one bf16 batch; split it");
+    if (prec != Prec::kF32 && p.total > 0x7fffffff) return g_err.fail(XVEC_ERR_TOO_LARGE, "too many frames for one bf16 batch; split it");
     const int nh = h->geo[0].n_pad;
     LayerCall c;
     memset(&c, 0, sizeof(c));
@@ -617,15 +608,15 @@ int stage_offsets(xvec_handle* h, const int64_t* offs_host, const int32_t* lengt
 }
 
 int common_checks(xvec_handle* h, const void* x, int B, int mode, int dtype, const void* out, const void* ws) {
-    if (!h) return fail(XVEC_ERR_ARG, "null handle");
-    if (!x || !out || !ws) return fail(XVEC_ERR_ARG, "null tensor pointer");
-    if (B < 1) return fail(XVEC_ERR_ARG, "B must be in [1, %d] (got %d)", kMaxUtts, B);
-    if (B > kMaxUtts) return fail(XVEC_ERR_TOO_LARGE, "B must be in [1, %d] (got %d); split larger batches", kMaxUtts, B);
+    if (!h) return g_err.fail(XVEC_ERR_ARG, "null handle");
+    if (!x || !out || !ws) return g_err.fail(XVEC_ERR_ARG, "null tensor pointer");
+    if (B < 1) return g_err.fail(XVEC_ERR_ARG, "B must be in [1, %d] (got %d)", kMaxUtts, B);
+    if (B > kMaxUtts) return g_err.fail(XVEC_ERR_TOO_LARGE, "B must be in [1, %d] (got %d); split larger batches", kMaxUtts, B);
     if (mode != XVEC_MODE_LOGITS && mode != XVEC_MODE_XVEC6 && mode != XVEC_MODE_XVEC7 && mode != XVEC_MODE_POOLED)
-        return fail(XVEC_ERR_ARG, "unknown mode %d", mode);
-    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return fail(XVEC_ERR_ARG, "unknown dtype %d", dtype);
+        return g_err.fail(XVEC_ERR_ARG, "unknown mode %d", mode);
+    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return g_err.fail(XVEC_ERR_ARG, "unknown dtype %d", dtype);
     if ((reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(ws) & 255))
-        return fail(XVEC_ERR_ARG, "x must be 16-byte and workspace 256-byte aligned");
+        return g_err.fail(XVEC_ERR_ARG, "x must be 16-byte and workspace 256-byte aligned");
     return check_loaded(h, mode);
 }
 
@@ -633,14 +624,14 @@ int common_checks(xvec_handle* h, const void* x, int B, int mode, int dtype, con
 // layout (stride = the producer's n_pad; layer 1: fp32 rows padded to cin_pad).  B and T are checked by the caller.
 int layer_entry(const xvec_handle* h, int layer, const void* x, const void* out, int B, int T, int dtype, void* workspace,
                 size_t workspace_bytes, Plan& p, LayerCall& c) {
-    if (!x || !out || !workspace) return fail(XVEC_ERR_ARG, "null tensor pointer");
-    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return fail(XVEC_ERR_ARG, "unknown dtype %d", dtype);
-    if (!h->tdnn_loaded[layer]) return fail(XVEC_ERR_STATE, "time_context_layers.%d weights not loaded", layer);
+    if (!x || !out || !workspace) return g_err.fail(XVEC_ERR_ARG, "null tensor pointer");
+    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return g_err.fail(XVEC_ERR_ARG, "unknown dtype %d", dtype);
+    if (!h->tdnn_loaded[layer]) return g_err.fail(XVEC_ERR_STATE, "time_context_layers.%d weights not loaded", layer);
     if (dtype == XVEC_BF16 && !h->folded[layer])
-        return fail(XVEC_ERR_STATE, "time_context_layers.%d: plain bf16 folds the BatchNorm of layer %d into it; load that layer too", layer, layer - 1);
+        return g_err.fail(XVEC_ERR_STATE, "time_context_layers.%d: plain bf16 folds the BatchNorm of layer %d into it; load that layer too", layer, layer - 1);
     p = make_plan(h, (int64_t)B * T, B);
     if (workspace_bytes < p.bytes)
-        return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
+        return g_err.fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
     char* ws = static_cast<char*>(workspace);
     const bool x3 = dtype == XVEC_BF16X3;
     const int span = h->geo[layer].ctx_span;
@@ -683,30 +674,30 @@ int stage_layer_input(const xvec_handle* h, const LayerCall& c, const LayerPlan&
 
 extern "C" {
 
-const char* xvec_last_error(void) { return g_err; }
+const char* xvec_last_error(void) { return g_err.c_str(); }
 #ifndef XVEC_BUILD_ID
 #define XVEC_BUILD_ID "unknown"
 #endif
 const char* xvec_version(void) { return "xvec_hip gfx950 build " XVEC_BUILD_ID; }
 
 int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
-    if (!cfg || !out) return fail(XVEC_ERR_ARG, "null argument");
+    if (!cfg || !out) return g_err.fail(XVEC_ERR_ARG, "null argument");
     if (cfg->input_size < 1 || cfg->hidden_size < 1 || cfg->num_classes < 1 || cfg->x_vector_size < 1)
-        return fail(XVEC_ERR_ARG, "sizes must be positive");
+        return g_err.fail(XVEC_ERR_ARG, "sizes must be positive");
     if (cfg->hidden_size > 8192 || cfg->input_size > 8192)
-        return fail(XVEC_ERR_ARG, "input_size / hidden_size above 8192 are not supported (32-bit row offsets)");
+        return g_err.fail(XVEC_ERR_ARG, "input_size / hidden_size above 8192 are not supported (32-bit row offsets)");
     DeviceGuard guard;                 // allocate on cfg->device, leave the caller's current device as it was
     HIP_TRY(guard.enter(cfg->device));
     hipDeviceProp_t prop;
     HIP_TRY(hipGetDeviceProperties(&prop, cfg->device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(XVEC_ERR_STATE, "device %d is %s; this library is built for gfx950 only", cfg->device,
-                    prop.gcnArchName);
+        return g_err.fail(XVEC_ERR_STATE, "device %d is %s; this library is built for gfx950 only", cfg->device,
+                          prop.gcnArchName);
     xvec_handle* h = new (std::nothrow) xvec_handle();
-    if (!h) return fail(XVEC_ERR_STATE, "out of host memory");
+    if (!h) return g_err.fail(XVEC_ERR_STATE, "out of host memory");
     memset(h, 0, sizeof(*h));
     h->cfg = *cfg;
-    h->num_cu = prop.multiProcessorCount;
+    h->num_cu = device_cu_count();
     h->pol = read_policy();
     h->cin_pad = round_up(cfg->input_size, 4);
     fill_geometry(h, h->geo, 2 * kBK);
@@ -721,7 +712,7 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
     });
     if (!ok) {
         xvec_destroy(h);
-        return fail(XVEC_ERR_HIP, "hipMalloc of packed weights failed");
+        return g_err.fail(XVEC_ERR_HIP, "hipMalloc of packed weights failed");
     }
     for (int i = 0; i < 2 && ok; ++i)
         ok = hipEventCreateWithFlags(&h->offs_evt[i], hipEventDisableTiming) == hipSuccess &&
@@ -733,7 +724,7 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
         ok = hipEventCreateWithFlags(&h->load_evt[i], hipEventDisableTiming) == hipSuccess;
     if (!ok) {
         xvec_destroy(h);
-        return fail(XVEC_ERR_HIP, "hipEventCreate / hipHostMalloc failed");
+        return g_err.fail(XVEC_ERR_HIP, "hipEventCreate / hipHostMalloc failed");
     }
     *out = h;
     return XVEC_OK;
@@ -760,15 +751,15 @@ void xvec_destroy(xvec_handle* h) {
 
 int xvec_load_tdnn(xvec_handle* h, int layer, const float* weight, const float* bias, const float* bn_weight,
                    const float* bn_bias, const float* bn_mean, const float* bn_var, float eps, xvec_stream stream) {
-    if (!h || layer < 0 || layer >= XVEC_NUM_TDNN) return fail(XVEC_ERR_ARG, "bad handle or layer %d", layer);
-    if (!weight || !bias) return fail(XVEC_ERR_ARG, "null weight/bias");
+    if (!h || layer < 0 || layer >= XVEC_NUM_TDNN) return g_err.fail(XVEC_ERR_ARG, "bad handle or layer %d", layer);
+    if (!weight || !bias) return g_err.fail(XVEC_ERR_ARG, "null weight/bias");
     DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
     HIP_TRY(guard.enter(h->cfg.device));
     const bool has_bn = bn_weight && bn_bias && bn_mean && bn_var;
     const bool none_bn = !bn_weight && !bn_bias && !bn_mean && !bn_var;
     if (h->cfg.batch_norm ? !has_bn : !none_bn)
-        return fail(XVEC_ERR_ARG, "BatchNorm tensors must be %s for batch_norm=%d",
-                    h->cfg.batch_norm ? "all given" : "all NULL", h->cfg.batch_norm);
+        return g_err.fail(XVEC_ERR_ARG, "BatchNorm tensors must be %s for batch_norm=%d",
+                          h->cfg.batch_norm ? "all given" : "all NULL", h->cfg.batch_norm);
     const TdnnGeom& g = h->geo[layer];
     // A RE-load of this layer while a neighbour's load is still in flight on another stream: that load's re-folds read
     // Wraw / vec of this layer (refold(layer) reads the producer's BatchNorm, refold(layer + 1) this layer's), which the writes
@@ -804,8 +795,8 @@ int xvec_load_tdnn(xvec_handle* h, int layer, const float* weight, const float* 
 
 int xvec_load_affine(xvec_handle* h, int which, const float* weight, const float* bias, xvec_stream stream) {
     const int i = aff_index(which);
-    if (!h || i < 0) return fail(XVEC_ERR_ARG, "bad handle or affine id %d", which);
-    if (!weight || !bias) return fail(XVEC_ERR_ARG, "null weight/bias");
+    if (!h || i < 0) return g_err.fail(XVEC_ERR_ARG, "bad handle or affine id %d", which);
+    if (!weight || !bias) return g_err.fail(XVEC_ERR_ARG, "null weight/bias");
     DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
     HIP_TRY(guard.enter(h->cfg.device));
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -822,7 +813,7 @@ size_t xvec_workspace_bytes(const xvec_handle* h, int64_t total_frames, int32_t 
 }
 
 int xvec_workspace_layout(const xvec_handle* h, int64_t total_frames, int32_t n_utts, xvec_ws_layout* out) {
-    if (!h || !out || total_frames < 1 || n_utts < 1) return fail(XVEC_ERR_ARG, "bad argument");
+    if (!h || !out || total_frames < 1 || n_utts < 1) return g_err.fail(XVEC_ERR_ARG, "bad argument");
     const Plan p = make_plan(h, total_frames, n_utts);
     out->act_a = p.actA;
     out->act_b = p.actB;
@@ -845,8 +836,8 @@ int xvec_forward(xvec_handle* h, const float* x, const int32_t* lengths_host, in
     DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
     HIP_TRY(guard.enter(h->cfg.device));
     if (T <= XVEC_TOTAL_CONTEXT)
-        return fail(XVEC_ERR_ARG, "T=%d: need at least %d frames (receptive field of the TDNN stack)", T,
-                    XVEC_TOTAL_CONTEXT + 1);
+        return g_err.fail(XVEC_ERR_ARG, "T=%d: need at least %d frames (receptive field of the TDNN stack)", T,
+                          XVEC_TOTAL_CONTEXT + 1);
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     const int C = h->cfg.input_size;
@@ -854,7 +845,7 @@ int xvec_forward(xvec_handle* h, const float* x, const int32_t* lengths_host, in
     if (!lengths_host) {
         const Plan p = make_plan(h, (int64_t)B * T, B);
         if (workspace_bytes < p.bytes)
-            return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
+            return g_err.fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
         float* xp = reinterpret_cast<float*>(ws + p.xpad);
         const bool pad = h->cin_pad != C;                 // channel count not a multiple of 4: pad rows once
         const float* rows = pad ? xp : x;
@@ -872,12 +863,12 @@ int xvec_forward(xvec_handle* h, const float* x, const int32_t* lengths_host, in
     for (int i = 0; i < B; ++i) {
         const int n = lengths_host[i];
         if (n <= XVEC_TOTAL_CONTEXT || n > T)
-            return fail(XVEC_ERR_ARG, "lengths[%d]=%d outside [%d, T=%d]", i, n, XVEC_TOTAL_CONTEXT + 1, T);
+            return g_err.fail(XVEC_ERR_ARG, "lengths[%d]=%d outside [%d, T=%d]", i, n, XVEC_TOTAL_CONTEXT + 1, T);
         total += n;
     }
     const Plan p = make_plan(h, total, B);
     if (workspace_bytes < p.bytes)
-        return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
+        return g_err.fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
     int64_t* offs_dev = reinterpret_cast<int64_t*>(ws + p.offs);
     float* xp = reinterpret_cast<float*>(ws + p.xpad);
     LayerPlan lp[XVEC_NUM_TDNN];
@@ -896,25 +887,25 @@ int xvec_forward_packed(xvec_handle* h, const float* x_packed, const int64_t* of
     if (rc) return rc;
     DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
     HIP_TRY(guard.enter(h->cfg.device));
-    if (!offsets_host) return fail(XVEC_ERR_ARG, "null offsets");
-    if (offsets_host[0] != 0) return fail(XVEC_ERR_ARG, "offsets[0] must be 0");
+    if (!offsets_host) return g_err.fail(XVEC_ERR_ARG, "null offsets");
+    if (offsets_host[0] != 0) return g_err.fail(XVEC_ERR_ARG, "offsets[0] must be 0");
     for (int i = 0; i < B; ++i) {
         const int64_t n = offsets_host[i + 1] - offsets_host[i];
         if (n <= XVEC_TOTAL_CONTEXT)
-            return fail(XVEC_ERR_ARG, "utterance %d has %lld frames; need at least %d", i, (long long)n,
-                        XVEC_TOTAL_CONTEXT + 1);
+            return g_err.fail(XVEC_ERR_ARG, "utterance %d has %lld frames; need at least %d", i, (long long)n,
+                              XVEC_TOTAL_CONTEXT + 1);
     }
     hipStream_t s = static_cast<hipStream_t>(stream);
     char* ws = static_cast<char*>(workspace);
     const int64_t total = offsets_host[B];
     const Plan p = make_plan(h, total, B);
     if (workspace_bytes < p.bytes)
-        return fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
+        return g_err.fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
     const int C = h->cfg.input_size;
     int64_t* offs_dev = reinterpret_cast<int64_t*>(ws + p.offs);
     float* xp = reinterpret_cast<float*>(ws + p.xpad);
     const bool pad = h->cin_pad != C;
-    if (pad && total > 0x7fffffff) return fail(XVEC_ERR_ARG, "too many frames");
+    if (pad && total > 0x7fffffff) return g_err.fail(XVEC_ERR_ARG, "too many frames");
     const float* rows = pad ? xp : x_packed;
     LayerPlan lp[XVEC_NUM_TDNN];
     if ((rc = plan_stack(h, rows, h->cin_pad, offs_dev, B, 0, p, dtype, ws, lp))) return rc;
@@ -928,9 +919,9 @@ int xvec_forward_packed(xvec_handle* h, const float* x_packed, const int64_t* of
 
 int xvec_tdnn_layer(xvec_handle* h, int layer, const float* x, int32_t B, int32_t T, int dtype, float* y,
                     void* workspace, size_t workspace_bytes, xvec_stream stream) {
-    if (!h || layer < 0 || layer >= XVEC_NUM_TDNN) return fail(XVEC_ERR_ARG, "bad handle or layer %d", layer);
+    if (!h || layer < 0 || layer >= XVEC_NUM_TDNN) return g_err.fail(XVEC_ERR_ARG, "bad handle or layer %d", layer);
     const TdnnGeom& g = h->geo[layer];
-    if (B < 1 || T <= g.ctx_span) return fail(XVEC_ERR_ARG, "need B>=1 and T>%d (got B=%d T=%d)", g.ctx_span, B, T);
+    if (B < 1 || T <= g.ctx_span) return g_err.fail(XVEC_ERR_ARG, "need B>=1 and T>%d (got B=%d T=%d)", g.ctx_span, B, T);
     Plan p;
     LayerCall c;
     int rc = layer_entry(h, layer, x, y, B, T, dtype, workspace, workspace_bytes, p, c);
@@ -972,9 +963,9 @@ int xvec_tdnn_layer(xvec_handle* h, int layer, const float* x, int32_t B, int32_
 int xvec_tdnn_pool_layer(xvec_handle* h, const float* x, int32_t B, int32_t T, int dtype, float* out, void* workspace,
                          size_t workspace_bytes, xvec_stream stream) {
     const int layer = XVEC_NUM_TDNN - 1;
-    if (!h) return fail(XVEC_ERR_ARG, "null handle");
+    if (!h) return g_err.fail(XVEC_ERR_ARG, "null handle");
     const int span = h->geo[layer].ctx_span;
-    if (B < 1 || B > kMaxUtts || T <= span) return fail(XVEC_ERR_ARG, "need 1<=B<=%d and T>%d (got B=%d T=%d)", kMaxUtts, span, B, T);
+    if (B < 1 || B > kMaxUtts || T <= span) return g_err.fail(XVEC_ERR_ARG, "need 1<=B<=%d and T>%d (got B=%d T=%d)", kMaxUtts, span, B, T);
     Plan p;
     LayerCall c;
     int rc = layer_entry(h, layer, x, out, B, T, dtype, workspace, workspace_bytes, p, c);
@@ -995,9 +986,9 @@ int xvec_tdnn_pool_layer(xvec_handle* h, const float* x, int32_t B, int32_t T, i
 
 int xvec_stat_pool(const float* x, const int32_t* lengths_dev, int32_t B, int32_t T, int32_t C, float* out,
                    xvec_stream stream) {
-    if (!x || !out) return fail(XVEC_ERR_ARG, "null tensor pointer");
-    if (B < 1 || T < 1 || C < 1) return fail(XVEC_ERR_ARG, "B, T, C must be positive");
-    if (B > 65535) return fail(XVEC_ERR_ARG, "B > 65535 not supported by the stand-alone pooling kernel");
+    if (!x || !out) return g_err.fail(XVEC_ERR_ARG, "null tensor pointer");
+    if (B < 1 || T < 1 || C < 1) return g_err.fail(XVEC_ERR_ARG, "B, T, C must be positive");
+    if (B > 65535) return g_err.fail(XVEC_ERR_ARG, "B > 65535 not supported by the stand-alone pooling kernel");
     PoolArgs a;
     memset(&a, 0, sizeof(a));
     a.X = x;
@@ -1012,9 +1003,9 @@ int xvec_stat_pool(const float* x, const int32_t* lengths_dev, int32_t B, int32_
 
 int xvec_affine(xvec_handle* h, int which, const float* x, int32_t M, int relu, float* y, xvec_stream stream) {
     const int i = aff_index(which);
-    if (!h || i < 0) return fail(XVEC_ERR_ARG, "bad handle or affine id %d", which);
-    if (!x || !y || M < 1) return fail(XVEC_ERR_ARG, "bad x/y/M");
-    if (!h->aff_loaded[i]) return fail(XVEC_ERR_STATE, "affine %d weights not loaded", which);
+    if (!h || i < 0) return g_err.fail(XVEC_ERR_ARG, "bad handle or affine id %d", which);
+    if (!x || !y || M < 1) return g_err.fail(XVEC_ERR_ARG, "bad x/y/M");
+    if (!h->aff_loaded[i]) return g_err.fail(XVEC_ERR_STATE, "affine %d weights not loaded", which);
     DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
     HIP_TRY(guard.enter(h->cfg.device));
     HIP_TRY(launch_affine_f32(x, h->affW[i], h->affB[i], y, M, h->affN[i], h->affK[i], relu,
@@ -1023,35 +1014,35 @@ int xvec_affine(xvec_handle* h, int which, const float* x, int32_t M, int relu, 
 }
 
 int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n) {
-    if (!h || !kernels || !n) return fail(XVEC_ERR_ARG, "null argument");
+    if (!h || !kernels || !n) return g_err.fail(XVEC_ERR_ARG, "null argument");
     for (int i = 0; i < XVEC_NUM_TDNN; ++i) kernels[i] = h->last_kernel[i];
     *n = XVEC_NUM_TDNN;
     return XVEC_OK;
 }
 
 int xvec_get_tdnn_form(const xvec_handle* h, int* forms, int* n) {
-    if (!h || !forms || !n) return fail(XVEC_ERR_ARG, "null argument");
+    if (!h || !forms || !n) return g_err.fail(XVEC_ERR_ARG, "null argument");
     for (int i = 0; i < XVEC_NUM_TDNN; ++i) forms[i] = h->last_form[i];
     *n = XVEC_NUM_TDNN;
     return XVEC_OK;
 }
 
 int xvec_get_tdnn_operands(const xvec_handle* h, int* operands, int* n) {
-    if (!h || !operands || !n) return fail(XVEC_ERR_ARG, "null argument");
+    if (!h || !operands || !n) return g_err.fail(XVEC_ERR_ARG, "null argument");
     for (int i = 0; i < XVEC_NUM_TDNN; ++i) operands[i] = h->last_operands[i];
     *n = XVEC_NUM_TDNN;
     return XVEC_OK;
 }
 
 int xvec_set_profiling(xvec_handle* h, int on) {
-    if (!h) return fail(XVEC_ERR_ARG, "null handle");
+    if (!h) return g_err.fail(XVEC_ERR_ARG, "null handle");
     h->profiling = on != 0;
     for (int i = 0; i < T_COUNT; ++i) h->ev_used[i] = false;
     return XVEC_OK;
 }
 
 int xvec_get_timings(xvec_handle* h, float* ms, int* n) {
-    if (!h || !ms || !n) return fail(XVEC_ERR_ARG, "null argument");
+    if (!h || !ms || !n) return g_err.fail(XVEC_ERR_ARG, "null argument");
     for (int i = 0; i < T_COUNT; ++i) {
         ms[i] = 0.f;
         if (h->ev_used[i]) {

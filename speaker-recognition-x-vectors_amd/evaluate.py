@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
+from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
 
 __all__ = ["TrialList", "TrialResult", "evaluate_trials", "evaluate_all_pairs", "sorted_keys", "EER", "minDCF",
            "plda_score_stat_object"]
@@ -37,20 +38,7 @@ class _Result(C.Structure):      # xvec_eval_result
                 ("n_nontarget", C.c_int64), ("n_nan", C.c_int64), ("n_bad_index", C.c_int64)]
 
 
-def _check(rc: int):
-    if rc != _hip.OK:
-        raise _hip.XvecError(rc, _hip.lib.xvec_eval_last_error().decode())
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _require_device(device) -> torch.device:
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("trial evaluation runs on a HIP device only (no CPU path)")
-    return device
+_check = checker(_hip.lib.xvec_eval_last_error)
 
 
 @dataclass
@@ -134,7 +122,7 @@ def _workspace(n: int, device) -> torch.Tensor:
     need = int(_hip.lib.xvec_eval_workspace_bytes(n))
     if need == 0:
         raise ValueError(f"{n} trials: the count must lie in 1 .. 2^31 - 1")
-    return torch.empty(need, dtype=torch.uint8, device=device)
+    return byte_workspace(need, device)
 
 
 def _read_result(out: torch.Tensor, what: str) -> TrialResult:
@@ -224,20 +212,16 @@ def sorted_keys(scores, is_target, workspace=None):
 
 def _score_vector(scores, device):
     """Scores as the reference feeds them to the package: float32 values (round to nearest even), here held as float64."""
-    if isinstance(scores, torch.Tensor):
-        t = scores.detach().reshape(-1)
-        if t.is_cuda:
-            device = t.device
-    else:
-        t = torch.from_numpy(np.asarray(scores, dtype=np.float64).reshape(-1))
-    return t.to(device=device).to(torch.float32).to(torch.float64), device
+    if isinstance(scores, torch.Tensor) and scores.is_cuda:
+        device = scores.device
+    return dev_f64(scores, device).reshape(-1).to(torch.float32).to(torch.float64), device
 
 
 def _pos_neg(positive_scores, negative_scores, c_miss, c_fa, p_target, device, what) -> TrialResult:
-    device = _require_device(device)
+    device = require_device(device, "trial evaluation")
     pos, device = _score_vector(positive_scores, device)
     neg, device = _score_vector(negative_scores, device)
-    device = _require_device(device)
+    device = require_device(device, "trial evaluation")
     if pos.numel() == 0 or neg.numel() == 0:
         raise ValueError(f"{what}: {pos.numel()} positive and {neg.numel()} negative scores; both kinds are needed")
     s = torch.cat([pos, neg.to(device)])
@@ -267,7 +251,7 @@ class plda_score_stat_object:
 
     def __init__(self, x_vectors_test, device="cuda:0"):
         from . import plda as _plda
-        self.device = _require_device(device)
+        self.device = require_device(device, "trial evaluation")
         self.x_vectors_test = x_vectors_test
         self.x_id_test = np.array(self.x_vectors_test.iloc[:, 1])
         self.x_vec_test = np.array([np.array(x_vec[1:-1].split(), dtype=np.float64)

@@ -16,22 +16,21 @@ import ctypes as C
 import torch
 
 from . import hip as _hip
+from ._device import checker, require_device, stream
+
+_check = checker(_hip.lib.xvec_mfcc_last_error)
 
 
 class MfccFrontEnd:
     def __init__(self, samplerate=16000, winlen=0.025, winstep=0.01, numcep=24, nfilt=26, nfft=512, lowfreq=0,
                  highfreq=None, preemph=0.97, ceplifter=22, appendEnergy=True, device="cuda:0"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("MfccFrontEnd runs on a HIP device only (no CPU path)")
+        self.device = require_device(device, "MfccFrontEnd")
         self.numcep = numcep
         cfg = _hip.MfccCfg(samplerate, winlen, winstep, numcep, nfilt, nfft, float(lowfreq), float(highfreq or 0),
                            preemph, int(ceplifter), int(bool(appendEnergy)),
                            self.device.index if self.device.index is not None else torch.cuda.current_device())
         plan = C.c_void_p()
-        rc = _hip.lib.xvec_mfcc_create(C.byref(cfg), C.byref(plan))
-        if rc != _hip.OK:
-            raise _hip.XvecError(rc, _hip.lib.xvec_mfcc_last_error().decode())
+        _check(_hip.lib.xvec_mfcc_create(C.byref(cfg), C.byref(plan)))
         self._plan = plan
 
     def __del__(self):
@@ -65,11 +64,9 @@ class MfccFrontEnd:
         B, n = w.shape
         out = torch.empty((B, self.num_frames(n), self.numcep), dtype=torch.float32, device=w.device)
         with torch.cuda.device(w.device):
-            stream = torch.cuda.current_stream(w.device).cuda_stream
             if i16:
-                rc = _hip.lib.xvec_mfcc_i16(self._plan, w.data_ptr(), float(scale), B, n, out.data_ptr(), stream)
+                rc = _hip.lib.xvec_mfcc_i16(self._plan, w.data_ptr(), float(scale), B, n, out.data_ptr(), stream(w.device))
             else:
-                rc = _hip.lib.xvec_mfcc(self._plan, w.data_ptr(), B, n, out.data_ptr(), stream)
-        if rc != _hip.OK:
-            raise _hip.XvecError(rc, _hip.lib.xvec_mfcc_last_error().decode())
+                rc = _hip.lib.xvec_mfcc(self._plan, w.data_ptr(), B, n, out.data_ptr(), stream(w.device))
+        _check(rc)
         return out

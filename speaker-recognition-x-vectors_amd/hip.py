@@ -14,6 +14,8 @@ import os
 # later one reports "no ROCm-capable device" (seen with build() followed by smoke() in one process).
 import torch  # noqa: F401
 
+from ._device import checker as _checker
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # XVEC_LIB: development override (A/B runs of two builds on one GPU box; diagnostic builds under build/).  It must
 # be an absolute path and is announced on stderr, so a stray library can never be picked up silently; the
@@ -137,9 +139,7 @@ def last_error() -> str:
     return lib.xvec_last_error().decode()
 
 
-def check(rc: int):
-    if rc != OK:
-        raise XvecError(rc, last_error())
+check = _checker(lib.xvec_last_error)
 
 
 def version() -> str:

@@ -20,6 +20,7 @@ import torch
 import torch.nn as nn
 
 from . import hip as _hip
+from ._device import stream as _stream_ptr
 
 TOTAL_CONTEXT = 14
 POOL_CHANNELS = 1500
@@ -34,10 +35,6 @@ def get_time_context(x: torch.Tensor, c: Sequence[int] = (0,)) -> List[torch.Ten
     last = len(c) - 1
     lo, hi = c[0], c[last]
     return [x[:, hi + cc: (lo + cc if cc != hi else None), :] for cc in c]
-
-
-def _stream_ptr(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _require_gpu(x: torch.Tensor, what: str):

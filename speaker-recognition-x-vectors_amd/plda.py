@@ -26,22 +26,9 @@ import numpy as np
 import torch
 
 from . import hip as _hip
+from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
 
-
-def _check(rc: int):
-    if rc != _hip.OK:
-        raise _hip.XvecError(rc, _hip.lib.xvec_plda_last_error().decode())
-
-
-def _require_device(device) -> torch.device:
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("PLDA training runs on a HIP device only (no CPU path)")
-    return device
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
+_check = checker(_hip.lib.xvec_plda_last_error)
 
 
 def host_em(sigma_obs, counts, rank_f, nb_iter, products):
@@ -92,17 +79,8 @@ class PldaStats:
     centred class sums on the device.  `fit(rank_f, nb_iter)` runs the EM from them; fits of several ranks share the pass."""
 
     def __init__(self, x, labels, scaling_factor=1.0, device="cuda:0"):
-        self.device = _require_device(device)
-        if isinstance(x, torch.Tensor):
-            t = x.detach()
-            if t.dtype not in (torch.float32, torch.float64):
-                t = t.to(torch.float64)
-            t = t.to(self.device).contiguous()
-        else:
-            a = np.asarray(x)
-            if a.dtype not in (np.float32, np.float64):
-                a = a.astype(np.float64)
-            t = torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        self.device = require_device(device, "PLDA training")
+        t = dev_f64(x, self.device, keep_f32=True)
         if t.dim() != 2:
             raise ValueError(f"PldaStats: expected [N, D] x-vectors, got shape {tuple(t.shape)}")
         n, dim = int(t.shape[0]), int(t.shape[1])
@@ -118,7 +96,7 @@ class PldaStats:
         self._cls_t = torch.empty((dim, C), **f64)
         sigma = torch.empty((dim, dim), **f64)
         order_d = torch.from_numpy(order).to(dev)
-        ws = torch.empty(max(1, int(_hip.lib.xvec_plda_stats_workspace_bytes(n, dim, C))), dtype=torch.uint8, device=dev)
+        ws = byte_workspace(_hip.lib.xvec_plda_stats_workspace_bytes(n, dim, C), dev)
         xd = _hip.PLDA_X_F32 if t.dtype == torch.float32 else _hip.PLDA_X_F64
         with torch.cuda.device(dev):
             _check(_hip.lib.xvec_plda_stats(t.data_ptr(), xd, n, dim, order_d.data_ptr(),
@@ -126,6 +104,7 @@ class PldaStats:
                                             mean.data_ptr(), counts.data_ptr(), self._cls.data_ptr(), self._cls_t.data_ptr(),
                                             sigma.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
         self._counts = counts
+        self._em_ws = None
         self.mean = mean.cpu().numpy()
         self.sigma_obs = sigma.cpu().numpy()
         self.counts = counts.cpu().numpy()
@@ -138,19 +117,17 @@ class PldaStats:
     def products(self, pq, lam):
         """(H'H, H' diag(n) H, H' S~) on the device for one EM iteration (see host_em)."""
         dev, R = self.device, int(np.asarray(lam).shape[0])
-        pq_t = torch.from_numpy(np.ascontiguousarray(np.asarray(pq, dtype=np.float64).T)).to(dev)
-        lam_d = torch.from_numpy(np.ascontiguousarray(lam, dtype=np.float64)).to(dev)
+        pq_t = dev_f64(np.asarray(pq).T, dev)
+        lam_d = dev_f64(lam, dev)
         out = torch.empty((R, 2 * R + self.dim), dtype=torch.float64, device=dev)
-        need = int(_hip.lib.xvec_plda_em_workspace_bytes(self.n_classes, R))
-        if getattr(self, "_em_ws", None) is None or self._em_ws.numel() < need:
-            self._em_ws = torch.empty(max(1, need), dtype=torch.uint8, device=dev)
+        self._em_ws = byte_workspace(_hip.lib.xvec_plda_em_workspace_bytes(self.n_classes, R), dev, self._em_ws)
         with torch.cuda.device(dev):
             s = torch.cuda.current_stream(dev)
             t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0.record(s)
             _check(_hip.lib.xvec_plda_em_products(pq_t.data_ptr(), self._cls.data_ptr(), self._cls_t.data_ptr(),
                                                   self._counts.data_ptr(), lam_d.data_ptr(), self.n_classes, self.dim, R,
-                                                  out.data_ptr(), self._em_ws.data_ptr(), self._em_ws.numel(), s.cuda_stream))
+                                                  out.data_ptr(), self._em_ws.data_ptr(), self._em_ws.numel(), _stream(dev)))
             t1.record(s)
         o = out.cpu().numpy()
         self._device_ms += t0.elapsed_time(t1)

@@ -21,30 +21,9 @@ import numpy as np
 import torch
 
 from . import hip as _hip
+from ._device import byte_workspace, checker, dev_f64 as _dev_f64, require_device, stream as _stream
 
-
-def _check(rc: int):
-    if rc != _hip.OK:
-        raise _hip.XvecError(rc, _hip.lib.xvec_score_last_error().decode())
-
-
-def _dev_f64(a, device) -> torch.Tensor:
-    if isinstance(a, torch.Tensor):
-        t = a.detach().to(device=device, dtype=torch.float64)
-    else:
-        t = torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64))).to(device)
-    return t.contiguous()
-
-
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _require_device(device) -> torch.device:
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("scoring runs on a HIP device only (no CPU path)")
-    return device
+_check = checker(_hip.lib.xvec_score_last_error)
 
 
 def gemm_nt(a: torch.Tensor, b: torch.Tensor, rowv=None, colv=None, cst=0.0, scale=1.0) -> torch.Tensor:
@@ -104,7 +83,7 @@ class PldaScorer:
     Phi / Psi products of the package's formulation."""
 
     def __init__(self, mean, F, Sigma, scaling_factor=1.0, device="cuda:0", lowrank=None):
-        self.device = _require_device(device)
+        self.device = require_device(device, "scoring")
         F = np.asarray(F, dtype=np.float64)
         self.dim = int(F.shape[0])
         if np.asarray(mean).shape != (self.dim,) or np.asarray(Sigma).shape != (self.dim, self.dim):
@@ -129,9 +108,7 @@ class PldaScorer:
         self._ws = None
 
     def _workspace(self, ne, nt):
-        need = int(_hip.lib.xvec_score_workspace_bytes(ne, nt, self.dim))
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws = byte_workspace(_hip.lib.xvec_score_workspace_bytes(ne, nt, self.dim), self.device, self._ws)
         return self._ws
 
     def score(self, enroll, test=None) -> torch.Tensor:
@@ -158,14 +135,13 @@ class PldaScorer:
 
 
 def cosine_scores(enroll, test=None, device="cuda:0") -> torch.Tensor:
-    device = _require_device(device)
+    device = require_device(device, "scoring")
     e = _dev_f64(enroll, device)
     t = None if test is None else _dev_f64(test, device)
     if e.dim() != 2 or (t is not None and (t.dim() != 2 or t.shape[1] != e.shape[1])):
         raise ValueError("cosine_scores: expected [N, D] x-vectors of one dimension")
     ne, nt, dim = e.shape[0], (e.shape[0] if t is None else t.shape[0]), e.shape[1]
-    ws = torch.empty(int(_hip.lib.xvec_score_workspace_bytes(ne, 0 if t is None else nt, dim)), dtype=torch.uint8,
-                     device=device)
+    ws = byte_workspace(_hip.lib.xvec_score_workspace_bytes(ne, 0 if t is None else nt, dim), device)
     out = torch.empty((ne, nt), dtype=torch.float64, device=device)
     with torch.cuda.device(device):
         _check(_hip.lib.xvec_cosine_score(e.data_ptr(), ne, t.data_ptr() if t is not None else None, nt, dim,
