@@ -8,7 +8,7 @@ from . import synth  # noqa: F401  (numpy only)
 
 __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontEnd", "PldaScorer", "hip", "extract",
            "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject", "evaluate", "TrialList", "TrialResult",
-           "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object"]
+           "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan"]
 
 
 def __getattr__(name):
@@ -28,7 +28,10 @@ def __getattr__(name):
     if name in ("TrialList", "TrialResult", "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object"):
         from . import evaluate
         return getattr(evaluate, name)
-    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate"):
+    if name in ("WaveAugmenter", "AugmentPlan"):
+        from . import augment
+        return getattr(augment, name)
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -1,4 +1,4 @@
-// Host-side plumbing of the C-ABI translation units (xvec_api, mfcc, score, plda_train, eval): the error text behind a
+// Host-side plumbing of the C-ABI translation units (xvec_api, mfcc, score, plda_train, eval, augment): the error text behind a
 // *_last_error() export, workspace carving, the CU count.  Host code only: nothing here is called from a kernel.
 #pragma once
 #include <hip/hip_runtime.h>

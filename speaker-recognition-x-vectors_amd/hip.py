@@ -31,6 +31,7 @@ LIB_PATH = _override or os.path.join(_HERE, "libxvec_hip.so")
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_WORKSPACE, ERR_TOO_LARGE = 0, 1, 2, 3, 4, 5
 F32, BF16, BF16X3 = 0, 1, 2
 PLDA_X_F32, PLDA_X_F64 = 0, 1                                   # XVEC_PLDA_X_*
+AUG_POOL_F32, AUG_POOL_I16 = 0, 1                               # XVEC_AUG_POOL_*
 MODE_LOGITS, MODE_POOLED, MODE_XVEC6, MODE_XVEC7 = 0, 5, 6, 7
 SEG6, SEG7, OUTPUT = 6, 7, 8
 KERNEL_NAMES = {0: None, 1: "tile128", 2: "pp", 3: "first"}      # XVEC_KERNEL_*
@@ -127,6 +128,14 @@ _SIGS = {
     "xvec_eval_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp,
                                       C.c_size_t, _vp]),
     "xvec_eval_sorted_keys": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    # include/xvec_augment.h
+    "xvec_aug_last_error": (C.c_char_p, []),
+    "xvec_aug_mix_workspace_bytes": (C.c_size_t, [_i32, _i64, _i64]),
+    "xvec_aug_mix": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                               C.c_size_t, _vp]),
+    "xvec_aug_reverb_workspace_bytes": (C.c_size_t, [_i32, _i64, _i64]),
+    "xvec_aug_reverb": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "xvec_aug_normalize": (C.c_int, [_vp, _i64, _i32, _i64, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 for _name, (_res, _args) in _SIGS.items():
