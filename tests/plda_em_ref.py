@@ -9,18 +9,18 @@ import numpy as np
 from scipy import linalg
 
 
-def class_stats(x, labels, scaling_factor=1.0):
+def class_stats(x, labels, scaling_factor=1.0, dtype=np.float64):
     """mean [D], sigma_obs [D, D] (biased), class names (sorted), counts [C] and class sums [C, D] (both scaled,
-    the sums NOT centred), numpy float64."""
-    x = np.asarray(x, dtype=np.float64)
+    the sums NOT centred), numpy float64 (or `dtype`: np.longdouble shows how far float64 itself is from the exact result)."""
+    x = np.asarray(x, dtype=dtype)
     classes, inv = np.unique(np.asarray(labels), return_inverse=True)
     inv = inv.reshape(-1)
     mean = x.mean(0)
     xc = x - mean
     sigma_obs = xc.T @ xc / x.shape[0]
-    sums = np.zeros((classes.shape[0], x.shape[1]))
+    sums = np.zeros((classes.shape[0], x.shape[1]), dtype=dtype)
     np.add.at(sums, inv, x)
-    counts = np.bincount(inv, minlength=classes.shape[0]).astype(np.float64)
+    counts = np.bincount(inv, minlength=classes.shape[0]).astype(dtype)
     return mean, sigma_obs, classes, counts * scaling_factor, sums * scaling_factor
 
 
@@ -58,6 +58,37 @@ def plda_em(x, labels, rank_f, nb_iter=10, scaling_factor=1.0):
         Sigma = sigma_obs - F @ _C / counts.sum()
         F = F @ linalg.cholesky(_R)
     return mean, F, Sigma
+
+
+def em_products_bound(sums_centred, counts, pq, lam):
+    """Element-wise error bounds (E_hh, E_nhh, E_hs) of the E-step products H'H, H' diag(n) H, H'S computed in float64 in
+    any summation order, with S = sums_centred [C, D], pq [D, R], H = (S pq) / (n lam + 1).  Derived, u = 2^-53:
+       a K-term product   |fl(A B') - A B'| <= (K + 8) u (|A| |B|'), whatever the order of the sum (the 8 is room for the
+                          second-order terms and for the roundings around the sum)
+       Y = S pq           E_Y = (D + 8) u (|S| |pq|)
+       H = Y / (n lam+1)  the denominator is positive and formed as one fused multiply-add or as a product and a sum, then the
+                          division: E_H = E_Y / (n lam + 1) + 2 u |H| (an unfused n lam adds u |H| <= u |S||pq| / (n lam + 1),
+                          inside the 8 u of E_Y)
+       n H                one more rounding: E_nH = n E_H + u |n H|
+       products of H      K = C, on operands that are themselves off by E_H: with Hb = |H| + E_H >= |computed H| and
+                          nHb = |n H| + E_nH
+                          E_hh  = (C + 8) u Hb' Hb  + Hb' E_H + E_H' Hb
+                          E_nhh = (C + 8) u Hb' nHb + E_H' nHb + Hb' E_nH
+                          E_hs  = (C + 8) u Hb' |S| + E_H' |S|           (S is an input: exact)
+    The bound terms themselves are formed in float64: they are sums of non-negative numbers, good to 1e-15 of themselves."""
+    S = np.abs(np.asarray(sums_centred, dtype=np.float64))
+    n = np.asarray(counts, dtype=np.float64)[:, None]
+    P = np.asarray(pq, dtype=np.float64)
+    u = 2.0 ** -53
+    C, D = S.shape
+    den = n * np.asarray(lam, dtype=np.float64)[None, :] + 1.0
+    H = np.abs(np.asarray(sums_centred, dtype=np.float64) @ P) / den
+    E_H = (D + 8) * u * (S @ np.abs(P)) / den + 2 * u * H
+    E_nH = n * E_H + u * n * H
+    Hb, nHb = H + E_H, n * H + E_nH
+    k = (C + 8) * u
+    return (k * Hb.T @ Hb + Hb.T @ E_H + E_H.T @ Hb, k * Hb.T @ nHb + E_H.T @ nHb + Hb.T @ E_nH,
+            k * Hb.T @ S + E_H.T @ S)
 
 
 def make_data(n_classes, dim, rank, sizes=(1, 40), seed=0, offset=3.0, between=1.0):

@@ -18,6 +18,38 @@ def numpy_products(sums_centred, counts):
     return products
 
 
+def em_inputs(C, dim, R, seed):
+    """Seeded E-step inputs (class_sums [C, dim], counts [C], pq_t [R, dim], lam [R]): normal sums, counts k / 2 with
+    k in 1 .. 60 (neither 1 nor always an integer), lam positive over three decades, pq of unit-norm-like columns."""
+    rng = np.random.default_rng(seed)
+    return (rng.normal(0, 1, (C, dim)), rng.integers(1, 61, C) * 0.5, rng.normal(0, 1, (R, dim)) / np.sqrt(dim),
+            10.0 ** rng.uniform(-1.5, 1.5, R))
+
+
+EM_SHAPES = [(1, 1, 1), (3, 5, 5), (130, 37, 7), (129, 64, 64), (257, 200, 50), (1211, 512, 200)]
+
+
+def em_reference(sums, counts, pq_t, lam):
+    """numpy_products in np.longdouble: (H'H, H' diag(n) H, H'S)."""
+    ld = lambda a: np.asarray(a, dtype=np.longdouble)
+    return numpy_products(ld(sums), ld(counts))(ld(pq_t).T, ld(lam))
+
+
+@pytest.mark.parametrize("C,dim,R", EM_SHAPES[:5])
+def test_em_products_bound_covers_float64_numpy(C, dim, R):
+    """The bound the device E-step is held to (plda_em_ref.em_products_bound) is not tighter than float64's own rounding:
+    numpy_products in float64 stays inside it against the longdouble evaluation."""
+    sums, counts, pq_t, lam = em_inputs(C, dim, R, C + dim + R)
+    got = numpy_products(sums, counts)(pq_t.T.copy(), lam)
+    want = em_reference(sums, counts, pq_t, lam)
+    bound = ref.em_products_bound(sums, counts, pq_t.T, lam)
+    for g, w, b, name in zip(got, want, bound, ("hh", "nhh", "hs")):
+        assert g.shape == w.shape == b.shape and (b > 0).all()
+        ratio = float((np.abs(g - w) / b).max())
+        print(f"C={C} dim={dim} R={R} {name}: float64 numpy error / bound = {ratio:.3f}")
+        assert ratio <= 1.0, (name, ratio)
+
+
 def host_fit(x, labels, rank_f, nb_iter=10, scaling_factor=1.0):
     from xvector_amd import plda
     mean, sigma_obs, _, counts, sums = ref.class_stats(x, labels, scaling_factor)
