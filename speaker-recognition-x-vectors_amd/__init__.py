@@ -8,7 +8,8 @@ from . import synth  # noqa: F401  (numpy only)
 
 __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontEnd", "PldaScorer", "hip", "extract",
            "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject", "evaluate", "TrialList", "TrialResult",
-           "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan"]
+           "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan",
+           "train", "XVectorTrainer", "tdnn_layer_train"]
 
 
 def __getattr__(name):
@@ -31,7 +32,10 @@ def __getattr__(name):
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
-    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment"):
+    if name in ("XVectorTrainer", "tdnn_layer_train"):
+        from . import train
+        return getattr(train, name)
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

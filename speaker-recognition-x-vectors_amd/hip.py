@@ -136,6 +136,13 @@ _SIGS = {
     "xvec_aug_reverb_workspace_bytes": (C.c_size_t, [_i32, _i64, _i64]),
     "xvec_aug_reverb": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "xvec_aug_normalize": (C.c_int, [_vp, _i64, _i32, _i64, _vp]),
+    # include/xvec_train.h
+    "xvec_train_last_error": (C.c_char_p, []),
+    "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
+    "xvec_tdnn_train_forward": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp, C.c_float,
+                                          _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "xvec_tdnn_train_backward": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp, _vp,
+                                           C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
 }
 EXPORTS = tuple(_SIGS)
 for _name, (_res, _args) in _SIGS.items():
