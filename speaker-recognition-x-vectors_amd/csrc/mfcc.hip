@@ -10,7 +10,8 @@
 // L2 -- plus numcep floats per frame out).
 //
 // The filterbank and the DCT x lifter matrices are built on the host in double precision with the
-// package's formulas (floor((nfft+1)*hz/samplerate) bin edges etc.) and kept on the device.
+// package's formulas (floor((nfft+1)*hz/samplerate) bin edges etc.) and kept on the device: mfcc_tables.h, host-only, which
+// also holds the layout constants (kThreads, fft512::k*) that the tables and the kernels below share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,16 +21,14 @@
 #include <cstring>
 #include <new>
 #include <type_traits>
-#include <vector>
 
 #include "../../include/xvec_hip.h"
 #include "host_support.h"
+#include "mfcc_tables.h"
 #include "xvec_internal.h"
 
 namespace {
 
-constexpr int kMaxNfft = 4096;
-constexpr int kThreads = 256;
 constexpr float kEps = 2.220446049250313e-16f;   // numpy.finfo(float).eps, what the package substitutes for 0
 
 struct MfccDev {
@@ -261,38 +260,6 @@ namespace fft512 {
 #define MF_KNOCK_TAIL false
 #endif
 
-constexpr int kTile = 16;                   // frames per block pass
-constexpr int kEx = 576;                    // complex slots of a wave's exchange region (8 x 72)
-constexpr int kPS = 264;                    // floats per row of the power-spectrum tile (256 + 8) and of the log-mel tile: row strides of 8 mod 64
-constexpr int kLS = 40;                     // dwords put the sixteen lanes of a ds_read_b128 service group (rows r, lane quads q: 16-byte
-                                            // fragments at 4 q) on sixteen distinct 4-bank windows (260 / 36: one 2-way conflict per group)
-constexpr int kMaxItems = 5;                // (filter tile, bin group) products per wave: 20 per block (the default filterbank has 18)
-// The power rows of a wave's SECOND pair of frames live in its own exchange region (idle from that pair's last exchange to the
-// next tile's first), its partial sums behind them; only the first pairs' eight rows have storage of their own: 30 016 bytes a
-// block, five blocks on a CU (round 6; sixteen rows of their own were 38 464 bytes, four blocks).
-constexpr int kExRow = 16;                  // floats: the rows in wave w's region start at 16 w + 4: with the row stride (8 mod 64) the
-constexpr int kExRow0 = 4;                  // eight rows of the array sit on bank offsets 0, 8, ..., 56 and these eight on 4, 12, ..., 60
-constexpr int kExPart = 592;                // floats: the partial sums (2 x 64 lanes x 4) behind the rows (3 x 16 + 4 + 2 x 264 = 580)
-static_assert(3 * kExRow + kExRow0 + 2 * kPS <= kExPart && kExPart + 512 <= 2 * kEx && kExPart % 4 == 0 && kExRow0 % 4 == 0,
-              "layout of an exchange region");
-constexpr int kLdsFloats = 4 * kEx * 2 + (kTile / 2) * kPS + kTile * kLS + 2 * kTile + 2 * 56;
-// ---- the banded filterbank (round 6).  A bin carries weight for two neighbouring triangles, the dense form multiplies it
-// with sixteen: 18 products of 16 x 16 x 16 per tile, 32 cycles of the matrix pipe per 16 x 16 x 4 step, 640 cycles per wave
-// and tile -- a fifth of a SIMD's busy time.  v_mfma_f32_4x4x1_16b_f32 is SIXTEEN independent 4 x 4 x 1 products (8 cycles):
-// block 4 fq + s takes frames 4 fq .. + 3 (rows) of ONE bin and the bin's weights for FOUR neighbouring filters (columns).
-// The host cuts the bins into at most 15 GROUPS of at most 20 consecutive bins whose filters fit one window of four (a .. a + 3);
-// wave w owns groups 4 w .. 4 w + 3, SLOT s of its instructions is group 4 w + s, instruction n the group's bin n: 20
-// instructions of 8 cycles per wave and tile, every lane ends with a group's [4 frames] x one filter, nothing to add across
-// lanes.  The summing threads gather per filter the (at most eight) groups that hold it, in bin order; an absent entry points
-// at group 15, whose weights are all zero.
-constexpr int kBandN = 20;                  // instructions per tile and wave = bins a group's lanes read
-constexpr int kBandCap = 19;                // bins of a group that may carry weight: one bin of play, so that the four groups of a wave
-                                            // can start their reads on four different residues mod 4 -- with the sixteen rows on bank
-                                            // offsets 0, 4, ..., 60 the 64 lanes of a read then fall on 64 different banks
-constexpr int kBandGroups = 15;             // (+ the all-zero group 15)
-constexpr int kBandGat = 8;                 // groups a filter can collect from
-constexpr int kBandLdsFloats = kLdsFloats + kBandGat * 32;   // + the gather table
-static_assert(kBandLdsFloats * 4 <= 32 * 1024, "five blocks per CU");
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
 // A complex value is a register pair and the arithmetic below is PACKED fp32 (v_pk_add_f32 / v_pk_mul_f32 /
@@ -805,8 +772,6 @@ __global__ __launch_bounds__(256, 5) void mfcc512_kernel(const void* __restrict_
 
 thread_local xvec::ErrorChannel g_merr;
 
-int round_half_up(double v) { return (int)std::floor(v + 0.5); }   // sigproc.round_half_up for v >= 0
-
 }  // namespace
 
 struct xvec_mfcc_plan {
@@ -821,262 +786,45 @@ extern "C" {
 
 const char* xvec_mfcc_last_error(void) { return g_merr.c_str(); }
 
-int xvec_mfcc_create(const xvec_mfcc_cfg* cfg, xvec_mfcc_plan** out) {
+int xvec_mfcc_create(const xvec_mfcc_cfg* cfg, xvec_mfcc_plan** out) try {
     if (!cfg || !out) return g_merr.fail(XVEC_ERR_ARG, "null argument");
-    const int nfft = cfg->nfft;
-    int log2n = 0;
-    while ((1 << log2n) < nfft) ++log2n;
-    if (nfft < 64 || nfft > kMaxNfft || (1 << log2n) != nfft) return g_merr.fail(XVEC_ERR_ARG, "nfft must be a power of two in [64, 4096]");
-    if (cfg->samplerate < 1 || cfg->nfilt < 1 || cfg->nfilt > kThreads || cfg->nfilt > nfft / 2 + 1 ||
-        cfg->numcep < 1 || cfg->numcep > cfg->nfilt)
-        return g_merr.fail(XVEC_ERR_ARG, "need 1 <= numcep <= nfilt <= min(256, nfft/2+1) and a positive sample rate");
-    const int frame_len = round_half_up((double)cfg->winlen * cfg->samplerate);
-    const int frame_step = round_half_up((double)cfg->winstep * cfg->samplerate);
-    if (frame_len < 1 || frame_step < 1) return g_merr.fail(XVEC_ERR_ARG, "window length/step too small");
+    // (XVEC_MFCC_FILTERBANK=dense keeps the dense products for a filterbank the banded form can hold: tests and A/B timing)
+    const char* force = getenv("XVEC_MFCC_FILTERBANK");
+    MfccTables t;
+    ErrorText why;
+    const int rc = build_mfcc_tables(*cfg, !(force && strcmp(force, "dense") == 0), t, why);
+    if (rc != XVEC_OK) return g_merr.fail(rc, "%s", why.text);
     if (hipSetDevice(cfg->device) != hipSuccess) return g_merr.fail(XVEC_ERR_HIP, "hipSetDevice failed");
-
-    const int nbins = nfft / 2 + 1, nfilt = cfg->nfilt, numcep = cfg->numcep;
-    // python_speech_features.base.get_filterbanks, in double
-    const double high = cfg->highfreq > 0 ? cfg->highfreq : cfg->samplerate / 2.0, low = cfg->lowfreq;
-    auto hz2mel = [](double hz) { return 2595.0 * std::log10(1.0 + hz / 700.0); };
-    auto mel2hz = [](double mel) { return 700.0 * (std::pow(10.0, mel / 2595.0) - 1.0); };
-    std::vector<double> bins(nfilt + 2);
-    for (int i = 0; i < nfilt + 2; ++i) {
-        const double mel = hz2mel(low) + (hz2mel(high) - hz2mel(low)) * i / (nfilt + 1);
-        bins[i] = std::floor((nfft + 1) * mel2hz(mel) / cfg->samplerate);
-    }
-    // non-zero weights only: filter j covers bins [lo_j, lo_j + len_j)
-    std::vector<float> fbw;
-    std::vector<int> lo(nfilt), off(nfilt + 1);
-    for (int j = 0; j < nfilt; ++j) {
-        const int b0 = std::min((int)bins[j], nbins), b1 = std::min((int)bins[j + 1], nbins),
-                  b2 = std::min((int)bins[j + 2], nbins);
-        lo[j] = b0;
-        off[j] = (int)fbw.size();
-        for (int i = b0; i < b1; ++i) fbw.push_back((float)((i - bins[j]) / (bins[j + 1] - bins[j])));
-        for (int i = b1; i < b2; ++i) fbw.push_back((float)((bins[j + 2] - i) / (bins[j + 2] - bins[j + 1])));
-    }
-    off[nfilt] = (int)fbw.size();
-    // scipy dct(type=2, norm='ortho') rows times base.lifter
-    const int dct_ld = nfilt | 1;
-    std::vector<float> dctl((size_t)numcep * dct_ld, 0.f);
-    for (int k = 0; k < numcep; ++k) {
-        const double scale = std::sqrt((k == 0 ? 1.0 : 2.0) / nfilt);
-        const double lift = cfg->ceplifter > 0 ? 1.0 + (cfg->ceplifter / 2.0) * std::sin(M_PI * k / cfg->ceplifter) : 1.0;
-        for (int m = 0; m < nfilt; ++m)
-            dctl[(size_t)k * dct_ld + m] = (float)(std::cos(M_PI * k * (2 * m + 1) / (2.0 * nfilt)) * scale * lift);
-    }
-    // twiddles W_M^j = exp(-2 pi i j / M), grouped per pass of the kernel: for h = 1, 4, 16, ...
-    // records {W_2h^j, W_4h^j, W_4h^(j+h)}, j < h; then, for odd log2(nfft), W_N^j, j < N/2
-    std::vector<float> tw;
-    auto push_w = [&](int j, int M) {
-        tw.push_back((float)std::cos(2.0 * M_PI * j / M));
-        tw.push_back((float)(-std::sin(2.0 * M_PI * j / M)));
-    };
-    int st = 0;
-    for (; st + 1 < log2n; st += 2) {
-        const int h = 1 << st;
-        for (int j = 0; j < h; ++j) {
-            push_w(j, 2 * h);
-            push_w(j, 4 * h);
-            push_w(j + h, 4 * h);
-        }
-    }
-    if (st < log2n)
-        for (int j = 0; j < nfft / 2; ++j) push_w(j, nfft);
-
     xvec_mfcc_plan* p = new (std::nothrow) xvec_mfcc_plan();
     if (!p) return g_merr.fail(XVEC_ERR_STATE, "out of host memory");
     memset(p, 0, sizeof(*p));
     p->cfg = *cfg;
-    // one blob: twiddle | dctl | fb_w | fb_lo | fb_off (ints stored bit-for-bit in the float array)
-    std::vector<float> blob;
-    auto app_f = [&](const std::vector<float>& v) { int o = (int)blob.size(); blob.insert(blob.end(), v.begin(), v.end()); return o; };
-    auto app_i = [&](const std::vector<int>& v) {
-        int o = (int)blob.size();
-        for (int x : v) { float fv; memcpy(&fv, &x, 4); blob.push_back(fv); }
-        return o;
-    };
-    p->dev.tw_off = app_f(tw);
-    p->dev.dctl_off = app_f(dctl);
-    p->dev.fbw_off = app_f(fbw);
-    p->dev.fblo_off = app_i(lo);
-    p->dev.fboff_off = app_i(off);
-    if (blob.size() & 1) blob.push_back(0.f);            // keep the per-wave regions 8-byte aligned
-    p->dev.table_floats = (int)blob.size();
-    // tables of the nfft == 512 kernel, after the LDS image (16-byte aligned)
-    int f_tw1 = 0, f_tw2 = 0, f_fb = 0, f_dct = 0, f_band = -1, f_gat = 0;
-    p->fast = (nfft == 512 && nfilt <= 32 && numcep <= 32);
-    if (p->fast) {
-        while (blob.size() & 3) blob.push_back(0.f);
-        f_tw1 = (int)blob.size();
-        for (int k = 1; k < 8; ++k)
-            for (int l = 0; l < 64; ++l) {
-                blob.push_back((float)std::cos(2.0 * M_PI * (l * k) / 512.0));
-                blob.push_back((float)(-std::sin(2.0 * M_PI * (l * k) / 512.0)));
-            }
-        f_tw2 = (int)blob.size();
-        for (int k = 1; k < 8; ++k)
-            for (int c = 0; c < 8; ++c) {
-                blob.push_back((float)std::cos(2.0 * M_PI * (c * k) / 64.0) * 0.015625f);   // (x 2^-6: fft512, kTwoM6)
-                blob.push_back((float)(-std::sin(2.0 * M_PI * (c * k) / 64.0)) * 0.015625f);
-            }
-        // dense filterbank [32][256] (bin 256 never carries a weight: the last edge is exclusive) -> B fragments
-        // of v_mfma_f32_16x16x4_f32: lane l of product (tile t, group g) holds FB[16t + (l & 15)][16g + 4(l >> 4) + j]
-        std::vector<float> dense(32 * 256, 0.f);
-        for (int j = 0; j < nfilt; ++j)
-            for (int k = 0; k < off[j + 1] - off[j]; ++k)
-                if (lo[j] + k < 256) dense[j * 256 + lo[j] + k] = 2.f * fbw[off[j] + k];   // (x 2: the kernel's power rows are halves, kTwoM6)
-        f_fb = (int)blob.size();
-        int g_lo[2] = {16, 16}, g_hi[2] = {0, 0};
-        for (int t = 0; t < 2; ++t)
-            for (int g = 0; g < 16; ++g)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 4; ++j) {
-                        const float w = dense[(16 * t + (l & 15)) * 256 + 16 * g + 4 * (l >> 4) + j];
-                        blob.push_back(w);
-                        if (w != 0.f) {
-                            g_lo[t] = std::min(g_lo[t], g);
-                            g_hi[t] = std::max(g_hi[t], g + 1);
-                        }
-                    }
-        for (int t = 0; t < 2; ++t)
-            if (g_hi[t] <= g_lo[t]) g_lo[t] = g_hi[t] = 0;
-        p->dev.f_lo0 = g_lo[0];
-        p->dev.f_n0 = g_hi[0] - g_lo[0];
-        p->dev.f_lo1 = g_lo[1];
-        p->dev.f_n1 = g_hi[1] - g_lo[1];
-        if (p->dev.f_n0 + p->dev.f_n1 > 4 * fft512::kMaxItems) p->fast = false;   // an unusually dense filterbank
-        f_dct = (int)blob.size();
-        for (int t = 0; t < 2; ++t)
-            for (int g = 0; g < 2; ++g)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 4; ++j) {
-                        const int c = 16 * t + (l & 15), m = 16 * g + 4 * (l >> 4) + j;
-                        blob.push_back(c < numcep && m < nfilt ? dctl[(size_t)c * dct_ld + m] : 0.f);
-                    }
-        // ---- the banded form (fft512::kBand*): groups of consecutive bins whose filters fit a window of four
-        {
-            using namespace fft512;
-            int fmin[256], fmax[256];
-            for (int k = 0; k < 256; ++k) {
-                fmin[k] = 32;
-                fmax[k] = -1;
-                for (int j = 0; j < 32; ++j)
-                    if (dense[j * 256 + k] != 0.f) {
-                        fmin[k] = std::min(fmin[k], j);
-                        fmax[k] = std::max(fmax[k], j);
-                    }
-            }
-            int g_k[16] = {}, g_cnt[16] = {}, g_a[16] = {}, n_groups = 0;   // (group 15 stays empty: all-zero weights)
-            bool ok = true;
-            for (int k = 0; k < 256 && ok;) {
-                if (n_groups == kBandGroups) { ok = false; break; }
-                int a = -1, cnt = 0;
-                const int k0 = k;
-                while (k < 256 && cnt < kBandCap) {
-                    if (fmax[k] >= 0) {                            // (a bin without weight joins any group)
-                        if (a < 0) a = std::min(fmin[k], 28);
-                        if (fmax[k] > a + 3) break;
-                    }
-                    ++k;
-                    ++cnt;
-                }
-                if (cnt == 0) { ok = false; break; }               // one bin wider than a window
-                g_k[n_groups] = k0;
-                g_cnt[n_groups] = cnt;
-                g_a[n_groups++] = a < 0 ? 0 : a;
-            }
-            // where the partial sums of group g, frame quad 0, filter column j sit (bytes from the start of the block's LDS):
-            // wave g >> 2 writes lane 16 fq + 4 (g & 3) + j
-            auto part_byte = [&](int g, int j) { return ((g >> 2) * 2 * kEx + kExPart) * 4 + ((g & 3) * 4 + j) * 16; };
-            std::vector<int> gat(kBandGat * 32, part_byte(15, 0));  // absent: a column of the all-zero group
-            int gat_n = 0;
-            for (int f = 0; f < 32 && ok; ++f) {
-                int e = 0;
-                for (int g = 0; g < n_groups; ++g) {
-                    if (f < g_a[g] || f > g_a[g] + 3) continue;
-                    bool any = false;
-                    for (int k = g_k[g]; k < g_k[g] + g_cnt[g]; ++k) any = any || dense[f * 256 + k] != 0.f;
-                    if (!any) continue;
-                    if (e == kBandGat) { ok = false; break; }
-                    gat[e++ * 32 + f] = part_byte(g, f - g_a[g]);
-                }
-                gat_n = std::max(gat_n, e);
-            }
-            p->dev.f_gat_n = gat_n;
-            // (XVEC_MFCC_FILTERBANK=dense keeps the dense products for a filterbank the banded form can hold: tests and A/B timing)
-            const char* force = getenv("XVEC_MFCC_FILTERBANK");
-            if (force && strcmp(force, "dense") == 0) ok = false;
-            if (ok) {
-                while (blob.size() & 3) blob.push_back(0.f);
-                f_band = (int)blob.size();
-                // first bin a group's lanes read: anywhere in [k + cnt - 20, k] (bins in front of the group carry weight 0), inside
-                // the row, and -- where that leaves a choice -- on a residue mod 4 no earlier group of the wave reads on
-                int k_rd[16];
-                for (int w = 0; w < 4; ++w) {
-                    bool used[4] = {false, false, false, false};
-                    for (int sl = 0; sl < 4; ++sl) {
-                        const int g = 4 * w + sl;
-                        const int hi_k = g < n_groups ? std::min(g_k[g], 256 - kBandN) : 256 - kBandN;
-                        const int lo_k = g < n_groups ? std::max(0, g_k[g] + g_cnt[g] - kBandN) : 0;
-                        int pick = hi_k;
-                        for (int kk = hi_k; kk >= lo_k; --kk)
-                            if (!used[kk & 3]) { pick = kk; break; }
-                        used[pick & 3] = true;
-                        k_rd[g] = pick;
-                    }
-                }
-                auto k_read = [&](int g) { return k_rd[g]; };
-                for (int w = 0; w < 4; ++w)
-                    for (int q5 = 0; q5 < 5; ++q5)
-                        for (int l = 0; l < 64; ++l)
-                            for (int c = 0; c < 4; ++c) {          // weight of instruction n = 4 q5 + c: bin n of group 4 w + slot
-                                const int g = 4 * w + ((l >> 2) & 3), t = l & 3, kk = k_read(g) + 4 * q5 + c;
-                                const bool live = g < n_groups && kk >= g_k[g] && kk < g_k[g] + g_cnt[g];
-                                blob.push_back(live ? dense[(g_a[g] + t) * 256 + kk] : 0.f);
-                            }
-                for (int w = 0; w < 4; ++w)                        // LDS byte address of frame 4 fq + t at the group's first bin
-                    for (int l = 0; l < 64; ++l) {
-                        const int fq = l >> 4, g = 4 * w + ((l >> 2) & 3), t = l & 3;
-                        const int rowf = (t >> 1) ? fq * (2 * kEx + kExRow) + kExRow0 + (t & 1) * kPS : 4 * kEx * 2 + (2 * fq + (t & 1)) * kPS;
-                        const int byte = (rowf + k_read(g)) * 4;
-                        float fv;
-                        memcpy(&fv, &byte, 4);
-                        blob.push_back(fv);
-                    }
-                f_gat = app_i(gat);
-            }
-        }
-    }
-    if (hipMalloc(&p->blob, blob.size() * 4) != hipSuccess) {
+    p->fast = t.fast;
+    if (hipMalloc(&p->blob, t.blob.size() * 4) != hipSuccess) {
         delete p;
         return g_merr.fail(XVEC_ERR_HIP, "hipMalloc failed");
     }
-    if (hipMemcpy(p->blob, blob.data(), blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+    if (hipMemcpy(p->blob, t.blob.data(), t.blob.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(p->blob);
         delete p;
         return g_merr.fail(XVEC_ERR_HIP, "hipMemcpy failed");
     }
-    p->dev.tables = static_cast<const float*>(p->blob);
-    p->dev.f_tw1 = p->dev.tables + f_tw1;
-    p->dev.f_tw2 = p->dev.tables + f_tw2;
-    p->dev.f_fb = p->dev.tables + f_fb;
-    p->dev.f_dct = p->dev.tables + f_dct;
-    p->dev.f_band = f_band >= 0 ? p->dev.tables + f_band : nullptr;
-    p->dev.f_gat = reinterpret_cast<const int*>(p->dev.tables + f_gat);
-    p->dev.frame_len = frame_len;
-    p->dev.frame_step = frame_step;
-    p->dev.nfft = nfft;
-    p->dev.log2n = log2n;
-    p->dev.nbins = nbins;
-    p->dev.nfilt = nfilt;
-    p->dev.numcep = numcep;
-    p->dev.append_energy = cfg->append_energy;
-    p->dev.preemph = cfg->preemph;
+    const float* tab = static_cast<const float*>(p->blob);
+    MfccDev& d = p->dev;
+    d.tables = tab;
+    d.tw_off = t.tw_off, d.dctl_off = t.dctl_off, d.fbw_off = t.fbw_off, d.fblo_off = t.fblo_off, d.fboff_off = t.fboff_off;
+    d.table_floats = t.table_floats;
+    d.frame_len = t.frame_len, d.frame_step = t.frame_step, d.nfft = cfg->nfft, d.log2n = t.log2n, d.nbins = t.nbins;
+    d.nfilt = cfg->nfilt, d.numcep = cfg->numcep, d.append_energy = cfg->append_energy, d.preemph = cfg->preemph;
+    d.f_tw1 = tab + t.f_tw1, d.f_tw2 = tab + t.f_tw2, d.f_fb = tab + t.f_fb, d.f_dct = tab + t.f_dct;
+    d.f_band = t.f_band >= 0 ? tab + t.f_band : nullptr;
+    d.f_gat = reinterpret_cast<const int*>(tab + t.f_gat);
+    d.f_n0 = t.f_n0, d.f_lo0 = t.f_lo0, d.f_n1 = t.f_n1, d.f_lo1 = t.f_lo1, d.f_gat_n = t.f_gat_n;
     p->num_cu = xvec::device_cu_count();     // (cfg->device is the current one: hipSetDevice above)
     *out = p;
     return XVEC_OK;
+} catch (const std::bad_alloc&) {            // the tables are std::vectors: nothing may throw across the C ABI
+    return g_merr.fail(XVEC_ERR_STATE, "out of host memory");
 }
 
 void xvec_mfcc_destroy(xvec_mfcc_plan* p) {
