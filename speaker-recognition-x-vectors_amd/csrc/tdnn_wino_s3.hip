@@ -8,19 +8,19 @@
 // accumulators per wave, as tdnn_wino.hip.  The K loop walks 16-wide chunks, each holding ALL FOUR products: a thread
 // loads the four input rows x0..x3 of its pair (16 bytes each), forms V0..V3 in fp32 (x0-x2 | x1+x2 | x2-x1 | x1-x3) and
 // writes their hi / mid / lo pieces to LDS -- each input row is read once per chunk instead of twice per product.  An LDS
-// buffer is [product][plane][64 pairs][16 k] bf16 = 24 KiB; two buffers, one barrier per chunk.  The U planes go from
-// global memory straight into the MFMA B operands (fragment-major, pack.hip: 12 KiB per wave and chunk, reloaded product
-// by product as soon as the previous chunk's MFMAs of that product have issued).
+// buffer is [product][plane][64 pairs][16 k] bf16 = 24 KiB, every (product, plane) block in the bank-conflict-free image of
+// wino_s3_lds_map.h; two buffers, one barrier per chunk.  The U planes go from global memory straight into the MFMA B operands
+// (fragment-major, pack.hip: 12 KiB per wave and chunk, requested product by product a whole chunk ahead, right behind the
+// MFMAs that last read their registers); the A fragments are read from LDS half a product ahead (s3_tile: the schedule).
 //   per block and chunk: 16 KiB of input rows + 48 KiB of U planes over 4 waves x 4 products x 2 groups x 6 = 192 MFMAs
 //   = 341 B per MFMA (the direct port of tdnn_wino.hip's tile: 427).
 #include "tdnn_wino_rows.h"
+#include "wino_s3_lds_map.h"
 
 namespace xvec {
 namespace wino {
 
-constexpr int kS3K = 16;                                  // k per chunk (one bf16 k-step)
-constexpr int kS3Plane = kPairs * kS3K * 2;               // bytes of one (product, plane) block: 64 pairs x 32 B
-constexpr int kS3Stage = 4 * 3 * kS3Plane;                // one LDS buffer: 4 products x hi | mid | lo
+static_assert(kS3Pairs == kPairs, "wino_s3_lds_map.h: kS3K, kS3Plane, kS3Stage and the image of a (product, plane) block");
 constexpr int kS3Const = kConst * 4;                      // bias | scale | shift of the tile's channels, bytes
 constexpr int kS3LdsBytes = 2 * kS3Stage + kS3Const + 2 * kTbl * 4 + 2 * 8;   // + row tables, per parity the base row
 
@@ -74,20 +74,91 @@ __device__ __forceinline__ void s3_vstore(char* B, int st, const S3Stage& s) {
     }
 }
 
-// the three U-plane fragments (hi | mid | lo) of product k of chunk c of this wave's column; the stream wraps to chunk 0
-// past the tile's last chunk (the next tile of the block is in the same channel column)
-__device__ __forceinline__ void s3_uld(__amdgpu_buffer_rsrc_t rsrc, int voff, float4* w, int k, int c, int n_chunks) {
-    if (c >= n_chunks) c -= n_chunks;
-#pragma unroll
-    for (int p = 0; p < 3; ++p) w[p] = buf_load16(rsrc, voff, ((4 * c + k) * 3 + p) * 1024);
-}
+// The U-plane fragments (hi | mid | lo) of the four products of a chunk, this wave's column, and the A fragments of one product
+// (a: pair group 0, b: pair group 1).  Named members, not arrays: the K loop below is pinned with scheduling barriers.
+struct S3U {
+    float4 w00, w01, w02, w10, w11, w12, w20, w21, w22, w30, w31, w32;
+};
+struct S3Frag {
+    float4 a0, a1, a2, b0, b1, b2;
+};
 
-// One tile of G pair groups x 128 channels; tp = its row-table parity.  On entry chunk 0 of the tile is in LDS buffer 0,
-// the U planes of chunk 0 are in w, and the staging registers hold chunk 1 (block prologue or the previous tile's chunks).
+// one MFMA of s3_mfma6's six (tdnn_common.h: the same products in the same order into the same accumulator)
+#define WS3_MF(acc_, x_, w_) \
+    acc_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x_), __builtin_bit_cast(bf16x8, w_), acc_, 0, 0, 0);
+// one A fragment of product kn_ of the chunk in buffer B_: plane pl_ of pair group g_ (0: ln.a_rd, 1: a_rd1)
+#define WS3_RD(dst_, B_, kn_, pl_, g_) \
+    dst_ = *reinterpret_cast<const float4*>((B_) + (3 * (kn_) + (pl_)) * kS3Plane + ((g_) ? a_rd1 : ln.a_rd));
+// the three U fragments of product K_ of chunk it + 1; the stream wraps to chunk 0 past the tile's last chunk (the next tile
+// of the block is in the same channel column)
+#define WS3_ULD(K_)                                                                   \
+    {                                                                                 \
+        int c_ = it + 1;                                                              \
+        if (c_ >= n_chunks) c_ -= n_chunks;                                           \
+        u.w##K_##0 = buf_load16(ursrc, ln.b_rd, ((4 * c_ + K_) * 3 + 0) * 1024);      \
+        u.w##K_##1 = buf_load16(ursrc, ln.b_rd, ((4 * c_ + K_) * 3 + 1) * 1024);      \
+        u.w##K_##2 = buf_load16(ursrc, ln.b_rd, ((4 * c_ + K_) * 3 + 2) * 1024);      \
+    }
+// Product K_ of a tile of two pair groups.  The two fragment sets roll: pair group 1's fragments of this product are read
+// from S behind the first MFMAs of pair group 0, pair group 0's of product kn_ (of the chunk in buffer NB_) behind the first
+// MFMAs of pair group 1 -- each into registers whose last MFMA has just issued, ONE ds_read_b128 per MFMA gap (MI355X: up to
+// two per gap are free), in the order the MFMAs take them (lo | mid | hi: the waits are counted), each five MFMAs ahead of
+// its use.  24 fragment registers, as without look-ahead.
+// BAR_: the chunk's barrier, between the two pair groups of product 3 (see the loop).
+#define WS3_PRODUCT2(K_, NB_, kn_, BAR_)                                                                   \
+    {                                                                                                      \
+        WS3_MF(acc##K_##_0, f.a2, u.w##K_##0) WS3_RD(f.b2, S, K_, 2, 1) SB();                              \
+        WS3_MF(acc##K_##_0, f.a1, u.w##K_##1) WS3_RD(f.b1, S, K_, 1, 1) SB();                              \
+        WS3_MF(acc##K_##_0, f.a0, u.w##K_##2) WS3_RD(f.b0, S, K_, 0, 1) SB();                              \
+        WS3_MF(acc##K_##_0, f.a1, u.w##K_##0) WS3_MF(acc##K_##_0, f.a0, u.w##K_##1) WS3_MF(acc##K_##_0, f.a0, u.w##K_##0) SB(); \
+        BAR_                                                                                               \
+        WS3_MF(acc##K_##_1, f.b2, u.w##K_##0) WS3_RD(f.a2, NB_, kn_, 2, 0) SB();                           \
+        WS3_MF(acc##K_##_1, f.b1, u.w##K_##1) WS3_RD(f.a1, NB_, kn_, 1, 0) SB();                           \
+        WS3_MF(acc##K_##_1, f.b0, u.w##K_##2) WS3_RD(f.a0, NB_, kn_, 0, 0) SB();                           \
+        WS3_MF(acc##K_##_1, f.b1, u.w##K_##0) WS3_MF(acc##K_##_1, f.b0, u.w##K_##1) WS3_MF(acc##K_##_1, f.b0, u.w##K_##0) SB(); \
+        WS3_ULD(K_)                                                                                        \
+        SB();                                                                                              \
+    }
+// Product K_ of a tile of one pair group (a block's odd last tile): the second set's registers are free, so the fragments of
+// product kn_ go to set N_ while this product runs on set C_ (a | b, alternating; product 0 runs on a).  BAR_ comes first:
+// product 3's own fragments were read a product ago, and the next chunk's must be read behind it.
+#define WS3_PRODUCT1(K_, C_, N_, NB_, kn_, BAR_)                                                           \
+    {                                                                                                      \
+        BAR_                                                                                               \
+        WS3_MF(acc##K_##_0, f.C_##2, u.w##K_##0) WS3_RD(f.N_##2, NB_, kn_, 2, 0) SB();                     \
+        WS3_MF(acc##K_##_0, f.C_##1, u.w##K_##1) WS3_RD(f.N_##1, NB_, kn_, 1, 0) SB();                     \
+        WS3_MF(acc##K_##_0, f.C_##0, u.w##K_##2) WS3_RD(f.N_##0, NB_, kn_, 0, 0) SB();                     \
+        WS3_MF(acc##K_##_0, f.C_##1, u.w##K_##0) WS3_MF(acc##K_##_0, f.C_##0, u.w##K_##1) WS3_MF(acc##K_##_0, f.C_##0, u.w##K_##0) SB(); \
+        WS3_ULD(K_)                                                                                        \
+        SB();                                                                                              \
+    }
+
+// One tile of G pair groups x 128 channels; tp = its row-table parity.  On entry chunk 0 of the tile is in LDS buffer 0, its
+// U planes are in u (or on their way), pair group 0's A fragments of its product 0 in f.a*, and the staging registers hold
+// chunk 1 (block prologue or the previous tile's last chunks).
+//
+// Schedule of chunk `it` (buffer S = it & 1, Sn the other one), per wave; every step is pinned in this order:
+//   head       V of chunk it+1 (staging registers) -> Sn; the load stream steps on; the four x rows of chunk it+2 are requested
+//   product k  (k = 0..3) 6 G MFMAs, the A fragments of each half read half a product ahead (WS3_PRODUCT2; G = 1: a whole
+//              product, WS3_PRODUCT1); then the three U fragments of product k of chunk it+1 are requested, straight into the
+//              registers product k has just finished with
+//   barrier    inside product 3, between its two pair groups (G = 1: in front of it): every wave has then READ all of S (the
+//              wait in front of the barrier covers its last fragments) and WRITTEN all of Sn (head).  Behind it, under the
+//              second half of product 3, pair group 0's fragments of product 0 of chunk it+1 are read from Sn; the next head
+//              overwrites S.
+// Vector-memory queue of a wave, oldest first, when the head of chunk it starts (buffer loads return in order):
+//   x(it+1) x 4 | U(it, 0) x 3 | U(it, 1) x 3 | U(it, 2) x 3 | U(it, 3) x 3
+//   head:       the V stores need x(it+1): 12 younger entries may stay            -> vmcnt(12); then x(it+2) x 4 is appended
+//   product 0:  needs U(it, 0): younger are U(it, 1..3) = 9 and x(it+2) = 4       -> vmcnt(13); then U(it+1, 0) x 3
+//   product k:  needs U(it, k): younger are U(it, k+1..3), x(it+2), U(it+1, 0..k-1) = 3 (3-k) + 4 + 3 k = 13  -> vmcnt(13)
+// (13 for the fragment a product takes last; its first two MFMAs take the two requested before it: vmcnt(15), vmcnt(14))
+// so a U fragment has a whole chunk (48 MFMAs) to arrive and the queue is never drained.  The counts are hipcc's own (it sees
+// every load here); the block prologue requests in the same order, so the first chunk meets the same queue.  A tile's first
+// head may find the previous epilogue's stores behind the loads: its wait then covers a few entries more, never fewer.
 template <int G>
 __device__ __forceinline__ void s3_tile(const TdnnArgs& a, char* lds, int* tbl, int64_t* tblh, Ctx& cx, const Lane& ln,
-                                        S3Stage& st, float4 (&w)[4][3], __amdgpu_buffer_rsrc_t ursrc, int n0, int tp,
-                                        int n_chunks) {
+                                        int a_rd1, S3Stage& st, S3U& u, S3Frag& f, __amdgpu_buffer_rsrc_t ursrc, int n0,
+                                        int tp, int n_chunks) {
     const bool grp = (threadIdx.x >> 2) & 1;
     f32x16 acc0_0, acc0_1, acc1_0, acc1_1, acc2_0, acc2_1, acc3_0, acc3_1;
 #pragma unroll
@@ -104,25 +175,26 @@ __device__ __forceinline__ void s3_tile(const TdnnArgs& a, char* lds, int* tbl, 
         s3_vstore(Sn, ln.st_off, st);
         s3_advance(a, cx, ln, tbl, tblh, n_chunks);
         s3_gld(cx, grp, st);
-#define WS3_PRODUCT(K_)                                                                                        \
-        {                                                                                                      \
-            float4 xf0[3], xf1[3];                                                                             \
-            _Pragma("unroll") for (int pl = 0; pl < 3; ++pl) {                                                 \
-                xf0[pl] = *reinterpret_cast<const float4*>(S + (3 * K_ + pl) * kS3Plane + ln.a_rd);            \
-                if constexpr (G > 1)                                                                           \
-                    xf1[pl] = *reinterpret_cast<const float4*>(S + (3 * K_ + pl) * kS3Plane + 32 * 32 + ln.a_rd); \
-            }                                                                                                  \
-            s3_mfma6(acc##K_##_0, xf0, w[K_]);                                                                 \
-            if constexpr (G > 1) s3_mfma6(acc##K_##_1, xf1, w[K_]);                                            \
-            s3_uld(ursrc, ln.b_rd, w[K_], K_, it + 1, n_chunks);                                               \
+        SB();
+        if constexpr (G > 1) {
+            WS3_PRODUCT2(0, S, 1, )
+            WS3_PRODUCT2(1, S, 2, )
+            WS3_PRODUCT2(2, S, 3, )
+            WS3_PRODUCT2(3, Sn, 0, __syncthreads(); SB();)
+        } else {
+            WS3_PRODUCT1(0, a, b, S, 1, )
+            WS3_PRODUCT1(1, b, a, S, 2, )
+            WS3_PRODUCT1(2, a, b, S, 3, )
+            WS3_PRODUCT1(3, b, a, Sn, 0, __syncthreads(); SB();)
         }
-        WS3_PRODUCT(0) WS3_PRODUCT(1) WS3_PRODUCT(2) WS3_PRODUCT(3)
-#undef WS3_PRODUCT
-        __syncthreads();   // chunk it + 1 complete in LDS; chunk it's buffer is free
     }
 
     epilogue<G>(a, reinterpret_cast<const float*>(lds + 2 * kS3Stage), tbl, tblh, ln, n0, tp, acc0_0, acc1_0, acc2_0, acc3_0, acc0_1,
                 acc1_1, acc2_1, acc3_1);
+    // With two chunks per tile the load stream reaches the tile after the next one at the head of the next tile's chunk 0:
+    // set_rows then rewrites the row-table parity this epilogue has just read, with no barrier of the K loop in between (from
+    // four chunks on there is one).  A wave that is still in this epilogue must not see those rows.
+    if (n_chunks == 2) __syncthreads();
 }
 
 __global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const TdnnArgs a) {
@@ -138,33 +210,48 @@ __global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const TdnnArgs a) 
     const int n_chunks = 2 * a.cpt;        // 16-wide chunks per product (cpt counts 32-wide ones)
     const int64_t g_begin = cx.g_s, g_end = cx.g_end;     // (the load stream moves cx.g_s on)
     const int tid = threadIdx.x, lane = tid & 63, wave = ln.wave;
-    ln.st_off = (ln.r0 + 32 * ((tid >> 2) & 1)) * (kS3K * 2) + (tid & 3) * 8;   // byte offset in a plane block
-    ln.a_rd = ln.r * (kS3K * 2) + ln.h * 16;     // A fragment of lane (r, h): pair r of the group, k 8h .. 8h + 7
-    ln.b_rd = lane * 16;                      // U fragment: 16 bytes per lane of a 1 KiB block
+    // byte offsets in a (product, plane) block (wino_s3_lds_map.h: the conflict-free image): of this thread's 8 staged bytes,
+    // and of the A fragment of lane (r, h) -- pair r of the group, k 8h .. 8h + 7 -- in pair groups 0 (a_rd) and 1 (a_rd1)
+    ln.st_off = s3_st_off(tid);
+    ln.a_rd = s3_a_rd(lane, 0);
+    const int a_rd1 = s3_a_rd(lane, 1);
     ln.sw = 0;
+    ln.b_rd = lane * 16;                      // U fragment: 16 bytes per lane of a 1 KiB block
     // U planes of this wave's 32-channel column: 12 KiB per chunk ((chunk, product, plane) blocks of 1 KiB)
     const int64_t ct = n0 / 32 + wave;
     const __amdgpu_buffer_rsrc_t ursrc = make_rsrc(static_cast<const char*>(a.Wf) + ct * (int64_t)n_chunks * 12288);
 
     stream_start(a, n0, cst, tbl, tblh, cx, ln);
 
-    // prologue: chunk 0 -> LDS buffer 0, the U planes of chunk 0 -> w, chunk 1 in the staging registers
+    // prologue: chunk 0 -> LDS buffer 0, chunk 1 in the staging registers, the U planes of chunk 0 requested behind it (the
+    // K loop's request order: s3_tile), the A fragments of product 0 read behind the barrier
     const bool grp = (tid >> 2) & 1;
     S3Stage st;
-    float4 w[4][3];
+    S3U u;
+    S3Frag f;
     s3_gld(cx, grp, st);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) s3_uld(ursrc, ln.b_rd, w[k], k, 0, n_chunks);
     s3_vstore(lds, ln.st_off, st);
     s3_advance(a, cx, ln, tbl, tblh, n_chunks);
     s3_gld(cx, grp, st);
+    SB();
+    {
+        const int it = -1;
+        WS3_ULD(0) WS3_ULD(1) WS3_ULD(2) WS3_ULD(3)
+    }
+    SB();
     __syncthreads();
+    WS3_RD(f.a2, lds, 0, 2, 0) WS3_RD(f.a1, lds, 0, 1, 0) WS3_RD(f.a0, lds, 0, 0, 0)
 
     int64_t g = g_begin;
     int tp = 0;
-    for (; g + 2 <= g_end; g += 2, tp ^= 1) s3_tile<2>(a, lds, tbl, tblh, cx, ln, st, w, ursrc, n0, tp, n_chunks);
-    if (g < g_end) s3_tile<1>(a, lds, tbl, tblh, cx, ln, st, w, ursrc, n0, tp, n_chunks);
+    for (; g + 2 <= g_end; g += 2, tp ^= 1) s3_tile<2>(a, lds, tbl, tblh, cx, ln, a_rd1, st, u, f, ursrc, n0, tp, n_chunks);
+    if (g < g_end) s3_tile<1>(a, lds, tbl, tblh, cx, ln, a_rd1, st, u, f, ursrc, n0, tp, n_chunks);
 }
+#undef WS3_PRODUCT2
+#undef WS3_PRODUCT1
+#undef WS3_ULD
+#undef WS3_RD
+#undef WS3_MF
 
 }  // namespace wino
 
