@@ -1,9 +1,12 @@
-/* xvec_train.h -- C ABI of the training-mode TDNN layer in libxvec_hip.so.
+/* xvec_train.h -- C ABI of a training step in libxvec_hip.so.
  *
  * One frame-level layer of the reference (tdnn_layer.py:26-41) as its training loop runs it (main.py:97-101 under
- * model.train()): context gather, Linear, ReLU and BatchNorm1d on the BATCH statistics, forward and backward.  The five
- * frame-level layers are 99.7 % of a training step's arithmetic; pooling, the segment layers, the loss and the optimizer
- * stay on torch ops for now (xvector_amd.train).
+ * model.train()): context gather, Linear, ReLU and BatchNorm1d on the BATCH statistics, forward and backward
+ * (xvec_tdnn_train_*, csrc/tdnn_train.hip).  The five frame-level layers are 99.7 % of a training step's arithmetic.  The
+ * tail of the step -- statistics pooling, the three segment-level Linear layers, the cross-entropy loss -- forward and
+ * backward, and the Adam update (xvec_train_tail_*, xvec_adam_step, csrc/train_tail.hip): 0.3 % of the arithmetic, but
+ * several passes over the layer-5 output and a string of small launches when left to torch ops.  xvector_amd.train uses
+ * the tail calls with XVectorTrainer(model, tail="hip").
  *
  * Conventions as xvec_plda.h: stateless (no handle), DEVICE pointers unless the name ends in _host, row-major, fp32,
  * asynchronous on the caller's stream, no allocation (the caller passes a workspace of the queried size), return codes
@@ -62,6 +65,48 @@ int xvec_tdnn_train_backward(const float* dy, const float* x, const float* z, in
                              const float* gamma, const float* batch_mean, const float* batch_var, float eps, float* dx,
                              float* dW, float* dbias, float* dgamma, float* dbeta, void* workspace,
                              size_t workspace_bytes, xvec_stream stream);
+
+/* ---- the tail of the step.  C = layer-5 width, Tp = pooled frames (>= 2), H = x-vector size, K = classes; B <= 65535.
+ *
+ * Scratch of xvec_train_tail_forward and xvec_train_tail_backward, one size for both (0 for arguments they would refuse). */
+size_t xvec_train_tail_workspace_bytes(int32_t B, int32_t Tp, int32_t C, int32_t H, int32_t K);
+
+/*   pooled [B, 2C] = (mean over Tp, UNBIASED std over Tp) per utterance and channel, in one pass over y5 [B, Tp, C] as sums
+ *                    of deviations about the utterance's first frame: it survives mean^2 >> var, and a channel that is
+ *                    constant over the utterance has an std of exactly 0
+ *   a6 [B, H]      = ReLU(pooled W6^T + b6)        W6 [H, 2C]   (the reduction split into slices, summed in slice order)
+ *   a7 [B, H]      = ReLU(a6 W7^T + b7)            W7 [H, H]
+ *   logits [B, K]  = a7 Wo^T + bo                  Wo [K, H]
+ *   loss [1]       = mean over the batch, in index order, of logsumexp(logits_b) - logits_b[labels_b]
+ * labels: int64 [B] on the device.  A label outside [0, K) makes that row's loss, and so the loss, NaN; nothing is read or
+ * written through it.  All five outputs are what the backward needs saved. */
+int xvec_train_tail_forward(const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, const float* b6, int32_t H,
+                            const float* W7, const float* b7, const float* Wo, const float* bo, int32_t K,
+                            const int64_t* labels, float* pooled, float* a6, float* a7, float* logits, float* loss,
+                            void* workspace, size_t workspace_bytes, xvec_stream stream);
+
+/* dloss [1] is a DEVICE scalar (the incoming gradient of the loss).
+ *   dlogits = dloss (softmax(logits) - onehot(labels)) / B
+ *   dWo = dlogits^T a7, dbo = column sums of dlogits;   dz7 = [a7 > 0] dlogits Wo
+ *   dW7 = dz7^T a6,     db7 = column sums of dz7;       dz6 = [a6 > 0] dz7 W7
+ *   dW6 = dz6^T pooled, db6 = column sums of dz6;       (dmean, dstd) = dz6 W6
+ *   dy5[b, t, c] = dmean[b, c] / Tp + dstd[b, c] (y5[b, t, c] - mean[b, c]) / ((Tp - 1) std[b, c]),
+ *                  the second term 0 where std == 0 (what torch's std backward does).  Written once.  dy5 may be NULL. */
+int xvec_train_tail_backward(const float* dloss, const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, int32_t H,
+                             const float* W7, const float* Wo, int32_t K, const int64_t* labels, const float* pooled,
+                             const float* a6, const float* a7, const float* logits, float* dy5, float* dW6, float* db6,
+                             float* dW7, float* db7, float* dWo, float* dbo, void* workspace, size_t workspace_bytes,
+                             xvec_stream stream);
+
+/* torch.optim.Adam with its defaults (no amsgrad, no weight decay, not maximize) on n_tensors tensors, step count t >= 1:
+ *   m = beta1 m + (1 - beta1) g,   v = beta2 v + (1 - beta2) g^2,
+ *   p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ * The four tables are HOST arrays of n_tensors DEVICE pointers, lengths_host their element counts.  The two bias
+ * corrections are computed in double on the host; one launch updates up to 32 tensors (the table travels in the kernel's
+ * argument block), more are chunked.  Any length and any 4-byte aligned base work. */
+int xvec_adam_step(float* const* params_host, const float* const* grads_host, float* const* exp_avg_host,
+                   float* const* exp_avg_sq_host, const int64_t* lengths_host, int32_t n_tensors, double lr, double beta1,
+                   double beta2, double eps, int64_t t, xvec_stream stream);
 
 #ifdef __cplusplus
 }

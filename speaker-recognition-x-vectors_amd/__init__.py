@@ -9,7 +9,7 @@ from . import synth  # noqa: F401  (numpy only)
 __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontEnd", "PldaScorer", "hip", "extract",
            "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject", "evaluate", "TrialList", "TrialResult",
            "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan",
-           "train", "XVectorTrainer", "tdnn_layer_train"]
+           "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam"]
 
 
 def __getattr__(name):
@@ -32,7 +32,7 @@ def __getattr__(name):
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
-    if name in ("XVectorTrainer", "tdnn_layer_train"):
+    if name in ("XVectorTrainer", "tdnn_layer_train", "DeviceAdam"):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train"):

@@ -28,6 +28,9 @@ struct ErrorChannel {
     const char* c_str() const { return text; }
 };
 
+// The channel behind xvec_train_last_error(): defined in tdnn_train.hip, shared with train_tail.hip (one header, one channel).
+ErrorChannel& train_error_channel();
+
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 inline int workspace_ok(size_t have, size_t need, ErrorChannel& err) {

@@ -572,6 +572,9 @@ GemmArgs gemm_args(const Shape& s) {
 dim3 col_grid(const Shape& s) { return dim3((s.Cout + 63) / 64, s.chunks); }
 
 }  // namespace
+
+ErrorChannel& train_error_channel() { return g_terr; }
+
 }  // namespace xvec
 
 using namespace xvec;

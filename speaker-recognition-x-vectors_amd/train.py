@@ -2,11 +2,12 @@
 
 The five frame-level layers -- 99.7 % of a step's arithmetic -- run forward AND backward in HIP (include/xvec_train.h,
 csrc/tdnn_train.hip): `tdnn_layer_train` is a torch.autograd.Function over the two C-ABI calls.  Statistics pooling, the three
-segment-level Linear layers, the loss and Adam ride on torch ops on the same stream for now (the next
-row).  Everything is fp32, the reference's own arithmetic.  There is no fallback: a CPU tensor, dropout or a reduced
-precision raise.
+segment-level Linear layers, the loss and Adam ride on torch ops on the same stream by default; with `tail="hip"` they run
+in HIP too (csrc/train_tail.hip): pooling through loss as ONE autograd.Function over xvec_train_tail_forward / _backward, the
+optimizer as `DeviceAdam` over xvec_adam_step.  Everything is fp32, the reference's own arithmetic.
+There is no fallback: a CPU tensor, dropout or a reduced precision raise.
 
-    trainer = XVectorTrainer(model)                 # an XVectorModel on a HIP device
+    trainer = XVectorTrainer(model)                 # an XVectorModel on a HIP device; tail="hip": the whole step in HIP
     for batch in loader:                            # the reference's (samples, labels, ids)
         loss = trainer.step(batch)
     trainer.save_checkpoint("last.ckpt")            # XVectorModel.load_from_checkpoint reads it back
@@ -94,6 +95,149 @@ class _TdnnTrain(torch.autograd.Function):
         return dx, dW, db, dgamma, dbeta, None, None
 
 
+def _tail_workspace(device, B, tp, c, h, k):
+    need = int(_hip.lib.xvec_train_tail_workspace_bytes(B, tp, c, h, k))
+    if need == 0:
+        raise _hip.XvecError(_hip.ERR_ARG, _hip.lib.xvec_train_last_error().decode())
+    key = (device.index, _stream_ptr(device))
+    ws = _workspaces[key] = _byte_workspace(need, device, _workspaces.get(key))
+    return ws
+
+
+class _TailTrain(torch.autograd.Function):
+    """loss, logits = f(h5, W6, b6, W7, b7, Wo, bo, labels): xvec_train_tail_forward / _backward.  Saved for the backward:
+    h5, the three weights, labels, and the call's own pooled, a6, a7 and logits.  logits is not differentiable (the loss is
+    the only way into the graph); the incoming gradient of the loss stays on the device."""
+
+    @staticmethod
+    def forward(ctx, h5, W6, b6, W7, b7, Wo, bo, labels):
+        B, tp, c = h5.shape
+        h, k = W6.shape[0], Wo.shape[0]
+        dev = h5.device
+        W6, b6, W7, b7, Wo, bo = (t.detach().contiguous() for t in (W6, b6, W7, b7, Wo, bo))
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+        pooled, a6, a7, logits, loss = new(B, 2 * c), new(B, h), new(B, h), new(B, k), new()
+        with torch.cuda.device(dev):
+            ws = _tail_workspace(dev, B, tp, c, h, k)
+            _check(_hip.lib.xvec_train_tail_forward(
+                h5.data_ptr(), B, tp, c, W6.data_ptr(), b6.data_ptr(), h, W7.data_ptr(), b7.data_ptr(), Wo.data_ptr(),
+                bo.data_ptr(), k, labels.data_ptr(), pooled.data_ptr(), a6.data_ptr(), a7.data_ptr(), logits.data_ptr(),
+                loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+        ctx.save_for_backward(h5, W6, W7, Wo, labels, pooled, a6, a7, logits)
+        ctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, dloss, _dlogits):
+        h5, W6, W7, Wo, labels, pooled, a6, a7, logits = ctx.saved_tensors
+        B, tp, c = h5.shape
+        h, k = W6.shape[0], Wo.shape[0]
+        dev = h5.device
+        dloss = dloss.to(device=dev, dtype=torch.float32).contiguous()
+        dy5 = torch.empty_like(h5) if ctx.needs_input_grad[0] else None
+        dW6, dW7, dWo = torch.empty_like(W6), torch.empty_like(W7), torch.empty_like(Wo)
+        db6, db7 = (torch.empty(h, dtype=torch.float32, device=dev) for _ in range(2))
+        dbo = torch.empty(k, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws = _tail_workspace(dev, B, tp, c, h, k)
+            _check(_hip.lib.xvec_train_tail_backward(
+                dloss.data_ptr(), h5.data_ptr(), B, tp, c, W6.data_ptr(), h, W7.data_ptr(), Wo.data_ptr(), k, labels.data_ptr(),
+                pooled.data_ptr(), a6.data_ptr(), a7.data_ptr(), logits.data_ptr(), None if dy5 is None else dy5.data_ptr(),
+                dW6.data_ptr(), db6.data_ptr(), dW7.data_ptr(), db7.data_ptr(), dWo.data_ptr(), dbo.data_ptr(), ws.data_ptr(),
+                ws.numel(), _stream_ptr(dev)))
+        return dy5, dW6, db6, dW7, db7, dWo, dbo, None
+
+
+class DeviceAdam:
+    """torch.optim.Adam with its defaults (amsgrad=False, weight_decay=0, not maximize) as ONE xvec_adam_step call per step
+    (one launch per 32 tensors).  `state_dict()` / `load_state_dict()` use torch.optim.Adam's own layout -- state[i] = {step,
+    exp_avg, exp_avg_sq} plus param_groups -- so a run can switch optimizer either way.  Parameters whose .grad is None are
+    skipped, as torch skips them.  No fallback: `step()` raises on a parameter that is not fp32, not on a HIP device or not
+    contiguous (checked where the pointers are taken: parameters may move between construction and the first step)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8):
+        self.params = list(params)
+        if not self.params:
+            raise ValueError("DeviceAdam: no parameters")
+        if not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0) or lr < 0.0 or eps < 0.0:
+            raise ValueError(f"DeviceAdam: lr = {lr}, betas = {betas}, eps = {eps}")
+        # the group's keys and defaults are torch.optim.Adam's own, whatever this torch's Adam carries (it holds no state
+        # before its first step: this one only lends its parameter group, so that state_dict() loads into a real one)
+        group = dict(torch.optim.Adam(self.params, lr=lr, betas=tuple(betas), eps=eps).param_groups[0])
+        group["params"] = self.params
+        self.param_groups = [group]
+        self.state = {}                 # parameter index -> {"step": int, "exp_avg", "exp_avg_sq"}, from its first step on
+
+    def zero_grad(self, set_to_none=True):
+        for p in self.params:
+            if p.grad is None:
+                continue
+            if set_to_none:
+                p.grad = None
+            else:
+                p.grad.detach_().zero_()
+
+    def _refuse_what_the_kernel_cannot_update(self):
+        for i, p in enumerate(self.params):
+            if p.dtype != torch.float32:
+                raise RuntimeError(f"DeviceAdam: parameter {i} is {p.dtype}; the update runs in fp32 only")
+            if p.device.type != "cuda":
+                raise RuntimeError(f"DeviceAdam: parameter {i} is on {p.device}; it runs on a HIP device only (no CPU path)")
+            if not p.is_contiguous():
+                raise RuntimeError(f"DeviceAdam: parameter {i} is not contiguous")
+
+    @torch.no_grad()
+    def step(self):
+        self._refuse_what_the_kernel_cannot_update()
+        g = self.param_groups[0]
+        calls = {}                      # (device index, t) -> parameter indices
+        for i, p in enumerate(self.params):
+            if p.grad is None:
+                continue
+            if p.grad.dtype != torch.float32 or p.grad.device != p.device:
+                raise RuntimeError(f"DeviceAdam: the gradient of parameter {i} is {p.grad.dtype} on {p.grad.device}")
+            st = self.state.get(i)
+            if st is None:
+                st = self.state[i] = {"step": 0, "exp_avg": torch.zeros_like(p, memory_format=torch.contiguous_format),
+                                      "exp_avg_sq": torch.zeros_like(p, memory_format=torch.contiguous_format)}
+            calls.setdefault((p.device.index, st["step"] + 1), []).append(i)
+        for (index, t), idx in calls.items():
+            dev = torch.device("cuda", index)
+            grads = [self.params[i].grad.contiguous() for i in idx]
+            table = lambda ts: (C.c_void_p * len(ts))(*[x.data_ptr() for x in ts])
+            lengths = (C.c_int64 * len(idx))(*[self.params[i].numel() for i in idx])
+            with torch.cuda.device(dev):
+                _check(_hip.lib.xvec_adam_step(
+                    table([self.params[i] for i in idx]), table(grads), table([self.state[i]["exp_avg"] for i in idx]),
+                    table([self.state[i]["exp_avg_sq"] for i in idx]), lengths, len(idx), float(g["lr"]), float(g["betas"][0]),
+                    float(g["betas"][1]), float(g["eps"]), int(t), _stream_ptr(dev)))
+            for i in idx:                  # counted once the update has been launched: a refused call leaves the state as it was
+                self.state[i]["step"] = t
+
+    def state_dict(self):
+        group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
+        group["params"] = list(range(len(self.params)))
+        state = {i: {"step": torch.tensor(float(st["step"])), "exp_avg": st["exp_avg"], "exp_avg_sq": st["exp_avg_sq"]}
+                 for i, st in sorted(self.state.items())}
+        return {"state": state, "param_groups": [group]}
+
+    def load_state_dict(self, sd):
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self.params):
+            raise ValueError("DeviceAdam.load_state_dict: one parameter group over the same parameters is expected")
+        g = groups[0]
+        if g.get("amsgrad") or g.get("weight_decay") or g.get("maximize"):
+            raise RuntimeError("DeviceAdam.load_state_dict: amsgrad, weight_decay and maximize are outside this build's scope")
+        self.param_groups[0].update({k: v for k, v in g.items() if k != "params"})
+        order = {pid: i for i, pid in enumerate(g["params"])}
+        self.state = {}
+        for pid, st in sd["state"].items():
+            i = order[pid]
+            p = self.params[i]
+            moment = lambda t: t.detach().to(device=p.device, dtype=torch.float32).contiguous().clone().view_as(p)
+            self.state[i] = {"step": int(st["step"]), "exp_avg": moment(st["exp_avg"]), "exp_avg_sq": moment(st["exp_avg_sq"])}
+
+
 def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer) -> torch.Tensor:
     """`layer(x)` as the reference computes it under model.train() (tdnn_layer.py:26-41): x[B, T, in] ->
     y[B, T - span, out] with a graph through the layer's own parameters, BatchNorm on the batch statistics, and the
@@ -130,16 +274,21 @@ class XVectorTrainer:
 
     _HPARAMS = ("x_vec_extract_layer", "batch_size", "learning_rate", "augmentations_per_sample", "data_folder_path")
 
-    def __init__(self, model: XVectorModel):
+    def __init__(self, model: XVectorModel, tail: str = "torch"):
+        if tail not in ("torch", "hip"):
+            raise ValueError(f"XVectorTrainer: tail = {tail!r}; 'torch' (pooling, segment layers, loss and Adam on torch ops) "
+                             f"or 'hip' (csrc/train_tail.hip)")
         if model.hparams["dropout_p"]:
             raise RuntimeError(f"XVectorTrainer: dropout_p = {model.hparams['dropout_p']} is outside this build's scope (only 0)")
         if model.precision not in ("fp32", "f32"):
             raise RuntimeError(f"XVectorTrainer: precision {model.precision!r}; training runs in fp32 only")
         self.model = model
+        self.tail = tail
         self.optimizer = None
 
     # ------------------------------------------------------------------ main.py:66-75 with a graph
-    def logits(self, x: torch.Tensor) -> torch.Tensor:
+    def _frames(self, x: torch.Tensor) -> torch.Tensor:
+        """The five frame-level layers: x[B, T, in] -> h5[B, T - 14, 1500]."""
         _require_gpu(x, "XVectorTrainer")
         if x.dim() != 3 or x.shape[2] != self.model.hparams["input_size"]:
             raise ValueError(f"expected x[B, T, {self.model.hparams['input_size']}], got {tuple(x.shape)}")
@@ -149,7 +298,12 @@ class XVectorTrainer:
         h = x.float()
         for layer in m.time_context_layers:
             h = tdnn_layer_train(h, layer)
-        # the tail, 0.3 % of the arithmetic, on torch ops (next row)
+        return h
+
+    def logits(self, x: torch.Tensor) -> torch.Tensor:
+        m = self.model
+        h = self._frames(x)
+        # the tail, 0.3 % of the arithmetic, on torch ops (tail="hip": training_step goes through _TailTrain instead)
         h = torch.cat((torch.mean(h, 1), torch.std(h, 1)), 1)
         h = F.relu(F.linear(h, m.segment_layer6.weight, m.segment_layer6.bias))
         h = F.relu(F.linear(h, m.segment_layer7.weight, m.segment_layer7.bias))
@@ -157,6 +311,13 @@ class XVectorTrainer:
 
     def training_step(self, batch, batch_index=0):
         samples, labels, ids = batch
+        if self.tail == "hip":
+            m = self.model
+            h5 = self._frames(samples.float())
+            loss, outputs = _TailTrain.apply(h5.contiguous(), m.segment_layer6.weight, m.segment_layer6.bias,
+                                             m.segment_layer7.weight, m.segment_layer7.bias, m.output.weight, m.output.bias,
+                                             labels.to(device=h5.device, dtype=torch.int64).contiguous())
+            return {"loss": loss, "train_preds": outputs, "train_labels": labels, "train_id": ids}
         outputs = self.logits(samples.float())
         loss = F.cross_entropy(outputs, labels.to(outputs.device))
         return {"loss": loss, "train_preds": outputs, "train_labels": labels, "train_id": ids}
@@ -175,6 +336,8 @@ class XVectorTrainer:
         return {"loss": loss, "val_preds": outputs, "val_labels": labels, "val_id": ids}
 
     def configure_optimizers(self):
+        if self.tail == "hip":
+            return DeviceAdam(self.model.parameters(), lr=self.model.learning_rate)
         return torch.optim.Adam(self.model.parameters(), lr=self.model.learning_rate)
 
     def step(self, batch) -> torch.Tensor:
