@@ -20,6 +20,30 @@
  * torch.cat(x_context, 2): column i * Cin + c multiplies channel c of tap i.  It is read as it is on every call (weights
  * change every step: there is no packed copy to keep in step).  B * T < 2^31 and n_ctx * max(Cin, Cout) < 2^31
  * (XVEC_ERR_TOO_LARGE otherwise).
+ *
+ * Ragged batches (the *_ragged calls; csrc/tdnn_train_ragged.hip, csrc/train_tail_ragged.hip).  The padded layout stays:
+ * x [B, T, Cin] with `lengths_dev`, a DEVICE int32 [B] of valid INPUT frames per utterance for that call (as xvec_stat_pool's
+ * lengths_dev).  Everything that depends on the lengths is computed on the device -- the valid row count, the row masks, the
+ * pooled counts: there is no read-back, no synchronisation and no allocation, and the workspace queries serve both forms
+ * unchanged.  The calls compute exactly what the valid frames alone would give.  For a layer with context span s and input
+ * lengths l[b], s + 1 <= l[b] <= T:
+ *   - utterance b has v[b] = l[b] - s valid output frames, the first v[b] of its T' rows; N = sum of v[b];
+ *   - forward: z, batch_mean, batch_var (biased) and y on the valid rows are those of the layer in training mode run on the N
+ *     valid rows as ONE BatchNorm batch; every invalid row of z and of y is written as exactly 0.0f.  (A caller that keeps
+ *     running statistics moves them with N: the unbiased factor is N / (N - 1).)  The next layer's lengths are l[b] - s;
+ *   - backward: dy on invalid rows is ignored, whatever it holds; dgamma, dbeta, dbias and dW sum over the valid rows only, the
+ *     1 / N of dz is the valid N, dz is 0 on invalid rows; dx[b, q] receives taps from valid rows only and is exactly 0 for
+ *     q >= l[b];
+ *   - no result depends on the padding of x or dy, NaN and Inf included: invalid rows are masked by SELECTION on the operands
+ *     (they are not loaded), never by a multiplication with 0;
+ *   - the tail pools over the v5[b] >= 2 valid frames of utterance b only (mean, unbiased std with divisor v5[b] - 1, a channel
+ *     that is constant over them has an std of exactly 0); dy5 on invalid rows is exactly 0; the loss stays the mean over the B
+ *     utterances.
+ * A length outside its range (a layer: [s + 1, T]; the tail: [2, Tp]) cannot be checked on the host.  Such an utterance
+ * contributes no rows: its rows of z, y, dz, dx and dy5 are 0, its pooled row is 0 (it still has a row of logits and a term in
+ * the loss); nothing is read or written out of bounds through it.  With no valid row at all batch_mean is 0 and batch_var is NaN (0 / 0).
+ * The calls without lengths are these with every length T; their results and code are unchanged by the masked form, which is a
+ * compile-time variant of the same kernels.  Two runs of one ragged call are bit-identical.
  */
 #ifndef XVEC_TRAIN_H
 #define XVEC_TRAIN_H
@@ -66,6 +90,17 @@ int xvec_tdnn_train_backward(const float* dy, const float* x, const float* z, in
                              float* dW, float* dbias, float* dgamma, float* dbeta, void* workspace,
                              size_t workspace_bytes, xvec_stream stream);
 
+/* The two calls above over a ragged batch (see the head of this file): the same arguments, plus the device lengths. */
+int xvec_tdnn_train_forward_ragged(const float* x, int32_t B, int32_t T, int32_t Cin, const float* W, const float* bias,
+                                   int32_t Cout, const int32_t* context_host, int32_t n_ctx, const float* gamma,
+                                   const float* beta, float eps, float* z, float* batch_mean, float* batch_var, float* y,
+                                   void* workspace, size_t workspace_bytes, xvec_stream stream, const int32_t* lengths_dev);
+int xvec_tdnn_train_backward_ragged(const float* dy, const float* x, const float* z, int32_t B, int32_t T, int32_t Cin,
+                                    const float* W, int32_t Cout, const int32_t* context_host, int32_t n_ctx,
+                                    const float* gamma, const float* batch_mean, const float* batch_var, float eps, float* dx,
+                                    float* dW, float* dbias, float* dgamma, float* dbeta, void* workspace,
+                                    size_t workspace_bytes, xvec_stream stream, const int32_t* lengths_dev);
+
 /* ---- the tail of the step.  C = layer-5 width, Tp = pooled frames (>= 2), H = x-vector size, K = classes; B <= 65535.
  *
  * Scratch of xvec_train_tail_forward and xvec_train_tail_backward, one size for both (0 for arguments they would refuse). */
@@ -97,6 +132,18 @@ int xvec_train_tail_backward(const float* dloss, const float* y5, int32_t B, int
                              const float* a6, const float* a7, const float* logits, float* dy5, float* dW6, float* db6,
                              float* dW7, float* db7, float* dWo, float* dbo, void* workspace, size_t workspace_bytes,
                              xvec_stream stream);
+
+/* The two tail calls over a ragged batch: `lengths_dev` holds the valid frames of y5 [B, Tp, C] per utterance, 2 <= v5[b] <= Tp.
+ * In the formulas above Tp becomes v5[b], the sums run over the first v5[b] frames, and dy5 is 0 on the others. */
+int xvec_train_tail_forward_ragged(const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, const float* b6, int32_t H,
+                                   const float* W7, const float* b7, const float* Wo, const float* bo, int32_t K,
+                                   const int64_t* labels, float* pooled, float* a6, float* a7, float* logits, float* loss,
+                                   void* workspace, size_t workspace_bytes, xvec_stream stream, const int32_t* lengths_dev);
+int xvec_train_tail_backward_ragged(const float* dloss, const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, int32_t H,
+                                    const float* W7, const float* Wo, int32_t K, const int64_t* labels, const float* pooled,
+                                    const float* a6, const float* a7, const float* logits, float* dy5, float* dW6, float* db6,
+                                    float* dW7, float* db7, float* dWo, float* dbo, void* workspace, size_t workspace_bytes,
+                                    xvec_stream stream, const int32_t* lengths_dev);
 
 /* torch.optim.Adam with its defaults (no amsgrad, no weight decay, not maximize) on n_tensors tensors, step count t >= 1:
  *   m = beta1 m + (1 - beta1) g,   v = beta2 v + (1 - beta2) g^2,

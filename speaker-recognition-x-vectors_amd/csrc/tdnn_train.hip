@@ -1,576 +1,11 @@
-// One TDNN layer in training mode, forward and backward, fp32 (reference tdnn_layer.py:26-41 under model.train()).
-// C ABI: include/xvec_train.h.  Three matrix products on v_mfma_f32_32x32x2_f32, all through ONE tiled kernel
-// (train_gemm_kernel) whose operand loaders differ per product:
-//   FWD  z  [N, Cout]          = ReLU(x_ctx [N, K] W^T + bias)     the context gather happens in the A loader
-//   DW   dW [Cout, K]          = dz^T x_ctx                        reduction over the N rows, split into slices: every
-//                                                                  slice writes its partial product to a slab, a second
-//                                                                  launch sums the slabs in slice order
-//   DX   dx [B*T, Cin]         = dz_ctx [B*T, taps*Cout] W_taps    row q of an utterance gathers dz rows q - off(tap),
-//                                                                  zero where that leaves the utterance
-// and column reductions over the rows (BatchNorm statistics, dbeta, dgamma, dbias) in 256-row chunks: one partial per
-// chunk and column, summed in chunk order by a second launch.  No atomics anywhere: results are bit-identical per call.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <cstdint>
-
-#include "../../include/xvec_hip.h"
-#include "../../include/xvec_train.h"
-#include "host_support.h"
-#include "tdnn_common.h"
+// One TDNN layer in training mode, forward and backward, fp32 (reference tdnn_layer.py:26-41 under model.train()): the calls
+// over full-length utterances.  C ABI: include/xvec_train.h.  Kernels and host code: tdnn_train_impl.h, here in the unmasked
+// instantiation; the length-masked calls are tdnn_train_ragged.hip.  This file also owns the training calls' error channel.
+#include "tdnn_train_impl.h"
 
 namespace xvec {
 namespace {
-
-constexpr int kMaxTaps = 8;
-constexpr int kBM = 128, kBN = 128, kBK = 16;   // block tile; 4 waves as 2 x 2, each 64 x 64 = 2 x 2 MFMA tiles of 32 x 32
-// LDS images are [k][row] with a row stride of 132 floats: the two lane halves of an MFMA operand read the k rows kk and
-// kk + 8, 8 * 132 = 32 banks apart (one conflict-free ds_read_b32); the transposing stores of the k-contiguous operands
-// (thread = 4 k of one row; a wave = 16 rows x 4 k-quads) land on (4 q + j) * 132 + row = 64 different banks.
-constexpr int kLD = 132;
-constexpr int kChunk = 256;                     // rows per partial of the column reductions
-constexpr int kDwMinRows = 256;                 // a dW slice is at least this many rows ...
-constexpr int kDwBlocks = 1024;                 // ... and slices x tiles aim at this many blocks (fixed: device-independent results)
-
-enum { OP_FWD = 0, OP_DW = 1, OP_DX = 2 };
-
-struct GemmArgs {
-    const float* a;      // FWD: x    DW: dz   DX: dz
-    const float* b;      // FWD: W    DW: x    DX: W
-    const float* bias;   // FWD
-    float* c;            // FWD: z    DW: slab (or dW itself with one slice)    DX: dx
-    int M, N, K;         // product dimensions; K is the whole reduction length
-    int k_per_slice;     // DW: rows per slice (a multiple of kBK); otherwise K
-    int tiles_m, tiles_n;
-    int T, Tp, Cin, Cout, Kw;   // Kw = taps * Cin, the row length of W
-    int off[kMaxTaps];          // context[i] - context[0]
-};
-
-// off[tap] without a dynamically indexed copy of the argument block (which would live in scratch)
-__device__ __forceinline__ int tap_off(const GemmArgs& g, int tap) {
-    int o = g.off[0];
-#pragma unroll
-    for (int i = 1; i < kMaxTaps; ++i) o = tap == i ? g.off[i] : o;
-    return o;
-}
-
-// (tap, c) + step along a [taps][width] axis
-__device__ __forceinline__ void advance(int& tap, int& c, int step, int width) {
-    c += step;
-    while (c >= width) {
-        c -= width;
-        ++tap;
-    }
-}
-
-template <int OP, bool VEC>
-__global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g) {
-    __shared__ __attribute__((aligned(16))) float sA[2][kBK][kLD];
-    __shared__ __attribute__((aligned(16))) float sB[2][kBK][kLD];
-    const int per_slice = g.tiles_m * g.tiles_n;
-    const int logical = xcd_remap(blockIdx.x, gridDim.x);       // the column tiles of one row tile share an XCD's L2
-    const int slice = logical / per_slice, tile = logical - slice * per_slice;
-    const int tm = tile / g.tiles_n, tn = tile - tm * g.tiles_n;
-    const int m0 = tm * kBM, n0 = tn * kBN;
-    const int kbeg = slice * g.k_per_slice;
-    const int kend = min(g.K, kbeg + g.k_per_slice);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wr = wave >> 1, wc = wave & 1, l31 = lane & 31, lh = lane >> 5;
-
-    // ---- loaders.  k-contiguous operands (FWD A, FWD B, DX A): pass i = row (tid >> 2) + 64 i, four k from (tid & 3) * 4.
-    // row-contiguous operands (DW A, DW B, DX B): pass i = k row (tid >> 5) + 8 i, four rows/columns from (tid & 31) * 4.
-    const int kc_row = tid >> 2, kc_k = (tid & 3) * 4;
-    const int mc_k = tid >> 5, mc_col = (tid & 31) * 4;
-    float ra[2][4], rb[2][4];
-
-    // per-thread state of the A operand
-    int a_base[2] = {0, 0}, a_q[2] = {0, 0};       // FWD: frame b*T + p      DX: b*Tp and q
-    bool a_ok[2] = {false, false};
-    int a_tap = 0, a_c = 0;                        // FWD / DX: (tap, channel) of k = kcur + kc_k
-    if constexpr (OP == OP_FWD) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m0 + kc_row + 64 * i;
-            a_ok[i] = m < g.M;
-            const int b = m / g.Tp;
-            a_base[i] = b * g.T + (m - b * g.Tp);
-        }
-        a_tap = kc_k / g.Cin;
-        a_c = kc_k - a_tap * g.Cin;
-    } else if constexpr (OP == OP_DX) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int m = m0 + kc_row + 64 * i;
-            a_ok[i] = m < g.M;
-            const int b = m / g.T;
-            a_base[i] = b * g.Tp;
-            a_q[i] = m - b * g.T;
-        }
-        a_tap = kc_k / g.Cout;
-        a_c = kc_k - a_tap * g.Cout;
-    }
-    // per-thread state of the B operand
-    int b_row[2] = {0, 0}, b_p[2] = {0, 0};        // DW: utterance b and frame p of row k     DX: (tap, co) of k
-    if constexpr (OP == OP_DW) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int r = kbeg + mc_k + 8 * i;
-            b_row[i] = r / g.Tp;
-            b_p[i] = r - b_row[i] * g.Tp;
-        }
-    } else if constexpr (OP == OP_DX) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int k = mc_k + 8 * i;
-            b_row[i] = k / g.Cout;
-            b_p[i] = k - b_row[i] * g.Cout;
-        }
-    }
-
-    auto load4 = [&](const float* p, float (&v)[4]) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    };
-
-    auto gload = [&](int kcur) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                ra[i][j] = 0.f;
-                rb[i][j] = 0.f;
-            }
-        // ---------------- A
-        if constexpr (OP == OP_FWD || OP == OP_DX) {
-            const int k = kcur + kc_k;
-            const int width = OP == OP_FWD ? g.Cin : g.Cout;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                if (!a_ok[i]) continue;
-                if constexpr (VEC) {
-                    if (k < kend) {
-                        const int o = tap_off(g, a_tap);
-                        if constexpr (OP == OP_FWD) {
-                            load4(g.a + (int64_t)(a_base[i] + o) * g.Cin + a_c, ra[i]);
-                        } else {
-                            const int p = a_q[i] - o;
-                            if (p >= 0 && p < g.Tp) load4(g.a + (int64_t)(a_base[i] + p) * g.Cout + a_c, ra[i]);
-                        }
-                    }
-                } else {
-                    int tj = a_tap, cj = a_c;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (k + j < kend) {
-                            const int o = tap_off(g, tj);
-                            if constexpr (OP == OP_FWD) {
-                                ra[i][j] = g.a[(int64_t)(a_base[i] + o) * g.Cin + cj];
-                            } else {
-                                const int p = a_q[i] - o;
-                                if (p >= 0 && p < g.Tp) ra[i][j] = g.a[(int64_t)(a_base[i] + p) * g.Cout + cj];
-                            }
-                        }
-                        advance(tj, cj, 1, width);
-                    }
-                }
-            }
-            advance(a_tap, a_c, kBK, width);
-        } else {                                   // DW: dz[k, m]
-            const int m = m0 + mc_col;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int k = kcur + mc_k + 8 * i;
-                if (k >= kend) continue;
-                const float* p = g.a + (int64_t)k * g.Cout + m;
-                if constexpr (VEC) {
-                    if (m < g.M) load4(p, ra[i]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (m + j < g.M) ra[i][j] = p[j];
-                }
-            }
-        }
-        // ---------------- B
-        if constexpr (OP == OP_FWD) {              // W[n, k]
-            const int k = kcur + kc_k;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int n = n0 + kc_row + 64 * i;
-                if (n >= g.N) continue;
-                const float* p = g.b + (int64_t)n * g.Kw + k;
-                if constexpr (VEC) {
-                    if (k < kend) load4(p, rb[i]);
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        if (k + j < kend) rb[i][j] = p[j];
-                }
-            }
-        } else if constexpr (OP == OP_DW) {        // x_ctx[k, n]: frame (b, p + off(tap of n)), channel of n
-            const int n = n0 + mc_col;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int k = kcur + mc_k + 8 * i;
-                if (k < kend) {
-                    const int frame = b_row[i] * g.T + b_p[i];
-                    if constexpr (VEC) {
-                        if (n < g.N) {
-                            const int tap = n / g.Cin;
-                            load4(g.b + (int64_t)(frame + tap_off(g, tap)) * g.Cin + (n - tap * g.Cin), rb[i]);
-                        }
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (n + j < g.N) {
-                                const int tap = (n + j) / g.Cin;
-                                rb[i][j] = g.b[(int64_t)(frame + tap_off(g, tap)) * g.Cin + (n + j - tap * g.Cin)];
-                            }
-                    }
-                }
-                advance(b_row[i], b_p[i], kBK, g.Tp);
-            }
-        } else {                                   // DX: W[co, tap * Cin + n] at k = tap * Cout + co
-            const int n = n0 + mc_col;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int k = kcur + mc_k + 8 * i;
-                if (k < kend) {
-                    const float* p = g.b + (int64_t)b_p[i] * g.Kw + b_row[i] * g.Cin + n;
-                    if constexpr (VEC) {
-                        if (n < g.N) load4(p, rb[i]);
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j)
-                            if (n + j < g.N) rb[i][j] = p[j];
-                    }
-                }
-                advance(b_row[i], b_p[i], kBK, g.Cout);
-            }
-        }
-    };
-
-    auto lstore = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            if constexpr (OP == OP_DW) {
-                *reinterpret_cast<f32x4*>(&sA[buf][mc_k + 8 * i][mc_col]) = f32x4{ra[i][0], ra[i][1], ra[i][2], ra[i][3]};
-            } else {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sA[buf][kc_k + j][kc_row + 64 * i] = ra[i][j];
-            }
-            if constexpr (OP == OP_FWD) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) sB[buf][kc_k + j][kc_row + 64 * i] = rb[i][j];
-            } else {
-                *reinterpret_cast<f32x4*>(&sB[buf][mc_k + 8 * i][mc_col]) = f32x4{rb[i][0], rb[i][1], rb[i][2], rb[i][3]};
-            }
-        }
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int n_it = kend > kbeg ? (kend - kbeg + kBK - 1) / kBK : 0;
-    if (n_it > 0) {
-        gload(kbeg);
-        lstore(0);
-        __syncthreads();
-    }
-    for (int it = 0; it < n_it; ++it) {
-        const int buf = it & 1;
-        if (it + 1 < n_it) gload(kbeg + (it + 1) * kBK);     // in flight while this chunk's 32 MFMAs per wave run
-#pragma unroll
-        for (int kk = 0; kk < kBK / 2; ++kk) {
-            const int k = kk + 8 * lh;
-            float a[2], b[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                a[i] = sA[buf][k][wr * 64 + i * 32 + l31];
-                b[i] = sB[buf][k][wc * 64 + i * 32 + l31];
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        if (it + 1 < n_it) lstore(buf ^ 1);
-        __syncthreads();
-    }
-
-    // C/D of the 32 x 32 MFMA: column lane & 31, row (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
-    const int ldc = g.N;
-    float* out = g.c + (OP == OP_DW ? (size_t)slice * g.M * g.N : (size_t)0);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int col = n0 + wc * 64 + j * 32 + l31;
-        if (col >= g.N) continue;
-        float bias = 0.f;
-        if constexpr (OP == OP_FWD) bias = g.bias[col];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-                if (row >= g.M) continue;
-                float v = acc[i][j][r];
-                if constexpr (OP == OP_FWD) v = fmaxf(v + bias, 0.f);
-                out[(size_t)row * ldc + col] = v;
-            }
-    }
-}
-
-// out[i] = sum over slices, in slice order, of slab[s][i]
-__global__ __launch_bounds__(256) void train_slab_reduce_kernel(const float* __restrict__ slab, int slices, size_t count,
-                                                                float* __restrict__ out) {
-    const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
-    if (i >= count) return;
-    float s = 0.f;
-    for (int sl = 0; sl < slices; ++sl) s += slab[sl * count + i];
-    out[i] = s;
-}
-
-// ---------------------------------------------------------------- column reductions over the rows
-// A block takes 64 columns of one 256-row chunk: thread (column tid & 63, row group tid >> 6) walks the rows
-// group, group + 4, ... of the chunk; the four groups are then added in group order.
-struct ColCtx {
-    int col, grp, r0, r1;
-    bool ok;
-};
-__device__ __forceinline__ ColCtx col_ctx(int N, int Cout) {
-    ColCtx c;
-    c.col = blockIdx.x * 64 + (threadIdx.x & 63);
-    c.grp = threadIdx.x >> 6;
-    c.r0 = blockIdx.y * kChunk;
-    c.r1 = min(N, c.r0 + kChunk);
-    c.ok = c.col < Cout;
-    return c;
-}
-// sum of the four row groups' values of every column, in group order, in all four threads of the column
-__device__ __forceinline__ float group_sum(float v, float (*sh)[64]) {
-    __syncthreads();                     // (the previous use of sh is over)
-    sh[threadIdx.x >> 6][threadIdx.x & 63] = v;
-    __syncthreads();
-    const int c = threadIdx.x & 63;
-    return ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
-}
-
-// chunk mean and sum of squared deviations about it: part[chunk][0][col] = mean, part[chunk][1][col] = M2.  The mean is
-// formed about a pivot (the chunk's first row), the deviations in a second pass over the chunk (it sits in the cache).
-__global__ __launch_bounds__(256) void train_stats_kernel(const float* __restrict__ z, int N, int Cout, float* __restrict__ part) {
-    __shared__ float sh[4][64];
-    const ColCtx c = col_ctx(N, Cout);
-    const float cnt = (float)(c.r1 - c.r0);
-    float pivot = 0.f, s = 0.f;
-    if (c.ok) {
-        pivot = z[(size_t)c.r0 * Cout + c.col];
-        for (int r = c.r0 + c.grp; r < c.r1; r += 4) s += z[(size_t)r * Cout + c.col] - pivot;
-    }
-    const float mean = pivot + group_sum(s, sh) / cnt;
-    float q = 0.f;
-    if (c.ok)
-        for (int r = c.r0 + c.grp; r < c.r1; r += 4) {
-            const float d = z[(size_t)r * Cout + c.col] - mean;
-            q = fmaf(d, d, q);
-        }
-    q = group_sum(q, sh);
-    if (c.ok && c.grp == 0) {
-        part[((size_t)blockIdx.y * 2 + 0) * Cout + c.col] = mean;
-        part[((size_t)blockIdx.y * 2 + 1) * Cout + c.col] = q;
-    }
-}
-
-// the chunks' (mean, M2) merged in chunk order (Chan et al.): batch mean and BIASED variance
-__global__ __launch_bounds__(64) void train_stats_merge_kernel(const float* __restrict__ part, int chunks, int N, int Cout,
-                                                               float* __restrict__ mean_out, float* __restrict__ var_out) {
-    const int col = blockIdx.x * 64 + threadIdx.x;
-    if (col >= Cout) return;
-    float mean = part[col], m2 = part[Cout + col], n = (float)min(N, kChunk);
-    for (int ch = 1; ch < chunks; ++ch) {
-        const float nc = (float)(min(N, (ch + 1) * kChunk) - ch * kChunk);
-        const float mc = part[((size_t)ch * 2 + 0) * Cout + col], qc = part[((size_t)ch * 2 + 1) * Cout + col];
-        const float tot = n + nc, delta = mc - mean;
-        mean += delta * (nc / tot);
-        m2 += qc + delta * delta * (n * nc / tot);
-        n = tot;
-    }
-    mean_out[col] = mean;
-    var_out[col] = m2 / (float)N;
-}
-
-__global__ __launch_bounds__(256) void train_norm_kernel(const float* __restrict__ z, int N, int Cout,
-                                                         const float* __restrict__ mean, const float* __restrict__ var,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                         float eps, float* __restrict__ y) {
-    const ColCtx c = col_ctx(N, Cout);
-    if (!c.ok) return;
-    const float mu = mean[c.col], scale = gamma[c.col] * (1.0f / sqrtf(var[c.col] + eps)), shift = beta[c.col];
-    for (int r = c.r0 + c.grp; r < c.r1; r += 4) {
-        const size_t i = (size_t)r * Cout + c.col;
-        y[i] = fmaf(z[i] - mu, scale, shift);
-    }
-}
-
-// part[chunk][0][col] = sum of dy, part[chunk][1][col] = sum of dy x^ over the chunk's rows
-__global__ __launch_bounds__(256) void train_bn_sums_kernel(const float* __restrict__ dy, const float* __restrict__ z, int N,
-                                                            int Cout, const float* __restrict__ mean,
-                                                            const float* __restrict__ var, float eps, float* __restrict__ part) {
-    __shared__ float sh[4][64];
-    const ColCtx c = col_ctx(N, Cout);
-    float s1 = 0.f, s2 = 0.f;
-    if (c.ok) {
-        const float mu = mean[c.col], invstd = 1.0f / sqrtf(var[c.col] + eps);
-        for (int r = c.r0 + c.grp; r < c.r1; r += 4) {
-            const size_t i = (size_t)r * Cout + c.col;
-            const float d = dy[i];
-            s1 += d;
-            s2 = fmaf(d, (z[i] - mu) * invstd, s2);
-        }
-    }
-    s1 = group_sum(s1, sh);
-    s2 = group_sum(s2, sh);
-    if (c.ok && c.grp == 0) {
-        part[((size_t)blockIdx.y * 2 + 0) * Cout + c.col] = s1;
-        part[((size_t)blockIdx.y * 2 + 1) * Cout + c.col] = s2;
-    }
-}
-
-// out_p[col] = sum over chunks, in chunk order, of part[chunk][p][col], p < planes (blockIdx.y = p)
-__global__ __launch_bounds__(64) void train_col_reduce_kernel(const float* __restrict__ part, int chunks, int planes, int Cout,
-                                                              float* __restrict__ out0, float* __restrict__ out1) {
-    const int col = blockIdx.x * 64 + threadIdx.x, p = blockIdx.y;
-    if (col >= Cout) return;
-    float s = 0.f;
-    for (int ch = 0; ch < chunks; ++ch) s += part[((size_t)ch * planes + p) * Cout + col];
-    (p == 0 ? out0 : out1)[col] = s;
-}
-
-// dz = [z > 0] gamma invstd (dy - dbeta / N - x^ dgamma / N), or [z > 0] dy without BatchNorm; part[chunk][col] = sum of dz
-// over the chunk's rows.  The mask is a SELECT: a channel that is never on gets exact zeros.
-__global__ __launch_bounds__(256) void train_dz_kernel(const float* __restrict__ dy, const float* __restrict__ z, int N, int Cout,
-                                                       const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                       const float* __restrict__ var, const float* __restrict__ dgamma,
-                                                       const float* __restrict__ dbeta, float eps, float* __restrict__ dz,
-                                                       float* __restrict__ part) {
-    __shared__ float sh[4][64];
-    const ColCtx c = col_ctx(N, Cout);
-    float s = 0.f;
-    if (c.ok) {
-        float mu = 0.f, invstd = 1.f, scale = 1.f, kb = 0.f, kg = 0.f;
-        if (gamma) {
-            const float inv_n = 1.0f / (float)N;
-            mu = mean[c.col];
-            invstd = 1.0f / sqrtf(var[c.col] + eps);
-            scale = gamma[c.col] * invstd;
-            kb = dbeta[c.col] * inv_n;
-            kg = dgamma[c.col] * inv_n;
-        }
-        for (int r = c.r0 + c.grp; r < c.r1; r += 4) {
-            const size_t i = (size_t)r * Cout + c.col;
-            const float zv = z[i];
-            float v = dy[i];
-            if (gamma) v = scale * ((v - kb) - (zv - mu) * invstd * kg);
-            v = zv > 0.f ? v : 0.f;
-            dz[i] = v;
-            s += v;
-        }
-    }
-    s = group_sum(s, sh);
-    if (c.ok && c.grp == 0) part[(size_t)blockIdx.y * Cout + c.col] = s;
-}
-
-// ---------------------------------------------------------------- host side
-
 thread_local ErrorChannel g_terr;
-
-struct Shape {
-    int B, T, Cin, Cout, taps, span, Tp, N, Kw, chunks;
-    int off[kMaxTaps];
-};
-
-struct Plan {
-    int dw_tiles_m, dw_tiles_n, slices, rows_per_slice;
-    float* part;       // column-reduction partials, 2 planes
-    float* dz;         // [N, Cout]
-    float* slab;       // dW partial products, one [Cout, Kw] per slice (slices > 1)
-    size_t total;
-};
-
-// XVEC_OK, or the code with the message set
-int make_shape(int B, int T, int Cin, int Cout, const int32_t* context_host, int n_ctx, Shape& s) {
-    if (!context_host) return g_terr.fail(XVEC_ERR_ARG, "null pointer: context_host");
-    if (B < 1 || T < 1 || Cin < 1 || Cout < 1)
-        return g_terr.fail(XVEC_ERR_ARG, "B = %d, T = %d, Cin = %d and Cout = %d must be >= 1", B, T, Cin, Cout);
-    if (n_ctx < 1 || n_ctx > kMaxTaps) return g_terr.fail(XVEC_ERR_ARG, "n_ctx = %d: 1 .. %d context offsets", n_ctx, kMaxTaps);
-    for (int i = 1; i < n_ctx; ++i)
-        if (context_host[i] <= context_host[i - 1])
-            return g_terr.fail(XVEC_ERR_ARG, "context is not strictly increasing at entry %d (%d after %d)", i, context_host[i],
-                               context_host[i - 1]);
-    const int64_t span = (int64_t)context_host[n_ctx - 1] - context_host[0];
-    if (T <= span) return g_terr.fail(XVEC_ERR_ARG, "T = %d is not longer than the context span %lld", T, (long long)span);
-    if ((int64_t)B * T > 0x7fffffff)
-        return g_terr.fail(XVEC_ERR_TOO_LARGE, "B * T = %lld frames: row indices are int32", (long long)B * T);
-    if ((int64_t)n_ctx * std::max(Cin, Cout) > 0x7fffffff)
-        return g_terr.fail(XVEC_ERR_TOO_LARGE, "n_ctx * max(Cin, Cout) = %lld: column indices are int32",
-                           (long long)n_ctx * std::max(Cin, Cout));
-    s.B = B; s.T = T; s.Cin = Cin; s.Cout = Cout; s.taps = n_ctx;
-    s.span = (int)span;
-    s.Tp = T - s.span;
-    s.N = B * s.Tp;
-    s.Kw = n_ctx * Cin;
-    s.chunks = (s.N + kChunk - 1) / kChunk;
-    if (s.chunks > 65535) return g_terr.fail(XVEC_ERR_TOO_LARGE, "N = %d rows: more than 65535 chunks of %d", s.N, kChunk);
-    for (int i = 0; i < kMaxTaps; ++i) s.off[i] = i < n_ctx ? context_host[i] - context_host[0] : 0;
-    return XVEC_OK;
-}
-
-Plan make_plan(void* ws, const Shape& s) {
-    Plan p{};
-    p.dw_tiles_m = (s.Cout + kBM - 1) / kBM;
-    p.dw_tiles_n = (s.Kw + kBN - 1) / kBN;
-    const int64_t tiles = (int64_t)p.dw_tiles_m * p.dw_tiles_n;
-    const int64_t by_blocks = std::max<int64_t>(1, kDwBlocks / tiles);
-    const int64_t by_rows = std::max<int64_t>(1, (s.N + kDwMinRows - 1) / kDwMinRows);
-    p.slices = (int)std::min(by_blocks, by_rows);
-    p.rows_per_slice = ((s.N + p.slices - 1) / p.slices + kBK - 1) / kBK * kBK;
-    Carver c(ws);
-    p.part = c.take<float>((size_t)2 * s.chunks * s.Cout);
-    p.dz = c.take<float>((size_t)s.N * s.Cout);
-    p.slab = c.take<float>(p.slices > 1 ? (size_t)p.slices * s.Cout * s.Kw : 0);
-    p.total = c.total();
-    return p;
-}
-
-int workspace_arg_ok(void* ws, size_t have, size_t need) {
-    if (!ws) return g_terr.fail(XVEC_ERR_ARG, "null pointer: workspace");
-    return have >= need ? XVEC_OK : g_terr.fail(XVEC_ERR_ARG, "workspace too small: %zu < %zu bytes", have, need);
-}
-
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
-template <int OP>
-int launch_gemm(const GemmArgs& g, int slices, bool vec, hipStream_t s, const char* what) {
-    const int64_t blocks = (int64_t)g.tiles_m * g.tiles_n * slices;
-    if (blocks > 0x7fffffff) return g_terr.fail(XVEC_ERR_TOO_LARGE, "%s: %lld blocks", what, (long long)blocks);
-    if (vec) train_gemm_kernel<OP, true><<<(unsigned)blocks, 256, 0, s>>>(g);
-    else train_gemm_kernel<OP, false><<<(unsigned)blocks, 256, 0, s>>>(g);
-    return g_terr.launch_ok(what);
-}
-
-GemmArgs gemm_args(const Shape& s) {
-    GemmArgs g{};
-    g.T = s.T; g.Tp = s.Tp; g.Cin = s.Cin; g.Cout = s.Cout; g.Kw = s.Kw;
-    for (int i = 0; i < kMaxTaps; ++i) g.off[i] = s.off[i];
-    return g;
-}
-
-dim3 col_grid(const Shape& s) { return dim3((s.Cout + 63) / 64, s.chunks); }
-
 }  // namespace
 
 ErrorChannel& train_error_channel() { return g_terr; }
@@ -590,85 +25,21 @@ size_t xvec_tdnn_train_workspace_bytes(int32_t B, int32_t T, int32_t Cin, int32_
     return make_plan(nullptr, s).total;
 }
 
-// Launches: the product (+ bias, ReLU) into z; with BatchNorm the chunk statistics, their merge, the normalisation.
 int xvec_tdnn_train_forward(const float* x, int32_t B, int32_t T, int32_t Cin, const float* W, const float* bias,
                             int32_t Cout, const int32_t* context_host, int32_t n_ctx, const float* gamma,
                             const float* beta, float eps, float* z, float* batch_mean, float* batch_var, float* y,
                             void* workspace, size_t workspace_bytes, xvec_stream stream) {
-    if (!x || !W || !bias || !z) return g_terr.fail(XVEC_ERR_ARG, "null pointer: x, W, bias and z are required");
-    if (gamma && (!beta || !batch_mean || !batch_var || !y))
-        return g_terr.fail(XVEC_ERR_ARG, "null pointer: with gamma, beta, batch_mean, batch_var and y are required");
-    Shape s;
-    int rc;
-    if ((rc = make_shape(B, T, Cin, Cout, context_host, n_ctx, s))) return rc;
-    const Plan p = make_plan(workspace, s);
-    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-
-    GemmArgs g = gemm_args(s);
-    g.a = x; g.b = W; g.bias = bias; g.c = z;
-    g.M = s.N; g.N = Cout; g.K = s.Kw; g.k_per_slice = s.Kw;
-    g.tiles_m = (g.M + kBM - 1) / kBM;
-    g.tiles_n = (g.N + kBN - 1) / kBN;
-    if ((rc = launch_gemm<OP_FWD>(g, 1, Cin % 4 == 0 && aligned16(x) && aligned16(W), st, "train_gemm_kernel (forward)"))) return rc;
-    if (!gamma) return XVEC_OK;
-    train_stats_kernel<<<col_grid(s), 256, 0, st>>>(z, s.N, Cout, p.part);
-    if ((rc = g_terr.launch_ok("train_stats_kernel"))) return rc;
-    train_stats_merge_kernel<<<(Cout + 63) / 64, 64, 0, st>>>(p.part, s.chunks, s.N, Cout, batch_mean, batch_var);
-    if ((rc = g_terr.launch_ok("train_stats_merge_kernel"))) return rc;
-    train_norm_kernel<<<col_grid(s), 256, 0, st>>>(z, s.N, Cout, batch_mean, batch_var, gamma, beta, eps, y);
-    return g_terr.launch_ok("train_norm_kernel");
+    return train_forward<false>(x, B, T, Cin, W, bias, Cout, context_host, n_ctx, gamma, beta, eps, z, batch_mean, batch_var, y,
+                                nullptr, workspace, workspace_bytes, stream);
 }
 
-// Launches: with BatchNorm the chunk sums of dy and dy x^ and their reduction (dbeta, dgamma); dz and its chunk sums, their
-// reduction (dbias); the dW product over row slices and, with more than one slice, the slab sum; the dx product.
 int xvec_tdnn_train_backward(const float* dy, const float* x, const float* z, int32_t B, int32_t T, int32_t Cin,
                              const float* W, int32_t Cout, const int32_t* context_host, int32_t n_ctx,
                              const float* gamma, const float* batch_mean, const float* batch_var, float eps, float* dx,
                              float* dW, float* dbias, float* dgamma, float* dbeta, void* workspace,
                              size_t workspace_bytes, xvec_stream stream) {
-    if (!dy || !x || !z || !W || !dW || !dbias)
-        return g_terr.fail(XVEC_ERR_ARG, "null pointer: dy, x, z, W, dW and dbias are required");
-    if (gamma && (!batch_mean || !batch_var || !dgamma || !dbeta))
-        return g_terr.fail(XVEC_ERR_ARG, "null pointer: with gamma, batch_mean, batch_var, dgamma and dbeta are required");
-    Shape s;
-    int rc;
-    if ((rc = make_shape(B, T, Cin, Cout, context_host, n_ctx, s))) return rc;
-    const Plan p = make_plan(workspace, s);
-    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total))) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 cols((Cout + 63) / 64);
-
-    if (gamma) {
-        train_bn_sums_kernel<<<col_grid(s), 256, 0, st>>>(dy, z, s.N, Cout, batch_mean, batch_var, eps, p.part);
-        if ((rc = g_terr.launch_ok("train_bn_sums_kernel"))) return rc;
-        train_col_reduce_kernel<<<dim3(cols.x, 2), 64, 0, st>>>(p.part, s.chunks, 2, Cout, dbeta, dgamma);
-        if ((rc = g_terr.launch_ok("train_col_reduce_kernel"))) return rc;
-    }
-    train_dz_kernel<<<col_grid(s), 256, 0, st>>>(dy, z, s.N, Cout, gamma, batch_mean, batch_var, dgamma, dbeta, eps, p.dz, p.part);
-    if ((rc = g_terr.launch_ok("train_dz_kernel"))) return rc;
-    train_col_reduce_kernel<<<dim3(cols.x, 1), 64, 0, st>>>(p.part, s.chunks, 1, Cout, dbias, nullptr);
-    if ((rc = g_terr.launch_ok("train_col_reduce_kernel"))) return rc;
-
-    const bool vec = Cin % 4 == 0 && Cout % 4 == 0 && aligned16(x) && aligned16(W);
-    GemmArgs g = gemm_args(s);
-    g.a = p.dz; g.b = x; g.c = p.slices > 1 ? p.slab : dW;
-    g.M = Cout; g.N = s.Kw; g.K = s.N; g.k_per_slice = p.rows_per_slice;
-    g.tiles_m = p.dw_tiles_m;
-    g.tiles_n = p.dw_tiles_n;
-    if ((rc = launch_gemm<OP_DW>(g, p.slices, vec, st, "train_gemm_kernel (dW)"))) return rc;
-    if (p.slices > 1) {
-        const size_t count = (size_t)Cout * s.Kw;
-        train_slab_reduce_kernel<<<(unsigned)((count + 255) / 256), 256, 0, st>>>(p.slab, p.slices, count, dW);
-        if ((rc = g_terr.launch_ok("train_slab_reduce_kernel"))) return rc;
-    }
-    if (!dx) return XVEC_OK;
-    g = gemm_args(s);
-    g.a = p.dz; g.b = W; g.c = dx;
-    g.M = B * T; g.N = Cin; g.K = s.taps * Cout; g.k_per_slice = g.K;
-    g.tiles_m = (g.M + kBM - 1) / kBM;
-    g.tiles_n = (g.N + kBN - 1) / kBN;
-    return launch_gemm<OP_DX>(g, 1, vec, st, "train_gemm_kernel (dx)");
+    return train_backward<false>(dy, x, z, B, T, Cin, W, Cout, context_host, n_ctx, gamma, batch_mean, batch_var, eps, dx, dW,
+                                 dbias, dgamma, dbeta, nullptr, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 // The tail of a training step, forward and backward, fp32 (reference main.py:72-75, 99-100, 148): statistics pooling, the three
 // segment-level Linear layers, the cross-entropy loss, and Adam.  C ABI: include/xvec_train.h.
 //   pooling    one pass over y5: sums of deviations about the utterance's first frame, four row groups added in group order
+//              (train_tail_pool.h; its length-masked form is what train_tail_ragged.hip passes in -- the only kernels of the
+//              tail that see frames; everything after the pooling is per utterance)
 //   products   ONE tiled kernel on v_mfma_f32_32x32x2_f32 (tail_gemm_kernel) over 64 x 64 tiles with the reduction split into
 //              slices; every slice writes its partial product to a slab and tail_epilogue_kernel sums the slabs in slice order
 //              and applies the bias, the ReLU or the ReLU mask.  With M = batch a product has few tiles: the slices are what
@@ -19,6 +21,7 @@
 #include "../../include/xvec_train.h"
 #include "host_support.h"
 #include "tdnn_common.h"
+#include "train_tail_pool.h"
 
 namespace xvec {
 namespace {
@@ -30,7 +33,6 @@ constexpr int kTM = 64, kTN = 64, kTK = 16;     // block tile; 4 waves as 2 x 2,
 constexpr int kTLD = 68;
 constexpr int kSliceMinK = 64;                  // a slice of the reduction is at least this long ...
 constexpr int kSliceBlocks = 512;               // ... and slices x tiles aim at this many blocks
-constexpr int kPoolRows = 32;                   // frames per block of the pooling backward
 
 enum { EPI_SUM = 0, EPI_BIAS = 1, EPI_BIAS_RELU = 2, EPI_MASK = 3 };
 
@@ -175,96 +177,6 @@ __global__ __launch_bounds__(256) void tail_colsum_kernel(const float* __restric
     sh[grp][c] = s;
     __syncthreads();
     if (grp == 0 && col < cols) out[col] = ((sh[0][c] + sh[1][c]) + sh[2][c]) + sh[3][c];
-}
-
-// ---------------------------------------------------------------- statistics pooling
-// A block takes 64 groups of W channels of one utterance: thread (group tid & 63, row group tid >> 6) walks the frames
-// grp, grp + 4, ...; W = 4 reads 16 bytes per lane (C % 4 == 0, y5 16-byte aligned), W = 1 is the element-wise form.
-template <int W>
-__device__ __forceinline__ void load_w(const float* p, float (&v)[W]) {
-    if constexpr (W == 4) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-    } else {
-        v[0] = *p;
-    }
-}
-
-// pooled[b][c] = mean, pooled[b][C + c] = unbiased std over the Tp frames, from s1 = sum (y - pivot) and s2 = sum (y - pivot)^2
-// about the pivot y[b][0][c]: a channel that is constant over the utterance has s1 = s2 = 0 and an std of exactly 0.
-template <int W>
-__global__ __launch_bounds__(256) void tail_pool_kernel(const float* __restrict__ y, int Tp, int C, float* __restrict__ pooled) {
-    __shared__ float sh[2][4][64 * W];
-    const int tid = threadIdx.x, cg = tid & 63, grp = tid >> 6, b = blockIdx.y;
-    const int c0 = (blockIdx.x * 64 + cg) * W;
-    const bool ok = c0 < C;
-    float piv[W], s1[W], s2[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) piv[j] = s1[j] = s2[j] = 0.f;
-    if (ok) {
-        const float* base = y + (size_t)b * Tp * C + c0;
-        load_w<W>(base, piv);
-#pragma unroll 4
-        for (int t = grp; t < Tp; t += 4) {
-            float v[W];
-            load_w<W>(base + (size_t)t * C, v);
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-                const float d = v[j] - piv[j];
-                s1[j] += d;
-                s2[j] = fmaf(d, d, s2[j]);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-        sh[0][grp][cg * W + j] = s1[j];
-        sh[1][grp][cg * W + j] = s2[j];
-    }
-    __syncthreads();
-    if (!ok || grp != 0) return;
-    const float n = (float)Tp;
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-        const int i = cg * W + j;
-        const float a1 = ((sh[0][0][i] + sh[0][1][i]) + sh[0][2][i]) + sh[0][3][i];
-        const float a2 = ((sh[1][0][i] + sh[1][1][i]) + sh[1][2][i]) + sh[1][3][i];
-        const float var = fmaxf(a2 - a1 * a1 / n, 0.f) / (n - 1.0f);
-        pooled[(size_t)b * 2 * C + c0 + j] = piv[j] + a1 / n;
-        pooled[(size_t)b * 2 * C + C + c0 + j] = sqrtf(var);
-    }
-}
-
-// dy5[b][t][c] = dmean / Tp + dstd (y5 - mean) / ((Tp - 1) std), the second term 0 where std == 0 (a SELECT on the factor)
-template <int W>
-__global__ __launch_bounds__(256) void tail_pool_bwd_kernel(const float* __restrict__ y, int Tp, int C, const float* __restrict__ pooled,
-                                                            const float* __restrict__ dpooled, float* __restrict__ dy) {
-    const int tid = threadIdx.x, cg = tid & 63, grp = tid >> 6, b = blockIdx.z;
-    const int c0 = (blockIdx.x * 64 + cg) * W;
-    if (c0 >= C) return;
-    const int t0 = blockIdx.y * kPoolRows, t1 = min(Tp, t0 + kPoolRows);
-    float mean[W], add[W], fac[W];
-#pragma unroll
-    for (int j = 0; j < W; ++j) {
-        const size_t i = (size_t)b * 2 * C + c0 + j;
-        const float sd = pooled[i + C];
-        mean[j] = pooled[i];
-        add[j] = dpooled[i] / (float)Tp;
-        fac[j] = sd > 0.f ? dpooled[i + C] / ((float)(Tp - 1) * sd) : 0.f;
-    }
-    const size_t base = (size_t)b * Tp * C + c0;
-#pragma unroll 4
-    for (int t = t0 + grp; t < t1; t += 4) {
-        float v[W];
-        load_w<W>(y + base + (size_t)t * C, v);
-#pragma unroll
-        for (int j = 0; j < W; ++j) v[j] = fmaf(fac[j], v[j] - mean[j], add[j]);
-        if constexpr (W == 4) {
-            *reinterpret_cast<f32x4*>(dy + base + (size_t)t * C) = f32x4{v[0], v[1], v[2], v[3]};
-        } else {
-            dy[base + (size_t)t * C] = v[0];
-        }
-    }
 }
 
 // ---------------------------------------------------------------- the loss
@@ -415,8 +327,6 @@ __global__ __launch_bounds__(256) void adam_step_kernel(const AdamTable t) {
 
 ErrorChannel& terr() { return train_error_channel(); }
 
-bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 struct Product {
     int M, N, K, tiles_m, tiles_n, slices, k_per_slice;
     size_t slab_floats() const { return (size_t)slices * M * N; }
@@ -537,11 +447,15 @@ size_t xvec_train_tail_workspace_bytes(int32_t B, int32_t Tp, int32_t C, int32_t
     return make_plan(nullptr, s).total;
 }
 
+}  // extern "C"
+
+namespace xvec {
+
 // Launches: the pooling; three times product + epilogue; the row losses and their mean.
-int xvec_train_tail_forward(const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, const float* b6, int32_t H,
-                            const float* W7, const float* b7, const float* Wo, const float* bo, int32_t K,
-                            const int64_t* labels, float* pooled, float* a6, float* a7, float* logits, float* loss,
-                            void* workspace, size_t workspace_bytes, xvec_stream stream) {
+int train_tail_forward(const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, const float* b6, int32_t H,
+                       const float* W7, const float* b7, const float* Wo, const float* bo, int32_t K, const int64_t* labels,
+                       float* pooled, float* a6, float* a7, float* logits, float* loss, void* workspace, size_t workspace_bytes,
+                       xvec_stream stream, TailPoolFn pool, const int32_t* lengths_dev) {
     if (!y5 || !W6 || !b6 || !W7 || !b7 || !Wo || !bo || !labels)
         return terr().fail(XVEC_ERR_ARG, "null pointer: y5, the six segment parameters and labels are required");
     if (!pooled || !a6 || !a7 || !logits || !loss)
@@ -553,9 +467,7 @@ int xvec_train_tail_forward(const float* y5, int32_t B, int32_t Tp, int32_t C, c
     if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
 
-    if (C % 4 == 0 && aligned16(y5)) tail_pool_kernel<4><<<dim3((C / 4 + 63) / 64, B), 256, 0, st>>>(y5, Tp, C, pooled);
-    else tail_pool_kernel<1><<<dim3((C + 63) / 64, B), 256, 0, st>>>(y5, Tp, C, pooled);
-    if ((rc = terr().launch_ok("tail_pool_kernel"))) return rc;
+    if ((rc = pool(y5, B, Tp, C, lengths_dev, pooled, st))) return rc;
     if ((rc = product<true, true>(p.pre6, pooled, W6, p.slab, EPI_BIAS_RELU, b6, nullptr, a6, st, "tail_gemm_kernel (layer 6)"))) return rc;
     if ((rc = product<true, true>(p.pre7, a6, W7, p.slab, EPI_BIAS_RELU, b7, nullptr, a7, st, "tail_gemm_kernel (layer 7)"))) return rc;
     if ((rc = product<true, true>(p.out, a7, Wo, p.slab, EPI_BIAS, bo, nullptr, logits, st, "tail_gemm_kernel (output)"))) return rc;
@@ -567,11 +479,11 @@ int xvec_train_tail_forward(const float* y5, int32_t B, int32_t Tp, int32_t C, c
 
 // Launches: dlogits and dbo; per layer from the output down the weight gradient, the gradient of its input under the ReLU
 // mask of the layer below, and that layer's bias gradient; the gradient of pooled; dy5.
-int xvec_train_tail_backward(const float* dloss, const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, int32_t H,
-                             const float* W7, const float* Wo, int32_t K, const int64_t* labels, const float* pooled,
-                             const float* a6, const float* a7, const float* logits, float* dy5, float* dW6, float* db6,
-                             float* dW7, float* db7, float* dWo, float* dbo, void* workspace, size_t workspace_bytes,
-                             xvec_stream stream) {
+int train_tail_backward(const float* dloss, const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, int32_t H,
+                        const float* W7, const float* Wo, int32_t K, const int64_t* labels, const float* pooled, const float* a6,
+                        const float* a7, const float* logits, float* dy5, float* dW6, float* db6, float* dW7, float* db7,
+                        float* dWo, float* dbo, void* workspace, size_t workspace_bytes, xvec_stream stream, TailPoolBwdFn pool_bwd,
+                        const int32_t* lengths_dev) {
     if (!dloss || !y5 || !W6 || !W7 || !Wo || !labels || !pooled || !a6 || !a7 || !logits)
         return terr().fail(XVEC_ERR_ARG, "null pointer: dloss, y5, W6, W7, Wo, labels, pooled, a6, a7 and logits are required");
     if (!dW6 || !db6 || !dW7 || !db7 || !dWo || !dbo)
@@ -595,13 +507,28 @@ int xvec_train_tail_backward(const float* dloss, const float* y5, int32_t B, int
     if ((rc = product<false, false>(p.dW6, p.dz6, pooled, p.slab, EPI_SUM, nullptr, nullptr, dW6, st, "tail_gemm_kernel (dW6)"))) return rc;
     if (!dy5) return XVEC_OK;
     if ((rc = product<true, false>(p.dpool, p.dz6, W6, p.slab, EPI_SUM, nullptr, nullptr, p.dpooled, st, "tail_gemm_kernel (dpooled)"))) return rc;
-    const int row_blocks = (Tp + kPoolRows - 1) / kPoolRows;
-    if (row_blocks > 65535) return terr().fail(XVEC_ERR_TOO_LARGE, "Tp = %d frames: more than 65535 blocks of %d", Tp, kPoolRows);
-    if (C % 4 == 0 && aligned16(y5) && aligned16(dy5))
-        tail_pool_bwd_kernel<4><<<dim3((C / 4 + 63) / 64, row_blocks, B), 256, 0, st>>>(y5, Tp, C, pooled, p.dpooled, dy5);
-    else
-        tail_pool_bwd_kernel<1><<<dim3((C + 63) / 64, row_blocks, B), 256, 0, st>>>(y5, Tp, C, pooled, p.dpooled, dy5);
-    return terr().launch_ok("tail_pool_bwd_kernel");
+    return pool_bwd(y5, B, Tp, C, lengths_dev, pooled, p.dpooled, dy5, st);
+}
+
+}  // namespace xvec
+
+extern "C" {
+
+int xvec_train_tail_forward(const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, const float* b6, int32_t H,
+                            const float* W7, const float* b7, const float* Wo, const float* bo, int32_t K,
+                            const int64_t* labels, float* pooled, float* a6, float* a7, float* logits, float* loss,
+                            void* workspace, size_t workspace_bytes, xvec_stream stream) {
+    return train_tail_forward(y5, B, Tp, C, W6, b6, H, W7, b7, Wo, bo, K, labels, pooled, a6, a7, logits, loss, workspace,
+                              workspace_bytes, stream, launch_tail_pool<false>, nullptr);
+}
+
+int xvec_train_tail_backward(const float* dloss, const float* y5, int32_t B, int32_t Tp, int32_t C, const float* W6, int32_t H,
+                             const float* W7, const float* Wo, int32_t K, const int64_t* labels, const float* pooled,
+                             const float* a6, const float* a7, const float* logits, float* dy5, float* dW6, float* db6,
+                             float* dW7, float* db7, float* dWo, float* dbo, void* workspace, size_t workspace_bytes,
+                             xvec_stream stream) {
+    return train_tail_backward(dloss, y5, B, Tp, C, W6, H, W7, Wo, K, labels, pooled, a6, a7, logits, dy5, dW6, db6, dW7, db7, dWo,
+                               dbo, workspace, workspace_bytes, stream, launch_tail_pool_bwd<false>, nullptr);
 }
 
 // Launches: one per 32 tensors.

@@ -148,6 +148,14 @@ _SIGS = {
                                           _vp, _vp, _vp, C.c_size_t, _vp]),
     "xvec_train_tail_backward": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "xvec_tdnn_train_forward_ragged": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp,
+                                                 C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "xvec_tdnn_train_backward_ragged": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp,
+                                                  _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "xvec_train_tail_forward_ragged": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp,
+                                                 _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "xvec_train_tail_backward_ragged": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
+                                                  _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "xvec_adam_step": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i32,
                                  C.c_double, C.c_double, C.c_double, C.c_double, _i64, _vp]),
 }

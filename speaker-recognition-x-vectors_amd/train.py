@@ -7,6 +7,10 @@ in HIP too (csrc/train_tail.hip): pooling through loss as ONE autograd.Function 
 optimizer as `DeviceAdam` over xvec_adam_step.  Everything is fp32, the reference's own arithmetic.
 There is no fallback: a CPU tensor, dropout or a reduced precision raise.
 
+Ragged batches: every entry point takes `lengths=` (valid frames per utterance of the padded batch x[B, T, C], as the
+extraction calls do) and then goes through the length-masked calls (xvec_*_ragged): the step computes what the valid frames
+alone would give, whatever the padding holds.  The layout stays padded, so the padding's arithmetic is still done.
+
     trainer = XVectorTrainer(model)                 # an XVectorModel on a HIP device; tail="hip": the whole step in HIP
     for batch in loader:                            # the reference's (samples, labels, ids)
         loss = trainer.step(batch)
@@ -29,6 +33,28 @@ _check = _checker(_hip.lib.xvec_train_last_error)
 _workspaces = {}        # (device index, stream) -> uint8 tensor; calls on one stream run in order and may share it
 
 
+class _Lengths:
+    """The valid input frames of one ragged call: `host` (a list of ints) and `dev` (the same as int32 on the device)."""
+
+    def __init__(self, host, dev):
+        self.host, self.dev = host, dev
+
+
+def _host_lengths(lengths, B, lo, hi, what):
+    """`lengths` (a list or a tensor) as a list of B ints in [lo, hi]; ValueError otherwise, before anything is launched."""
+    if torch.is_tensor(lengths):
+        lengths = lengths.detach().cpu().tolist()
+    try:
+        host = [int(v) for v in lengths]
+    except TypeError:
+        raise ValueError(f"{what}: lengths must be a list or a tensor of {B} integers") from None
+    if len(host) != B or any(v != w for v, w in zip(host, lengths)):
+        raise ValueError(f"{what}: lengths must be {B} integers, one per utterance; got {list(lengths)!r}")
+    if min(host) < lo or max(host) > hi:
+        raise ValueError(f"{what}: lengths must lie in [{lo}, T={hi}]; got {min(host)} .. {max(host)}")
+    return host
+
+
 def _workspace(device, B, T, cin, cout, ctx, n_ctx):
     need = int(_hip.lib.xvec_tdnn_train_workspace_bytes(B, T, cin, cout, ctx, n_ctx))
     if need == 0:
@@ -43,7 +69,7 @@ class _TdnnTrain(torch.autograd.Function):
     x, z (the ReLU output), W, gamma and the batch statistics; y is not needed."""
 
     @staticmethod
-    def forward(ctx, x, W, bias, gamma, beta, context, eps):
+    def forward(ctx, x, W, bias, gamma, beta, context, eps, lengths_dev=None):
         B, T, cin = x.shape
         cout = W.shape[0]
         n_ctx = len(context)
@@ -60,13 +86,16 @@ class _TdnnTrain(torch.autograd.Function):
             gamma, beta = gamma.detach().contiguous(), beta.detach().contiguous()
         with torch.cuda.device(dev):
             ws = _workspace(dev, B, T, cin, cout, carr, n_ctx)
-            _check(_hip.lib.xvec_tdnn_train_forward(
-                x.data_ptr(), B, T, cin, W.data_ptr(), bias.data_ptr(), cout, carr, n_ctx,
-                gamma.data_ptr() if bn else None, beta.data_ptr() if bn else None, eps, z.data_ptr(),
-                mean.data_ptr() if bn else None, var.data_ptr() if bn else None, y.data_ptr() if bn else None,
-                ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+            args = (x.data_ptr(), B, T, cin, W.data_ptr(), bias.data_ptr(), cout, carr, n_ctx,
+                    gamma.data_ptr() if bn else None, beta.data_ptr() if bn else None, eps, z.data_ptr(),
+                    mean.data_ptr() if bn else None, var.data_ptr() if bn else None, y.data_ptr() if bn else None,
+                    ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+            if lengths_dev is None:
+                _check(_hip.lib.xvec_tdnn_train_forward(*args))
+            else:
+                _check(_hip.lib.xvec_tdnn_train_forward_ragged(*args, lengths_dev.data_ptr()))
         ctx.save_for_backward(x, z, W, *((gamma, mean, var) if bn else ()))
-        ctx.context, ctx.eps, ctx.bn = tuple(context), eps, bn
+        ctx.context, ctx.eps, ctx.bn, ctx.lengths_dev = tuple(context), eps, bn, lengths_dev
         ctx.mark_non_differentiable(mean, var)
         return y, mean, var
 
@@ -88,11 +117,14 @@ class _TdnnTrain(torch.autograd.Function):
         ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             ws = _workspace(dev, B, T, cin, cout, carr, n_ctx)
-            _check(_hip.lib.xvec_tdnn_train_backward(
-                dy.data_ptr(), x.data_ptr(), z.data_ptr(), B, T, cin, W.data_ptr(), cout, carr, n_ctx, ptr(gamma),
-                ptr(mean), ptr(var), ctx.eps, ptr(dx), dW.data_ptr(), db.data_ptr(), ptr(dgamma), ptr(dbeta),
-                ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
-        return dx, dW, db, dgamma, dbeta, None, None
+            args = (dy.data_ptr(), x.data_ptr(), z.data_ptr(), B, T, cin, W.data_ptr(), cout, carr, n_ctx, ptr(gamma),
+                    ptr(mean), ptr(var), ctx.eps, ptr(dx), dW.data_ptr(), db.data_ptr(), ptr(dgamma), ptr(dbeta),
+                    ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+            if ctx.lengths_dev is None:
+                _check(_hip.lib.xvec_tdnn_train_backward(*args))
+            else:
+                _check(_hip.lib.xvec_tdnn_train_backward_ragged(*args, ctx.lengths_dev.data_ptr()))
+        return dx, dW, db, dgamma, dbeta, None, None, None
 
 
 def _tail_workspace(device, B, tp, c, h, k):
@@ -110,7 +142,7 @@ class _TailTrain(torch.autograd.Function):
     the only way into the graph); the incoming gradient of the loss stays on the device."""
 
     @staticmethod
-    def forward(ctx, h5, W6, b6, W7, b7, Wo, bo, labels):
+    def forward(ctx, h5, W6, b6, W7, b7, Wo, bo, labels, lengths_dev=None):
         B, tp, c = h5.shape
         h, k = W6.shape[0], Wo.shape[0]
         dev = h5.device
@@ -119,11 +151,15 @@ class _TailTrain(torch.autograd.Function):
         pooled, a6, a7, logits, loss = new(B, 2 * c), new(B, h), new(B, h), new(B, k), new()
         with torch.cuda.device(dev):
             ws = _tail_workspace(dev, B, tp, c, h, k)
-            _check(_hip.lib.xvec_train_tail_forward(
-                h5.data_ptr(), B, tp, c, W6.data_ptr(), b6.data_ptr(), h, W7.data_ptr(), b7.data_ptr(), Wo.data_ptr(),
-                bo.data_ptr(), k, labels.data_ptr(), pooled.data_ptr(), a6.data_ptr(), a7.data_ptr(), logits.data_ptr(),
-                loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev)))
+            args = (h5.data_ptr(), B, tp, c, W6.data_ptr(), b6.data_ptr(), h, W7.data_ptr(), b7.data_ptr(), Wo.data_ptr(),
+                    bo.data_ptr(), k, labels.data_ptr(), pooled.data_ptr(), a6.data_ptr(), a7.data_ptr(), logits.data_ptr(),
+                    loss.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+            if lengths_dev is None:
+                _check(_hip.lib.xvec_train_tail_forward(*args))
+            else:
+                _check(_hip.lib.xvec_train_tail_forward_ragged(*args, lengths_dev.data_ptr()))
         ctx.save_for_backward(h5, W6, W7, Wo, labels, pooled, a6, a7, logits)
+        ctx.lengths_dev = lengths_dev
         ctx.mark_non_differentiable(logits)
         return loss, logits
 
@@ -140,12 +176,15 @@ class _TailTrain(torch.autograd.Function):
         dbo = torch.empty(k, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             ws = _tail_workspace(dev, B, tp, c, h, k)
-            _check(_hip.lib.xvec_train_tail_backward(
-                dloss.data_ptr(), h5.data_ptr(), B, tp, c, W6.data_ptr(), h, W7.data_ptr(), Wo.data_ptr(), k, labels.data_ptr(),
-                pooled.data_ptr(), a6.data_ptr(), a7.data_ptr(), logits.data_ptr(), None if dy5 is None else dy5.data_ptr(),
-                dW6.data_ptr(), db6.data_ptr(), dW7.data_ptr(), db7.data_ptr(), dWo.data_ptr(), dbo.data_ptr(), ws.data_ptr(),
-                ws.numel(), _stream_ptr(dev)))
-        return dy5, dW6, db6, dW7, db7, dWo, dbo, None
+            args = (dloss.data_ptr(), h5.data_ptr(), B, tp, c, W6.data_ptr(), h, W7.data_ptr(), Wo.data_ptr(), k, labels.data_ptr(),
+                    pooled.data_ptr(), a6.data_ptr(), a7.data_ptr(), logits.data_ptr(), None if dy5 is None else dy5.data_ptr(),
+                    dW6.data_ptr(), db6.data_ptr(), dW7.data_ptr(), db7.data_ptr(), dWo.data_ptr(), dbo.data_ptr(), ws.data_ptr(),
+                    ws.numel(), _stream_ptr(dev))
+            if ctx.lengths_dev is None:
+                _check(_hip.lib.xvec_train_tail_backward(*args))
+            else:
+                _check(_hip.lib.xvec_train_tail_backward_ragged(*args, ctx.lengths_dev.data_ptr()))
+        return dy5, dW6, db6, dW7, db7, dWo, dbo, None, None
 
 
 class DeviceAdam:
@@ -238,10 +277,14 @@ class DeviceAdam:
             self.state[i] = {"step": int(st["step"]), "exp_avg": moment(st["exp_avg"]), "exp_avg_sq": moment(st["exp_avg_sq"])}
 
 
-def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer) -> torch.Tensor:
+def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer, lengths=None) -> torch.Tensor:
     """`layer(x)` as the reference computes it under model.train() (tdnn_layer.py:26-41): x[B, T, in] ->
     y[B, T - span, out] with a graph through the layer's own parameters, BatchNorm on the batch statistics, and the
-    layer's running_mean / running_var / num_batches_tracked updated as nn.BatchNorm1d updates them in training mode."""
+    layer's running_mean / running_var / num_batches_tracked updated as nn.BatchNorm1d updates them in training mode.
+
+    `lengths` (a list or a tensor of B integers in [span + 1, T]): the valid frames of a padded batch.  Utterance b then has
+    lengths[b] - span valid output frames -- the next layer's lengths -- which alone form the BatchNorm batch and receive
+    gradients; the other rows of y are exactly 0, and nothing depends on what x holds past its lengths."""
     _require_gpu(x, "tdnn_layer_train")
     if layer.dropout_p:
         raise RuntimeError(f"tdnn_layer_train: dropout_p = {layer.dropout_p} is outside this build's scope (only 0)")
@@ -253,11 +296,18 @@ def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer) -> torch.Tensor:
     context = [int(c) for c in layer.context]
     x = x.float().contiguous()
     norm = layer.norm if layer.batch_norm else None
-    n_rows = x.shape[0] * (x.shape[1] - (context[-1] - context[0]))
+    span = context[-1] - context[0]
+    n_rows = x.shape[0] * (x.shape[1] - span)
+    if lengths is not None:
+        if not isinstance(lengths, _Lengths):
+            host = _host_lengths(lengths, x.shape[0], span + 1, x.shape[1], "tdnn_layer_train")
+            lengths = _Lengths(host, torch.tensor(host, dtype=torch.int32).to(x.device))
+        n_rows = sum(lengths.host) - x.shape[0] * span
     if norm is not None and n_rows == 1:
         raise ValueError("tdnn_layer_train: BatchNorm in training mode needs more than one row per channel")
-    y, mean, var = _TdnnTrain.apply(x, W, layer.linear.bias, norm.weight if norm is not None else None,
-                                    norm.bias if norm is not None else None, context, norm.eps if norm is not None else 0.0)
+    args = (x, W, layer.linear.bias, norm.weight if norm is not None else None, norm.bias if norm is not None else None, context,
+            norm.eps if norm is not None else 0.0)
+    y, mean, var = _TdnnTrain.apply(*args) if lengths is None else _TdnnTrain.apply(*args, lengths.dev)
     if norm is not None and norm.track_running_stats:
         with torch.no_grad():
             norm.num_batches_tracked += 1
@@ -287,8 +337,12 @@ class XVectorTrainer:
         self.optimizer = None
 
     # ------------------------------------------------------------------ main.py:66-75 with a graph
-    def _frames(self, x: torch.Tensor) -> torch.Tensor:
-        """The five frame-level layers: x[B, T, in] -> h5[B, T - 14, 1500]."""
+    def _frames(self, x: torch.Tensor, lengths=None):
+        """The five frame-level layers: x[B, T, in] -> h5[B, T - 14, 1500]; with `lengths`, (h5, the pooled lengths): every
+        layer's lengths are the ones before less its span, uploaded as one table per step."""
+        host = None
+        if lengths is not None and x.dim() == 3:     # refused on the host first: a bad length never reaches a launch
+            host = _host_lengths(lengths, x.shape[0], TOTAL_CONTEXT + 2, x.shape[1], "XVectorTrainer")
         _require_gpu(x, "XVectorTrainer")
         if x.dim() != 3 or x.shape[2] != self.model.hparams["input_size"]:
             raise ValueError(f"expected x[B, T, {self.model.hparams['input_size']}], got {tuple(x.shape)}")
@@ -296,40 +350,72 @@ class XVectorTrainer:
             raise ValueError(f"T={x.shape[1]}: training needs T >= {TOTAL_CONTEXT + 2} (two pooled frames for torch.std)")
         m = self.model
         h = x.float()
+        if lengths is None:
+            for layer in m.time_context_layers:
+                h = tdnn_layer_train(h, layer)
+            return h
+        table = [host]
         for layer in m.time_context_layers:
-            h = tdnn_layer_train(h, layer)
-        return h
+            span = int(layer.context[-1]) - int(layer.context[0])
+            table.append([v - span for v in table[-1]])
+        dev = torch.tensor(table, dtype=torch.int32).to(x.device)
+        for i, layer in enumerate(m.time_context_layers):
+            h = tdnn_layer_train(h, layer, _Lengths(table[i], dev[i]))
+        return h, _Lengths(table[-1], dev[-1])
 
-    def logits(self, x: torch.Tensor) -> torch.Tensor:
+    def logits(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
         m = self.model
-        h = self._frames(x)
         # the tail, 0.3 % of the arithmetic, on torch ops (tail="hip": training_step goes through _TailTrain instead)
-        h = torch.cat((torch.mean(h, 1), torch.std(h, 1)), 1)
+        if lengths is None:
+            h = self._frames(x)
+            h = torch.cat((torch.mean(h, 1), torch.std(h, 1)), 1)
+        else:
+            h, pooled_lengths = self._frames(x, lengths)
+            h = self._masked_pool(h, pooled_lengths.dev)
         h = F.relu(F.linear(h, m.segment_layer6.weight, m.segment_layer6.bias))
         h = F.relu(F.linear(h, m.segment_layer7.weight, m.segment_layer7.bias))
         return F.linear(h, m.output.weight, m.output.bias)
 
-    def training_step(self, batch, batch_index=0):
+    @staticmethod
+    def _masked_pool(h, frames):
+        """(mean, unbiased std) over the first frames[b] frames of h[b], by selection: what h holds past them does not matter.
+        The std of a channel that is constant over them is 0 with a zero gradient, as torch.std's."""
+        valid = (torch.arange(h.shape[1], device=h.device)[None, :] < frames[:, None])[:, :, None]
+        n = frames.to(h.dtype)[:, None]
+        zero = torch.zeros((), dtype=h.dtype, device=h.device)
+        h = torch.where(valid, h, zero)                # selected BEFORE any arithmetic: the backward has no 0 * NaN either
+        mean = h.sum(1) / n
+        var = torch.where(valid, (h - mean[:, None, :]) ** 2, zero).sum(1) / (n - 1.0)
+        std = torch.where(var > 0, torch.sqrt(torch.where(var > 0, var, torch.ones_like(var))), zero)
+        return torch.cat((mean, std), 1)
+
+    def training_step(self, batch, batch_index=0, lengths=None):
         samples, labels, ids = batch
         if self.tail == "hip":
             m = self.model
-            h5 = self._frames(samples.float())
-            loss, outputs = _TailTrain.apply(h5.contiguous(), m.segment_layer6.weight, m.segment_layer6.bias,
-                                             m.segment_layer7.weight, m.segment_layer7.bias, m.output.weight, m.output.bias,
-                                             labels.to(device=h5.device, dtype=torch.int64).contiguous())
+            tail = (m.segment_layer6.weight, m.segment_layer6.bias, m.segment_layer7.weight, m.segment_layer7.bias,
+                    m.output.weight, m.output.bias)
+            if lengths is None:
+                h5 = self._frames(samples.float())
+                loss, outputs = _TailTrain.apply(h5.contiguous(), *tail, labels.to(device=h5.device, dtype=torch.int64).contiguous())
+            else:
+                h5, pooled_lengths = self._frames(samples.float(), lengths)
+                loss, outputs = _TailTrain.apply(h5.contiguous(), *tail, labels.to(device=h5.device, dtype=torch.int64).contiguous(),
+                                                 pooled_lengths.dev)
             return {"loss": loss, "train_preds": outputs, "train_labels": labels, "train_id": ids}
-        outputs = self.logits(samples.float())
+        outputs = self.logits(samples.float(), lengths)
         loss = F.cross_entropy(outputs, labels.to(outputs.device))
         return {"loss": loss, "train_preds": outputs, "train_labels": labels, "train_id": ids}
 
-    def validation_step(self, batch, batch_index=0):
-        """main.py:120-124 as Lightning runs it (model.eval(), no graph): the HIP extraction path's logits."""
+    def validation_step(self, batch, batch_index=0, lengths=None):
+        """main.py:120-124 as Lightning runs it (model.eval(), no graph): the HIP extraction path's logits, over the same
+        `lengths` as the training step takes."""
         samples, labels, ids = batch
         was_training = self.model.training
         self.model.eval()
         try:
             with torch.no_grad():
-                outputs = self.model(samples.float())
+                outputs = self.model(samples.float(), lengths)
                 loss = F.cross_entropy(outputs, labels.to(outputs.device))
         finally:
             self.model.train(was_training)
@@ -340,12 +426,12 @@ class XVectorTrainer:
             return DeviceAdam(self.model.parameters(), lr=self.model.learning_rate)
         return torch.optim.Adam(self.model.parameters(), lr=self.model.learning_rate)
 
-    def step(self, batch) -> torch.Tensor:
+    def step(self, batch, lengths=None) -> torch.Tensor:
         """zero_grad, training_step, backward, optimizer step; returns the (detached) loss of the step."""
         if self.optimizer is None:
             self.optimizer = self.configure_optimizers()
         self.optimizer.zero_grad(set_to_none=True)
-        loss = self.training_step(batch)["loss"]
+        loss = self.training_step(batch, lengths=lengths)["loss"]
         loss.backward()
         self.optimizer.step()
         return loss.detach()
