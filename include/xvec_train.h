@@ -44,6 +44,23 @@
  * the loss); nothing is read or written out of bounds through it.  With no valid row at all batch_mean is 0 and batch_var is NaN (0 / 0).
  * The calls without lengths are these with every length T; their results and code are unchanged by the masked form, which is a
  * compile-time variant of the same kernels.  Two runs of one ragged call are bit-identical.
+ *
+ * Dropout (the *_dropout calls; csrc/tdnn_train_dropout.hip, csrc/dropout_mask.h).  The reference's layer is Linear, ReLU,
+ * Dropout, BatchNorm.  The mask is a stateless function of (seed, stream, row, channel, p): nothing is stored and no generator
+ * state lives anywhere.  With n = b * T' + t the row of the padded layout and c the output channel, element (n, c) is decided by
+ * word n & 3 of Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) on
+ *     counter = (c, n >> 2, low word of stream, high word of stream),   key = (low word of seed, high word of seed):
+ *   - the element is DROPPED iff word < thr, thr = (uint32) floor((double) p * 2^32); p = 0 drops nothing;
+ *   - forward: z = kept ? max(x_ctx W^T + bias, 0) * scale : 0 with scale = (float) (1 / (1 - (double) p)), one fp32 multiply.
+ *     The z that is written (and saved for the backward) is this post-dropout value; batch_mean, batch_var and y are those of
+ *     that z, so a caller's running statistics see the post-dropout batch, as torch's do;
+ *   - backward: a kept element with a positive pre-activation has z > 0 (scale >= 1), every other one has z == 0 and no
+ *     gradient, so dz = [z > 0] scale (the dz of the formulas below): the call needs p, and neither the seed nor a mask;
+ *     dgamma and dbeta are the formulas below on the post-dropout z;
+ *   - the mask of (n, c) does not depend on B, on the other utterances' lengths or on whether the call is ragged: a ragged
+ *     call uses the padded row index, and its invalid rows stay exactly 0;
+ *   - 0 <= p < 1, anything else (NaN included) is XVEC_ERR_ARG before any launch.  With p = 0 the calls are bit-identical to
+ *     the ones without dropout; two runs of one call are bit-identical.
  */
 #ifndef XVEC_TRAIN_H
 #define XVEC_TRAIN_H
@@ -100,6 +117,24 @@ int xvec_tdnn_train_backward_ragged(const float* dy, const float* x, const float
                                     const float* gamma, const float* batch_mean, const float* batch_var, float eps, float* dx,
                                     float* dW, float* dbias, float* dgamma, float* dbeta, void* workspace,
                                     size_t workspace_bytes, xvec_stream stream, const int32_t* lengths_dev);
+
+/* The same two calls with dropout after the ReLU (see the head of this file).  lengths_dev == NULL: the fixed-length form;
+ * otherwise the ragged one.  xvec_tdnn_train_workspace_bytes serves them unchanged.  `dropout_stream` tells the masks of one
+ * seed apart (xvector_amd.train: 8 * step + layer); it is not a device stream. */
+int xvec_tdnn_train_forward_dropout(const float* x, int32_t B, int32_t T, int32_t Cin, const float* W, const float* bias,
+                                    int32_t Cout, const int32_t* context_host, int32_t n_ctx, const float* gamma,
+                                    const float* beta, float eps, float* z, float* batch_mean, float* batch_var, float* y,
+                                    void* workspace, size_t workspace_bytes, xvec_stream stream, const int32_t* lengths_dev,
+                                    float p, uint64_t seed, uint64_t dropout_stream);
+int xvec_tdnn_train_backward_dropout(const float* dy, const float* x, const float* z, int32_t B, int32_t T, int32_t Cin,
+                                     const float* W, int32_t Cout, const int32_t* context_host, int32_t n_ctx,
+                                     const float* gamma, const float* batch_mean, const float* batch_var, float eps, float* dx,
+                                     float* dW, float* dbias, float* dgamma, float* dbeta, void* workspace,
+                                     size_t workspace_bytes, xvec_stream stream, const int32_t* lengths_dev, float p);
+
+/* keep_host[n * Cout + c] = 1 if element (n, c) is kept, 0 if it is dropped, for n < N: the forward call's own mask, computed
+ * on the CPU from the same header (to reproduce a step, and for the tests).  HOST memory; touches no device.  1 <= N < 2^31. */
+int xvec_dropout_keep_host(uint8_t* keep_host, int64_t N, int32_t Cout, float p, uint64_t seed, uint64_t dropout_stream);
 
 /* ---- the tail of the step.  C = layer-5 width, Tp = pooled frames (>= 2), H = x-vector size, K = classes; B <= 65535.
  *

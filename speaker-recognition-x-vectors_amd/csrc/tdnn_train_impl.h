@@ -24,6 +24,7 @@
 
 #include "../../include/xvec_hip.h"
 #include "../../include/xvec_train.h"
+#include "dropout_mask.h"
 #include "host_support.h"
 #include "tdnn_common.h"
 
@@ -40,7 +41,9 @@ constexpr int kChunk = 256;                     // rows per partial of the colum
 constexpr int kDwMinRows = 256;                 // a dW slice is at least this many rows ...
 constexpr int kDwBlocks = 1024;                 // ... and slices x tiles aim at this many blocks (fixed: device-independent results)
 
-enum { OP_FWD = 0, OP_DW = 1, OP_DX = 2 };
+// (a NAMED enumeration: the kernels' parameter list depends on OP == OP_FWD_DROPOUT, which is part of their mangled names, and
+// the host and the device compilation number unnamed types differently)
+enum Op : int { OP_FWD = 0, OP_DW = 1, OP_DX = 2, OP_FWD_DROPOUT = 3 };
 
 // The valid INPUT frames per utterance of a ragged call, device int32 [B]; empty in the unmasked kernels.
 template <bool RAGGED>
@@ -49,6 +52,17 @@ template <>
 struct Lengths<true> {
     const int32_t* len;
     int B, T, span;
+};
+
+// Dropout after the ReLU (the *_dropout calls): threshold and scale of dropout_mask.h for the call's p, and the (seed, stream)
+// that name its mask; empty in the kernels without it.  The backward carries the scale only.
+template <bool DROPOUT>
+struct Dropout {};
+template <>
+struct Dropout<true> {
+    uint32_t thr;
+    float scale;
+    uint64_t seed, stream;
 };
 
 // valid output rows of utterance b: len[b] - span for a length in [span + 1, T]; a length outside that range, which the host
@@ -129,8 +143,12 @@ __device__ __forceinline__ void advance(int& tap, int& c, int step, int width) {
     }
 }
 
+// OP_FWD_DROPOUT is OP_FWD with the dropout mask in the epilogue: z = keep ? max(acc + bias, 0) * scale : 0, the mask from
+// dropout_mask.h.  Only csrc/tdnn_train_dropout.hip instantiates it; D is empty in every other product.
 template <int OP, bool VEC, bool RAGGED>
-__global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, const Lengths<RAGGED> L) {
+__global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, const Lengths<RAGGED> L,
+                                                            const Dropout<OP == OP_FWD_DROPOUT> D) {
+    constexpr bool FWD = OP == OP_FWD || OP == OP_FWD_DROPOUT, DROPOUT = OP == OP_FWD_DROPOUT;
     __shared__ __attribute__((aligned(16))) float sA[2][kBK][kLD];
     __shared__ __attribute__((aligned(16))) float sB[2][kBK][kLD];
     const int per_slice = g.tiles_m * g.tiles_n;
@@ -154,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, co
     int a_v[2] = {0, 0};                           // RAGGED DX: valid dz rows of the utterance
     bool a_ok[2] = {false, false};
     int a_tap = 0, a_c = 0;                        // FWD / DX: (tap, channel) of k = kcur + kc_k
-    if constexpr (OP == OP_FWD) {
+    if constexpr (FWD) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int m = m0 + kc_row + 64 * i;
@@ -212,16 +230,16 @@ __global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, co
                 rb[i][j] = 0.f;
             }
         // ---------------- A
-        if constexpr (OP == OP_FWD || OP == OP_DX) {
+        if constexpr (FWD || OP == OP_DX) {
             const int k = kcur + kc_k;
-            const int width = OP == OP_FWD ? g.Cin : g.Cout;
+            const int width = FWD ? g.Cin : g.Cout;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
                 if (!a_ok[i]) continue;
                 if constexpr (VEC) {
                     if (k < kend) {
                         const int o = tap_off(g, a_tap);
-                        if constexpr (OP == OP_FWD) {
+                        if constexpr (FWD) {
                             load4(g.a + (int64_t)(a_base[i] + o) * g.Cin + a_c, ra[i]);
                         } else {
                             const int p = a_q[i] - o;
@@ -234,7 +252,7 @@ __global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, co
                     for (int j = 0; j < 4; ++j) {
                         if (k + j < kend) {
                             const int o = tap_off(g, tj);
-                            if constexpr (OP == OP_FWD) {
+                            if constexpr (FWD) {
                                 ra[i][j] = g.a[(int64_t)(a_base[i] + o) * g.Cin + cj];
                             } else {
                                 const int p = a_q[i] - o;
@@ -263,7 +281,7 @@ __global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, co
             }
         }
         // ---------------- B
-        if constexpr (OP == OP_FWD) {              // W[n, k]
+        if constexpr (FWD) {              // W[n, k]
             const int k = kcur + kc_k;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -336,7 +354,7 @@ __global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, co
 #pragma unroll
                 for (int j = 0; j < 4; ++j) sA[buf][kc_k + j][kc_row + 64 * i] = ra[i][j];
             }
-            if constexpr (OP == OP_FWD) {
+            if constexpr (FWD) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) sB[buf][kc_k + j][kc_row + 64 * i] = rb[i][j];
             } else {
@@ -383,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, co
     // RAGGED forward: which of the tile's rows are valid, once per row, in the first words of sA (the K loop ended on a barrier:
     // nobody reads the operands any more)
     int* const s_valid = reinterpret_cast<int*>(&sA[0][0][0]);
-    if constexpr (OP == OP_FWD && RAGGED) {
+    if constexpr (FWD && RAGGED) {
         if (tid < kBM) {
             const int m = m0 + tid, b = m / g.Tp;
             s_valid[tid] = m < g.M && m - b * g.Tp < valid_rows(L, b);
@@ -399,20 +417,27 @@ __global__ __launch_bounds__(256, 2) void train_gemm_kernel(const GemmArgs g, co
         const int col = n0 + wc * 64 + j * 32 + l31;
         if (col >= g.N) continue;
         float bias = 0.f;
-        if constexpr (OP == OP_FWD) bias = g.bias[col];
+        if constexpr (FWD) bias = g.bias[col];
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 2; ++i) {
+            [[maybe_unused]] dropout::Words words{};
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wr * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
+                // DROPOUT: the accumulators r & 3 are four consecutive rows from a multiple of 4 -- the four words of one call
+                if constexpr (DROPOUT)
+                    if ((r & 3) == 0 && row < g.M) words = dropout::row_quad_words((uint32_t)col, (uint32_t)row >> 2, D.seed, D.stream);
                 if (row >= g.M) continue;
                 float v = acc[i][j][r];
-                if constexpr (OP == OP_FWD) v = fmaxf(v + bias, 0.f);
-                if constexpr (OP == OP_FWD && RAGGED) v = s_valid[row - m0] ? v : 0.f;      // an invalid row of z is exactly 0
+                if constexpr (FWD) v = fmaxf(v + bias, 0.f);
+                if constexpr (DROPOUT) v = words.w[r & 3] >= D.thr ? v * D.scale : 0.f;
+                if constexpr (FWD && RAGGED) v = s_valid[row - m0] ? v : 0.f;      // an invalid row of z is exactly 0
                 out[(size_t)row * ldc + col] = v;
             }
+        }
     }
 }
+
 
 // out[i] = sum over slices, in slice order, of slab[s][i]
 __global__ __launch_bounds__(256) void train_slab_reduce_kernel(const float* __restrict__ slab, int slices, size_t count,
@@ -619,12 +644,13 @@ __global__ __launch_bounds__(64) void train_col_reduce_kernel(const float* __res
 // dz = [z > 0] gamma invstd (dy - dbeta / N - x^ dgamma / N), or [z > 0] dy without BatchNorm; part[chunk][col] = sum of dz
 // over the chunk's rows.  The mask is a SELECT: a channel that is never on gets exact zeros.
 // RAGGED: the 1 / N is over the call's valid rows; an invalid row of dz is exactly 0 and its dy is not read.
-template <bool RAGGED>
-__global__ __launch_bounds__(256) void train_dz_kernel(const float* __restrict__ dy, const float* __restrict__ z, int N, int Cout, int Tp,
-                                                       const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                       const float* __restrict__ var, const float* __restrict__ dgamma,
-                                                       const float* __restrict__ dbeta, float eps, float* __restrict__ dz,
-                                                       float* __restrict__ part, const Lengths<RAGGED> L) {
+// DROPOUT: z is the post-dropout value, so [z > 0] is "kept and on" (scale >= 1); dz is the value above times the scale.
+template <bool RAGGED, bool DROPOUT>
+__device__ __forceinline__ void dz_chunk(const float* __restrict__ dy, const float* __restrict__ z, int N, int Cout, int Tp,
+                                         const float* __restrict__ gamma, const float* __restrict__ mean,
+                                         const float* __restrict__ var, const float* __restrict__ dgamma,
+                                         const float* __restrict__ dbeta, float eps, float* __restrict__ dz,
+                                         float* __restrict__ part, const Lengths<RAGGED>& L, [[maybe_unused]] float keep_scale) {
     __shared__ float sh[4][64];
     ColCtx c = col_ctx(N, Cout);
     int rows = N;
@@ -649,6 +675,7 @@ __global__ __launch_bounds__(256) void train_dz_kernel(const float* __restrict__
             const float zv = z[i];
             float v = dy[i];
             if (gamma) v = scale * ((v - kb) - (zv - mu) * invstd * kg);
+            if constexpr (DROPOUT) v *= keep_scale;
             v = zv > 0.f ? v : 0.f;
             dz[i] = v;
             s += v;
@@ -665,6 +692,25 @@ __global__ __launch_bounds__(256) void train_dz_kernel(const float* __restrict__
     }
     s = group_sum(s, sh);
     if (c.ok && c.grp == 0) part[(size_t)blockIdx.y * Cout + c.col] = s;
+}
+
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void train_dz_kernel(const float* __restrict__ dy, const float* __restrict__ z, int N, int Cout, int Tp,
+                                                       const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                       const float* __restrict__ var, const float* __restrict__ dgamma,
+                                                       const float* __restrict__ dbeta, float eps, float* __restrict__ dz,
+                                                       float* __restrict__ part, const Lengths<RAGGED> L) {
+    dz_chunk<RAGGED, false>(dy, z, N, Cout, Tp, gamma, mean, var, dgamma, dbeta, eps, dz, part, L, 1.0f);
+}
+
+// Only csrc/tdnn_train_dropout.hip instantiates it.
+template <bool RAGGED>
+__global__ __launch_bounds__(256) void train_dz_dropout_kernel(const float* __restrict__ dy, const float* __restrict__ z, int N, int Cout,
+                                                               int Tp, const float* __restrict__ gamma, const float* __restrict__ mean,
+                                                               const float* __restrict__ var, const float* __restrict__ dgamma,
+                                                               const float* __restrict__ dbeta, float eps, float* __restrict__ dz,
+                                                               float* __restrict__ part, const Lengths<RAGGED> L, float keep_scale) {
+    dz_chunk<RAGGED, true>(dy, z, N, Cout, Tp, gamma, mean, var, dgamma, dbeta, eps, dz, part, L, keep_scale);
 }
 
 // ---------------------------------------------------------------- host side
@@ -737,12 +783,20 @@ inline int workspace_arg_ok(void* ws, size_t have, size_t need) {
 inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 template <int OP, bool RAGGED>
-int launch_gemm(const GemmArgs& g, const Lengths<RAGGED>& L, int slices, bool vec, hipStream_t s, const char* what) {
+int launch_gemm(const GemmArgs& g, const Lengths<RAGGED>& L, int slices, bool vec, hipStream_t s, const char* what,
+                const Dropout<OP == OP_FWD_DROPOUT>& D = {}) {
     const int64_t blocks = (int64_t)g.tiles_m * g.tiles_n * slices;
     if (blocks > 0x7fffffff) return terr().fail(XVEC_ERR_TOO_LARGE, "%s: %lld blocks", what, (long long)blocks);
-    if (vec) train_gemm_kernel<OP, true, RAGGED><<<(unsigned)blocks, 256, 0, s>>>(g, L);
-    else train_gemm_kernel<OP, false, RAGGED><<<(unsigned)blocks, 256, 0, s>>>(g, L);
+    if (vec) train_gemm_kernel<OP, true, RAGGED><<<(unsigned)blocks, 256, 0, s>>>(g, L, D);
+    else train_gemm_kernel<OP, false, RAGGED><<<(unsigned)blocks, 256, 0, s>>>(g, L, D);
     return terr().launch_ok(what);
+}
+
+// XVEC_OK and the call's Dropout block, or the code with the message set: 0 <= p < 1, NaN refused
+inline int make_dropout(float p, uint64_t seed, uint64_t stream, Dropout<true>& D) {
+    if (!dropout::valid_p(p)) return terr().fail(XVEC_ERR_ARG, "dropout p = %g: 0 <= p < 1", (double)p);
+    D = Dropout<true>{dropout::threshold(p), dropout::keep_scale(p), seed, stream};
+    return XVEC_OK;
 }
 
 inline GemmArgs gemm_args(const Shape& s) {
@@ -761,11 +815,12 @@ Lengths<RAGGED> make_lengths(const Shape& s, const int32_t* lengths_dev) {
 }
 
 // Launches: the product (+ bias, ReLU) into z; with BatchNorm the chunk statistics, their merge, the normalisation.
-template <bool RAGGED>
+// DROPOUT: the product's epilogue applies the mask, everything after it sees the post-dropout z.
+template <bool RAGGED, bool DROPOUT = false>
 int train_forward(const float* x, int32_t B, int32_t T, int32_t Cin, const float* W, const float* bias, int32_t Cout,
                   const int32_t* context_host, int32_t n_ctx, const float* gamma, const float* beta, float eps, float* z,
                   float* batch_mean, float* batch_var, float* y, const int32_t* lengths_dev, void* workspace,
-                  size_t workspace_bytes, xvec_stream stream) {
+                  size_t workspace_bytes, xvec_stream stream, const Dropout<DROPOUT>& D = {}) {
     if (!x || !W || !bias || !z) return terr().fail(XVEC_ERR_ARG, "null pointer: x, W, bias and z are required");
     if (gamma && (!beta || !batch_mean || !batch_var || !y))
         return terr().fail(XVEC_ERR_ARG, "null pointer: with gamma, beta, batch_mean, batch_var and y are required");
@@ -783,7 +838,9 @@ int train_forward(const float* x, int32_t B, int32_t T, int32_t Cin, const float
     g.M = s.N; g.N = Cout; g.K = s.Kw; g.k_per_slice = s.Kw;
     g.tiles_m = (g.M + kBM - 1) / kBM;
     g.tiles_n = (g.N + kBN - 1) / kBN;
-    if ((rc = launch_gemm<OP_FWD>(g, L, 1, Cin % 4 == 0 && aligned16(x) && aligned16(W), st, "train_gemm_kernel (forward)"))) return rc;
+    if ((rc = launch_gemm<DROPOUT ? OP_FWD_DROPOUT : OP_FWD>(g, L, 1, Cin % 4 == 0 && aligned16(x) && aligned16(W), st,
+                                                             "train_gemm_kernel (forward)", D)))
+        return rc;
     if (!gamma) return XVEC_OK;
     train_stats_kernel<RAGGED><<<col_grid(s), 256, 0, st>>>(z, s.N, Cout, s.Tp, p.part, L);
     if ((rc = terr().launch_ok("train_stats_kernel"))) return rc;
@@ -795,11 +852,13 @@ int train_forward(const float* x, int32_t B, int32_t T, int32_t Cin, const float
 
 // Launches: with BatchNorm the chunk sums of dy and dy x^ and their reduction (dbeta, dgamma); dz and its chunk sums, their
 // reduction (dbias); the dW product over row slices and, with more than one slice, the slab sum; the dx product.
-template <bool RAGGED>
+// DROPOUT: z is the post-dropout value and dz carries the scale of the kept elements; nothing else differs.
+template <bool RAGGED, bool DROPOUT = false>
 int train_backward(const float* dy, const float* x, const float* z, int32_t B, int32_t T, int32_t Cin, const float* W,
                    int32_t Cout, const int32_t* context_host, int32_t n_ctx, const float* gamma, const float* batch_mean,
                    const float* batch_var, float eps, float* dx, float* dW, float* dbias, float* dgamma, float* dbeta,
-                   const int32_t* lengths_dev, void* workspace, size_t workspace_bytes, xvec_stream stream) {
+                   const int32_t* lengths_dev, void* workspace, size_t workspace_bytes, xvec_stream stream,
+                   [[maybe_unused]] const Dropout<DROPOUT>& D = {}) {
     if (!dy || !x || !z || !W || !dW || !dbias)
         return terr().fail(XVEC_ERR_ARG, "null pointer: dy, x, z, W, dW and dbias are required");
     if (gamma && (!batch_mean || !batch_var || !dgamma || !dbeta))
@@ -820,9 +879,14 @@ int train_backward(const float* dy, const float* x, const float* z, int32_t B, i
         train_col_reduce_kernel<<<dim3(cols.x, 2), 64, 0, st>>>(p.part, s.chunks, 2, Cout, dbeta, dgamma);
         if ((rc = terr().launch_ok("train_col_reduce_kernel"))) return rc;
     }
-    train_dz_kernel<RAGGED><<<col_grid(s), 256, 0, st>>>(dy, z, s.N, Cout, s.Tp, gamma, batch_mean, batch_var, dgamma, dbeta, eps, p.dz,
-                                                        p.part, L);
-    if ((rc = terr().launch_ok("train_dz_kernel"))) return rc;
+    if constexpr (DROPOUT) {
+        train_dz_dropout_kernel<RAGGED><<<col_grid(s), 256, 0, st>>>(dy, z, s.N, Cout, s.Tp, gamma, batch_mean, batch_var, dgamma, dbeta,
+                                                                    eps, p.dz, p.part, L, D.scale);
+    } else {
+        train_dz_kernel<RAGGED><<<col_grid(s), 256, 0, st>>>(dy, z, s.N, Cout, s.Tp, gamma, batch_mean, batch_var, dgamma, dbeta, eps, p.dz,
+                                                            p.part, L);
+    }
+    if ((rc = terr().launch_ok(DROPOUT ? "train_dz_dropout_kernel" : "train_dz_kernel"))) return rc;
     train_col_reduce_kernel<<<dim3(cols.x, 1), 64, 0, st>>>(p.part, s.chunks, 1, Cout, dbias, nullptr);
     if ((rc = terr().launch_ok("train_col_reduce_kernel"))) return rc;
 

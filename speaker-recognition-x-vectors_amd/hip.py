@@ -156,6 +156,13 @@ _SIGS = {
                                                  _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
     "xvec_train_tail_backward_ragged": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp,
                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp]),
+    "xvec_tdnn_train_forward_dropout": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp,
+                                                  C.c_float, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp, C.c_float,
+                                                  C.c_uint64, C.c_uint64]),
+    "xvec_tdnn_train_backward_dropout": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, C.POINTER(_i32), _i32, _vp, _vp,
+                                                   _vp, C.c_float, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _vp,
+                                                   C.c_float]),
+    "xvec_dropout_keep_host": (C.c_int, [_vp, _i64, _i32, C.c_float, C.c_uint64, C.c_uint64]),
     "xvec_adam_step": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i64), _i32,
                                  C.c_double, C.c_double, C.c_double, C.c_double, _i64, _vp]),
 }

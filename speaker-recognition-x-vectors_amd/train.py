@@ -5,7 +5,12 @@ csrc/tdnn_train.hip): `tdnn_layer_train` is a torch.autograd.Function over the t
 segment-level Linear layers, the loss and Adam ride on torch ops on the same stream by default; with `tail="hip"` they run
 in HIP too (csrc/train_tail.hip): pooling through loss as ONE autograd.Function over xvec_train_tail_forward / _backward, the
 optimizer as `DeviceAdam` over xvec_adam_step.  Everything is fp32, the reference's own arithmetic.
-There is no fallback: a CPU tensor, dropout or a reduced precision raise.
+There is no fallback: a CPU tensor or a reduced precision raise.
+
+Dropout (`dropout_p` of the model, the reference's Linear -> ReLU -> Dropout -> BatchNorm): the forward product's epilogue
+draws the mask from a counter-based generator (csrc/dropout_mask.h: Philox4x32-10 on (seed, stream, row, channel)), so no
+mask is stored and a step is reproducible bit for bit.  It needs a seed: `XVectorTrainer(model, dropout_seed=...)`; layer i
+of training step k uses stream 8 k + i.
 
 Ragged batches: every entry point takes `lengths=` (valid frames per utterance of the padded batch x[B, T, C], as the
 extraction calls do) and then goes through the length-masked calls (xvec_*_ragged): the step computes what the valid frames
@@ -66,10 +71,11 @@ def _workspace(device, B, T, cin, cout, ctx, n_ctx):
 
 class _TdnnTrain(torch.autograd.Function):
     """y, batch_mean, batch_var = f(x, W, bias, gamma, beta): xvec_tdnn_train_forward / _backward.  Saved for the backward:
-    x, z (the ReLU output), W, gamma and the batch statistics; y is not needed."""
+    x, z (the ReLU output), W, gamma and the batch statistics; y is not needed.  `dropout` = (p, seed, stream): the
+    *_dropout calls, z is then the post-dropout value and the backward needs p alone."""
 
     @staticmethod
-    def forward(ctx, x, W, bias, gamma, beta, context, eps, lengths_dev=None):
+    def forward(ctx, x, W, bias, gamma, beta, context, eps, lengths_dev=None, dropout=None):
         B, T, cin = x.shape
         cout = W.shape[0]
         n_ctx = len(context)
@@ -90,12 +96,16 @@ class _TdnnTrain(torch.autograd.Function):
                     gamma.data_ptr() if bn else None, beta.data_ptr() if bn else None, eps, z.data_ptr(),
                     mean.data_ptr() if bn else None, var.data_ptr() if bn else None, y.data_ptr() if bn else None,
                     ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-            if lengths_dev is None:
+            if dropout is not None:
+                _check(_hip.lib.xvec_tdnn_train_forward_dropout(*args, None if lengths_dev is None else lengths_dev.data_ptr(),
+                                                                *dropout))
+            elif lengths_dev is None:
                 _check(_hip.lib.xvec_tdnn_train_forward(*args))
             else:
                 _check(_hip.lib.xvec_tdnn_train_forward_ragged(*args, lengths_dev.data_ptr()))
         ctx.save_for_backward(x, z, W, *((gamma, mean, var) if bn else ()))
         ctx.context, ctx.eps, ctx.bn, ctx.lengths_dev = tuple(context), eps, bn, lengths_dev
+        ctx.dropout_p = None if dropout is None else dropout[0]
         ctx.mark_non_differentiable(mean, var)
         return y, mean, var
 
@@ -120,11 +130,14 @@ class _TdnnTrain(torch.autograd.Function):
             args = (dy.data_ptr(), x.data_ptr(), z.data_ptr(), B, T, cin, W.data_ptr(), cout, carr, n_ctx, ptr(gamma),
                     ptr(mean), ptr(var), ctx.eps, ptr(dx), dW.data_ptr(), db.data_ptr(), ptr(dgamma), ptr(dbeta),
                     ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-            if ctx.lengths_dev is None:
+            if ctx.dropout_p is not None:
+                _check(_hip.lib.xvec_tdnn_train_backward_dropout(
+                    *args, None if ctx.lengths_dev is None else ctx.lengths_dev.data_ptr(), ctx.dropout_p))
+            elif ctx.lengths_dev is None:
                 _check(_hip.lib.xvec_tdnn_train_backward(*args))
             else:
                 _check(_hip.lib.xvec_tdnn_train_backward_ragged(*args, ctx.lengths_dev.data_ptr()))
-        return dx, dW, db, dgamma, dbeta, None, None, None
+        return dx, dW, db, dgamma, dbeta, None, None, None, None
 
 
 def _tail_workspace(device, B, tp, c, h, k):
@@ -277,17 +290,29 @@ class DeviceAdam:
             self.state[i] = {"step": int(st["step"]), "exp_avg": moment(st["exp_avg"]), "exp_avg_sq": moment(st["exp_avg_sq"])}
 
 
-def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer, lengths=None) -> torch.Tensor:
+def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer, lengths=None, dropout=None) -> torch.Tensor:
     """`layer(x)` as the reference computes it under model.train() (tdnn_layer.py:26-41): x[B, T, in] ->
     y[B, T - span, out] with a graph through the layer's own parameters, BatchNorm on the batch statistics, and the
     layer's running_mean / running_var / num_batches_tracked updated as nn.BatchNorm1d updates them in training mode.
 
     `lengths` (a list or a tensor of B integers in [span + 1, T]): the valid frames of a padded batch.  Utterance b then has
     lengths[b] - span valid output frames -- the next layer's lengths -- which alone form the BatchNorm batch and receive
-    gradients; the other rows of y are exactly 0, and nothing depends on what x holds past its lengths."""
+    gradients; the other rows of y are exactly 0, and nothing depends on what x holds past its lengths.
+
+    `dropout` = (seed, stream), two integers below 2^64: a layer with dropout_p != 0 needs them.  They name the mask (include/
+    xvec_train.h, "Dropout"): the same pair gives the same mask, whatever the batch; BatchNorm and the running statistics see
+    the post-dropout activations, as torch's do.  A layer with dropout_p == 0 ignores them."""
     _require_gpu(x, "tdnn_layer_train")
+    if layer.dropout_p and dropout is None:
+        raise RuntimeError(f"tdnn_layer_train: dropout_p = {layer.dropout_p} needs dropout=(seed, stream): the mask is a "
+                           f"function of them, there is no hidden generator state")
     if layer.dropout_p:
-        raise RuntimeError(f"tdnn_layer_train: dropout_p = {layer.dropout_p} is outside this build's scope (only 0)")
+        seed, stream = (int(v) for v in dropout)
+        if not (0 <= seed < 1 << 64 and 0 <= stream < 1 << 64):
+            raise ValueError(f"tdnn_layer_train: dropout = {dropout!r}; seed and stream are integers in [0, 2^64)")
+        dropout = (float(layer.dropout_p), seed, stream)
+    else:
+        dropout = None
     if x.dim() != 3 or x.shape[2] != layer.input_size:
         raise ValueError(f"tdnn_layer_train: expected x[B, T, {layer.input_size}], got {tuple(x.shape)}")
     W = layer.linear.weight
@@ -307,7 +332,10 @@ def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer, lengths=None) -> torch.T
         raise ValueError("tdnn_layer_train: BatchNorm in training mode needs more than one row per channel")
     args = (x, W, layer.linear.bias, norm.weight if norm is not None else None, norm.bias if norm is not None else None, context,
             norm.eps if norm is not None else 0.0)
-    y, mean, var = _TdnnTrain.apply(*args) if lengths is None else _TdnnTrain.apply(*args, lengths.dev)
+    if dropout is not None:
+        y, mean, var = _TdnnTrain.apply(*args, None if lengths is None else lengths.dev, dropout)
+    else:
+        y, mean, var = _TdnnTrain.apply(*args) if lengths is None else _TdnnTrain.apply(*args, lengths.dev)
     if norm is not None and norm.track_running_stats:
         with torch.no_grad():
             norm.num_batches_tracked += 1
@@ -320,26 +348,36 @@ def tdnn_layer_train(x: torch.Tensor, layer: TdnnLayer, lengths=None) -> torch.T
 class XVectorTrainer:
     """The training half of the reference's LightningModule (main.py:97-131, 148) over an XVectorModel's own parameters.
     It does not look at `model.training`: `training_step` always uses batch statistics, `validation_step` always the
-    running ones."""
+    running ones.
+
+    `dropout_seed` (an integer in [0, 2^64)): required by a model with dropout_p != 0, ignored by one without.  Layer i of
+    the k-th `training_step` call (k from 0) drops by the mask of (dropout_seed, stream 8 k + i); `dropout_state()` /
+    `load_dropout_state()` carry (seed, k) across a checkpoint, so that a resumed run continues the sequence."""
 
     _HPARAMS = ("x_vec_extract_layer", "batch_size", "learning_rate", "augmentations_per_sample", "data_folder_path")
 
-    def __init__(self, model: XVectorModel, tail: str = "torch"):
+    def __init__(self, model: XVectorModel, tail: str = "torch", dropout_seed=None):
         if tail not in ("torch", "hip"):
             raise ValueError(f"XVectorTrainer: tail = {tail!r}; 'torch' (pooling, segment layers, loss and Adam on torch ops) "
                              f"or 'hip' (csrc/train_tail.hip)")
-        if model.hparams["dropout_p"]:
-            raise RuntimeError(f"XVectorTrainer: dropout_p = {model.hparams['dropout_p']} is outside this build's scope (only 0)")
+        if model.hparams["dropout_p"] and dropout_seed is None:
+            raise RuntimeError(f"XVectorTrainer: dropout_p = {model.hparams['dropout_p']} needs a seed: pass dropout_seed= "
+                               f"(the masks are a function of it and of the step count, which makes a run reproducible)")
+        if dropout_seed is not None and not 0 <= int(dropout_seed) < 1 << 64:
+            raise ValueError(f"XVectorTrainer: dropout_seed = {dropout_seed!r}; an integer in [0, 2^64)")
         if model.precision not in ("fp32", "f32"):
             raise RuntimeError(f"XVectorTrainer: precision {model.precision!r}; training runs in fp32 only")
         self.model = model
         self.tail = tail
         self.optimizer = None
+        self._dropout_seed = int(dropout_seed) if model.hparams["dropout_p"] else None      # None: no dropout in this run
+        self._dropout_step = 0              # training_step calls so far
 
     # ------------------------------------------------------------------ main.py:66-75 with a graph
     def _frames(self, x: torch.Tensor, lengths=None):
         """The five frame-level layers: x[B, T, in] -> h5[B, T - 14, 1500]; with `lengths`, (h5, the pooled lengths): every
-        layer's lengths are the ones before less its span, uploaded as one table per step."""
+        layer's lengths are the ones before less its span, uploaded as one table per step.  With dropout, layer i uses the
+        stream 8 k + i of the step count k as it stands."""
         host = None
         if lengths is not None and x.dim() == 3:     # refused on the host first: a bad length never reaches a launch
             host = _host_lengths(lengths, x.shape[0], TOTAL_CONTEXT + 2, x.shape[1], "XVectorTrainer")
@@ -350,9 +388,10 @@ class XVectorTrainer:
             raise ValueError(f"T={x.shape[1]}: training needs T >= {TOTAL_CONTEXT + 2} (two pooled frames for torch.std)")
         m = self.model
         h = x.float()
+        drop = lambda i: None if self._dropout_seed is None else (self._dropout_seed, 8 * self._dropout_step + i)
         if lengths is None:
-            for layer in m.time_context_layers:
-                h = tdnn_layer_train(h, layer)
+            for i, layer in enumerate(m.time_context_layers):
+                h = tdnn_layer_train(h, layer, dropout=drop(i))
             return h
         table = [host]
         for layer in m.time_context_layers:
@@ -360,7 +399,7 @@ class XVectorTrainer:
             table.append([v - span for v in table[-1]])
         dev = torch.tensor(table, dtype=torch.int32).to(x.device)
         for i, layer in enumerate(m.time_context_layers):
-            h = tdnn_layer_train(h, layer, _Lengths(table[i], dev[i]))
+            h = tdnn_layer_train(h, layer, _Lengths(table[i], dev[i]), drop(i))
         return h, _Lengths(table[-1], dev[-1])
 
     def logits(self, x: torch.Tensor, lengths=None) -> torch.Tensor:
@@ -390,6 +429,12 @@ class XVectorTrainer:
         return torch.cat((mean, std), 1)
 
     def training_step(self, batch, batch_index=0, lengths=None):
+        try:
+            return self._training_step(batch, lengths)
+        finally:
+            self._dropout_step += 1         # counted per call, whatever became of it: step k always means streams 8 k + i
+
+    def _training_step(self, batch, lengths):
         samples, labels, ids = batch
         if self.tail == "hip":
             m = self.model
@@ -436,9 +481,26 @@ class XVectorTrainer:
         self.optimizer.step()
         return loss.detach()
 
+    def dropout_state(self):
+        """{"seed", "step"} of a run with dropout -- what names the masks of the next training_step -- or None without."""
+        return None if self._dropout_seed is None else {"seed": self._dropout_seed, "step": self._dropout_step}
+
+    def load_dropout_state(self, state):
+        """Continue the mask sequence of `dropout_state()` (a checkpoint's "xvec_dropout" entry)."""
+        if self._dropout_seed is None:
+            raise RuntimeError("XVectorTrainer.load_dropout_state: this run has no dropout (dropout_p == 0)")
+        seed, step = int(state["seed"]), int(state["step"])
+        if not 0 <= seed < 1 << 64 or step < 0:
+            raise ValueError(f"XVectorTrainer.load_dropout_state: {state!r}")
+        self._dropout_seed, self._dropout_step = seed, step
+
     def save_checkpoint(self, path):
-        """A Lightning-shaped file: `state_dict` and `hyper_parameters` (what save_hyperparameters() stores, main.py:56)."""
+        """A Lightning-shaped file: `state_dict` and `hyper_parameters` (what save_hyperparameters() stores, main.py:56).  A
+        run with dropout adds "xvec_dropout", its `dropout_state()`; without dropout the file has the two keys alone."""
         m = self.model
         hp = dict(m.hparams)
         hp.update({k: getattr(m, k) for k in self._HPARAMS})
-        torch.save({"state_dict": {k: v.detach().cpu() for k, v in m.state_dict().items()}, "hyper_parameters": hp}, path)
+        ckpt = {"state_dict": {k: v.detach().cpu() for k, v in m.state_dict().items()}, "hyper_parameters": hp}
+        if self._dropout_seed is not None:
+            ckpt["xvec_dropout"] = self.dropout_state()
+        torch.save(ckpt, path)
