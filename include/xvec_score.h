@@ -38,7 +38,9 @@ size_t xvec_score_workspace_bytes(int64_t n_enroll, int64_t n_test, int32_t dim)
 /* fast_PLDA_scoring (speechbrain.processing.PLDA_LDA, as called at plda_classifier.py:86):
  *   e = enroll - mean, t = test - mean
  *   scores[i,j] = scaling * ( 0.5 e_i' Phi e_i + 0.5 t_j' Phi t_j + e_i' Psi t_j + plda_cst )
- * (when phi_t == psi_t + dim*dim, i.e. the caller keeps [Psi^T ; Phi^T] stacked in one buffer, [e Psi | e Phi] is formed in one launch)
+ * (when phi_t == psi_t + dim*dim, i.e. the caller keeps [Psi^T ; Phi^T] stacked in one buffer, [e Psi | e Phi] is formed in one
+ * launch; with psi_t and phi_t anywhere else the library takes its two-product branch -- e Psi in one launch, the row dots of
+ * e Phi in a second -- and gives the same scores to rounding: tests/test_score_edges_gpu.py runs both)
  * psi_t / phi_t are the TRANSPOSES of Psi / Phi ([dim,dim], row-major), plda_cst the Gaussian
  * constant; the host derives them from (F, Sigma) once per model (scoring.PldaScorer).
  * test == NULL scores enroll against itself (the reference's use: plda_score_stat.py:19-20). */
@@ -58,7 +60,9 @@ int xvec_plda_score_lowrank(const double* enroll, int64_t n_enroll, const double
                             double plda_cst, double scaling_factor, double* scores, void* workspace,
                             size_t workspace_bytes, xvec_stream stream);
 
-/* Cosine scoring: scores[i,j] = <enroll_i, test_j> / (|enroll_i| |test_j|).  test == NULL as above. */
+/* Cosine scoring: scores[i,j] = <enroll_i, test_j> / (|enroll_i| |test_j|), 0 where either vector is zero.  test == NULL
+ * as above; the diagonal of such a self call is exactly 1.0 for every non-zero row (the rounded product would be a few
+ * 2^-52 off). */
 int xvec_cosine_score(const double* enroll, int64_t n_enroll, const double* test, int64_t n_test,
                       int32_t dim, double* scores, void* workspace, size_t workspace_bytes,
                       xvec_stream stream);

@@ -10,6 +10,7 @@
 #include "../../include/xvec_hip.h"
 #include "../../include/xvec_score.h"
 #include "host_support.h"
+#include "score_tiles.h"
 #include "tdnn_common.h"
 
 namespace xvec {
@@ -56,49 +57,8 @@ struct GemmArgs {
     int dot_col0;
 };
 
-// Tile t of the walk -> (row tile, column tile).  The tiles are walked in 8 x 8 SUPERTILES (bands of eight row tiles, inside a
-// band eight column tiles at a time, row-major inside the supertile): the 64 consecutive tiles an XCD's blocks work on at a time
-// (xcd_remap) then share eight row operands and eight column operands -- 8 MiB at K = 512, the XCD's L2 twice over -- instead
-// of two row operands and ALL column operands (row-major walk, round 4: 950 MB per 4874 x 4874 score matrix for 230 MB of
-// operands and scores).  Bijective for any tiles_m x tiles_n (the last band / the last supertile of a band are narrower).
-__device__ __forceinline__ void tile_rc(int t, int tiles_m, int tiles_n, int& r, int& c) {
-    const int band = t / (8 * tiles_n);
-    const int tb = t - band * 8 * tiles_n;
-    const int h = min(8, tiles_m - 8 * band);
-    const int sc = tb / (8 * h);
-    const int w = min(8, tiles_n - 8 * sc);
-    const int within = tb - sc * 8 * h;
-    r = band * 8 + within / w;
-    c = sc * 8 + within % w;
-}
-
-// The same walk over the tiles ON OR ABOVE the diagonal of a square tile grid (T x T, tile row <= tile column): band by band,
-// the diagonal supertile first (its upper triangle row by row), then the band's other supertiles as above.  t < T (T + 1) / 2.
-__device__ __forceinline__ void tile_rc_sym(int t, int T, int& r, int& c) {
-    int band = 0;
-    for (;;) {                                   // (T + 7) / 8 iterations at most, scalar
-        const int h = min(8, T - 8 * band);
-        const int cnt = h * (h + 1) / 2 + h * (T - 8 * band - h);
-        if (t < cnt) break;
-        t -= cnt;
-        ++band;
-    }
-    const int h = min(8, T - 8 * band);
-    int i = 0;
-    for (; i < h; ++i) {                         // diagonal supertile: row i holds h - i tiles
-        if (t < h - i) {
-            r = band * 8 + i;
-            c = band * 8 + i + t;
-            return;
-        }
-        t -= h - i;
-    }
-    const int sc = t / (8 * h);                  // (h == 8 here: a shorter band is the last one and has no supertile to its right)
-    const int w = min(8, T - 8 * (band + 1 + sc));
-    const int within = t - sc * 8 * h;
-    r = band * 8 + within / w;
-    c = (band + 1 + sc) * 8 + within % w;
-}
+using score_tiles::tile_rc;          // the supertile walks of the tiles: csrc/score_tiles.h
+using score_tiles::tile_rc_sym;
 
 // two consecutive doubles of row `row` at column k (zero outside the matrix)
 template <bool VEC>
@@ -346,6 +306,14 @@ __global__ void normalize_rows_kernel(const double* __restrict__ x, int64_t n, i
     for (int d = lane; d < dim; d += 64) out[row * dim + d] = x[row * dim + d] * inv;
 }
 
+// the diagonal of a cosine self call: <a, a> / |a|^2 is 1 for every row that does not normalise to zero, while the product of the
+// ROUNDED unit rows is off by the rounding of 1 / |a| twice and that of dim fused multiply-adds (4.5 x 2^-52 at dim 130).  A zero
+// row's 0.0, a NaN and an element no tile wrote stay as they are.
+__global__ void unit_diagonal_kernel(double* __restrict__ c, int64_t n, int64_t ldc) {
+    const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (i < n && c[i * ldc + i] > 0.0) c[i * ldc + i] = 1.0;
+}
+
 thread_local ErrorChannel g_serr;
 
 // the scorers' fused forms of one product (see GemmArgs)
@@ -369,26 +337,12 @@ int gemm_nt(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t 
     const int num_cu = device_cu_count();      // two persistent blocks per CU
     const bool sym = ex && ex->sym, pre = ex && ex->pre;
     if (sym && M != N) return g_serr.fail(XVEC_ERR_ARG, "symmetric walk needs a square score matrix");
-    // Two tilings (a symmetric walk visits only the tiles on or above the diagonal):
-    //   128 x 128, two blocks per CU (255 registers);  64 x 64, FOUR blocks per CU (121 registers, 32 KiB of LDS each).
-    // Per CU the two finish the same work in the same time within a few per cent (a round of four 64 x 64 tiles against a round
-    // of two 128 x 128 ones: 0.49 for K <= 256, 0.53 for longer K, measured N = 1200 ... 16384, profiles/experiments/README.md), and
-    // a block slot walks ceil(tiles / slots) tiles -- so what decides is how full the LAST round is.  The reference's self-score
-    // of 4874 vectors is 780 tiles of 128 x 128 on 512 slots (two rounds, the second half empty) against 3003 of 64 x 64 on 1024
-    // (three rounds): 0.261 -> 0.200 ms in the low-rank form, 0.487 -> 0.411 dense (round 6; until then the 64 x 64 kernel ran two
-    // blocks per CU and served only products under a tile and a half per slot).
+    // 128 x 128 tiles, two blocks per CU, or 64 x 64, four blocks per CU: the rule and its reasons are csrc/score_tiles.h
     const int64_t slots128 = 2 * (int64_t)num_cu, slots64 = 4 * (int64_t)num_cu;
-    auto count = [&](int64_t ts) {
-        const int64_t tm = (M + ts - 1) / ts, tn = (N + ts - 1) / ts;
-        return sym ? tm * (tm + 1) / 2 : tm * tn;
-    };
-    // (the prelude product stays on 64 x 64 tiles at every size: with the centring and the row dots on top, the 128 x 128 form
-    //  needs more registers than it has)
-    const int64_t r128 = (count(128) + slots128 - 1) / slots128, r64 = (count(64) + slots64 - 1) / slots64;
-    const bool small = pre || count(128) * 2 < 3 * slots128 || r64 * (K <= 256 ? 49 : 53) < r128 * 100;
-    const int ts = small ? 64 : 128;
+    const int ts = score_tiles::gemm_tile_size(M, N, K, sym, pre, num_cu);
+    const bool small = ts == 64;
     const int64_t tm = (M + ts - 1) / ts, tn = (N + ts - 1) / ts;
-    const int64_t n_tiles = count(ts);
+    const int64_t n_tiles = score_tiles::tile_count(M, N, sym, ts);
     if (n_tiles > 0x7fffffff) return g_serr.fail(XVEC_ERR_ARG, "score matrix too large for one launch");
     GemmArgs g{};
     g.A = A; g.B = B; g.rowv = rowv; g.colv = colv; g.C = C;
@@ -618,7 +572,10 @@ int xvec_cosine_score(const double* enroll, int64_t n_enroll, const double* test
     }
     GemmExtra ex;
     ex.sym = self;                        // <a, b> = <b, a>: walk the upper triangle, mirror the rest
-    return gemm_nt(p.ec, dim, tc, dim, n_enroll, n_test, dim, nullptr, nullptr, 0.0, 1.0, scores, n_test, s, &ex);
+    if ((rc = gemm_nt(p.ec, dim, tc, dim, n_enroll, n_test, dim, nullptr, nullptr, 0.0, 1.0, scores, n_test, s, &ex))) return rc;
+    if (!self) return XVEC_OK;
+    unit_diagonal_kernel<<<(unsigned)((n_enroll + 255) / 256), 256, 0, s>>>(scores, n_enroll, n_enroll);
+    return g_serr.launch_ok("unit_diagonal_kernel");
 }
 
 }  // extern "C"

@@ -70,7 +70,10 @@ def scattered(pos, neg, seed, n_rows=300, n_cols=411, pad=5):
 
 # ------------------------------------------------------------------ the sort
 
-@pytest.mark.parametrize("n", [1, 2, 255, 256, 257, 37720, 2 ** 20 + 3])
+# (1024: a wave's share of a tile in the scatter; 4096: a tile; 65536 = 16 tiles: the digit table of 256 x tiles entries fills
+#  one scan chunk exactly, 17 tiles spill into a second)
+@pytest.mark.parametrize("n", [1, 2, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 8191, 8192, 8193, 37720, 65535, 65536,
+                               65537, 69633, 2 ** 20 + 3])
 @pytest.mark.parametrize("ties", [False, True])
 def test_sorted_pairs_equal_a_stable_sort_bit_for_bit(n, ties):
     from xvector_amd import evaluate as ev

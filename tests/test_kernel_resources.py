@@ -34,7 +34,7 @@ def test_no_kernel_uses_scratch():
     for name, r in results["mfcc.hip"].items():
         if "mfcc512_kernel" in name:
             assert r["vgprs"] + r.get("agprs", 0) <= 96 and r["lds"] <= 32 * 1024 and r["occupancy"] == 5, f"{name}: {r}"
-    assert len(results["score.hip"]) == 7         # gemm_nt_f64_kernel<VEC, WT, PRE>: 2 x (2 + 1) + normalize_rows_kernel
+    assert len(results["score.hip"]) == 8         # gemm_nt_f64_kernel<VEC, WT, PRE>: 2 x (2 + 1) + normalize_rows_kernel + unit_diagonal_kernel
     assert total >= 41
 
 
