@@ -24,6 +24,18 @@
  *   - every function returns XVEC_OK (0) or an error code and never throws; the message
  *     for the last error on the calling thread is available from xvec_last_error();
  *   - one handle per device; distinct handles may be used from distinct threads.
+ *
+ * Segments (xvec_forward_segments, xvec_stat_pool_segments)
+ *   A batch is B recordings, packed.  A SEGMENT is (utt, start, len) in INPUT frames of recording utt, with 0 <= start,
+ *   len >= 15 and start + len <= T_utt.
+ *   - Its result is, to rounding, what the whole path gives on the crop x[utt, start : start + len] alone (x-vector,
+ *     logits, layer 7 or the pooled [3000] statistics, by mode).  This is exact and no approximation: the five frame-level
+ *     layers are valid convolutions with a per-frame eval BatchNorm, output frame j of layer 5 depends on input frames
+ *     j .. j + 14 only, so the crop's layer-5 rows ARE rows start .. start + len - 15 of the recording's.  The stack runs once
+ *     per recording and every segment pools its own rows.
+ *   - Segments may overlap, repeat, come in any order and skip frames.
+ *   - Row i of the output belongs to segment i and depends on no other segment of the list.
+ *   - len == 15 gives one pooled frame and a NaN std, as torch.std and xvec_stat_pool do.
  */
 #ifndef XVEC_HIP_H
 #define XVEC_HIP_H
@@ -143,6 +155,22 @@ int xvec_forward_packed(xvec_handle* h, const float* x_packed, const int64_t* of
                         int32_t B, int mode, int dtype, float* out, void* workspace,
                         size_t workspace_bytes, xvec_stream stream);
 
+/* The same stack run ONCE over B packed recordings, then one result per segment (see "Segments" at the head of this file):
+ * seg_utt_dev / seg_start_dev / seg_len_dev are DEVICE int32[n_segments]; out is [n_segments, .] by mode, as xvec_forward's.
+ * Layer 5 writes its rows to the workspace instead of pooling in its epilogue (fp32 rows in XVEC_F32 / XVEC_BF16X3, bf16 rows
+ * in XVEC_BF16), a small kernel turns the segments into row ranges, and xvec_stat_pool_segments' kernel pools each range; the
+ * segment-level layers then run with M = n_segments.  Overlapping windows cost one run of the frame-level stack, not one per
+ * window.  Errors and limits as xvec_forward_packed: everything is planned before anything is enqueued, XVEC_ERR_TOO_LARGE
+ * leaves stream and handle as they were (also: more than 65 535 x 16 = 1 048 560 segments in one call).  The host cannot see the device segment
+ * arrays and does not validate them: a segment that breaks the constraints gives a NaN row and reads nothing.  n_segments < 1
+ * or a null array: XVEC_ERR_ARG.  Offsets are staged as the ragged entries stage them (not capturable into a graph).
+ * workspace >= xvec_segments_workspace_bytes(h, offsets_host[B], B, n_segments) (0 for a null handle or a count < 1). */
+size_t xvec_segments_workspace_bytes(const xvec_handle* h, int64_t total_frames, int32_t n_utts, int64_t n_segments);
+int xvec_forward_segments(xvec_handle* h, const float* x_packed, const int64_t* offsets_host, int32_t B,
+                          const int32_t* seg_utt_dev, const int32_t* seg_start_dev, const int32_t* seg_len_dev,
+                          int64_t n_segments, int mode, int dtype, float* out, void* workspace, size_t workspace_bytes,
+                          xvec_stream stream);
+
 /* ---- per-stage entry points (unit tests; each mirrors one reference function) --------
  * TdnnLayer.forward (tdnn_layer.py:26-41), eval mode, for time_context_layers.{layer}:
  * x[B,T,in] -> y[B,T-(c[-1]-c[0]),out].  workspace >= xvec_workspace_bytes(h, B*T, B). */
@@ -157,6 +185,22 @@ int xvec_tdnn_pool_layer(xvec_handle* h, const float* x, int32_t B, int32_t T, i
  * lengths_dev: NULL or DEVICE int32[B] valid-frame counts (mask).  Stand-alone: no handle. */
 int xvec_stat_pool(const float* x, const int32_t* lengths_dev, int32_t B, int32_t T, int32_t C,
                    float* out, xvec_stream stream);
+/* XVectorModel.stat_pool over row ranges of a row matrix y[rows, ldy] with C <= ldy channels (elem 0: fp32, 1: bf16):
+ * segment i = rows [seg_row_dev[i], seg_row_dev[i] + seg_n_dev[i]) (DEVICE int64 / int32 arrays) -> out[i, 2C] = mean ‖ unbiased
+ * std.  One pass with the segment's own first row as the pivot of its sums: a channel constant over the segment comes out
+ * with std == 0.0 and mean == the constant exactly, whatever it does outside.  Fixed summation order, no atomics: repeat calls
+ * are bit-identical, and a segment's row of out depends on its rows alone.  scale_dev / shift_dev: both NULL, or a per-channel
+ * affine map of the rows applied to the statistics instead (mean = shift + scale * mean_r, std = |scale| * std_r: a deferred
+ * BatchNorm).  16-byte loads when the base is 16-byte aligned, ldy * element size is a multiple of 16 and C rounded up to the
+ * vector (4 fp32 / 8 bf16) fits in ldy -- the padding columns C..ldy of a row may then be read, never stored; element-wise
+ * otherwise.  A segment with n <= 0, row0 < 0 or row0 + n > rows reads nothing and gets a NaN row; n == 1 gives a NaN std.
+ * Stand-alone: no handle. */
+int xvec_stat_pool_segments(const void* y, int elem, int64_t rows, int32_t ldy, int32_t C, const int64_t* seg_row_dev,
+                            const int32_t* seg_n_dev, int64_t n_segments, const float* scale_dev, const float* shift_dev,
+                            float* out, xvec_stream stream);
+/* Which variant xvec_stat_pool_segments runs for this base, element type, row stride and width: 1 the 16-byte loads, 0 the
+ * element-wise one, -1 for arguments the call refuses.  Host arithmetic only: y is not dereferenced, no device is touched. */
+int xvec_stat_pool_segments_vector(const void* y, int elem, int32_t ldy, int32_t C);
 /* nn.Linear (+ optional F.relu) of segment_layer6 / segment_layer7 / output
  * (main.py:72-75,87-90): x[M,in] -> y[M,out]. */
 int xvec_affine(xvec_handle* h, int which, const float* x, int32_t M, int relu, float* y,

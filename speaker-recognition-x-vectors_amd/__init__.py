@@ -9,12 +9,12 @@ from . import synth  # noqa: F401  (numpy only)
 __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontEnd", "PldaScorer", "hip", "extract",
            "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject", "evaluate", "TrialList", "TrialResult",
            "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan",
-           "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam"]
+           "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam", "sliding_windows", "plan_segment_calls"]
 
 
 def __getattr__(name):
     # torch-dependent parts load lazily so that `synth` stays importable anywhere
-    if name in ("XVectorModel", "TdnnLayer", "get_time_context"):
+    if name in ("XVectorModel", "TdnnLayer", "get_time_context", "sliding_windows", "plan_segment_calls"):
         from . import model
         return getattr(model, name)
     if name == "MfccFrontEnd":

@@ -10,6 +10,7 @@
 
 #include "../../include/xvec_hip.h"
 #include "host_support.h"
+#include "pool_segments.h"
 #include "tdnn_common.h"   // wino_pair_count
 #include "xvec_internal.h"
 
@@ -492,8 +493,10 @@ int finalize_pool(xvec_handle* h, const LayerPlan& l5, float* pooled, hipStream_
 // Layer 1 reads the caller's rows (guarded against the end of the buffer and the K tail; bf16 rounds them on the way in,
 // bf16x3 reads them as they are or their hi / lo split); every activation buffer holds fp32, bf16 or two bf16 planes in the
 // space of one fp32.  Layer 5 carries the statistics-pooling epilogue: its [frames,1500] output stays on chip.
+// l5_rows (xvec_forward_segments): layer 5 writes its rows to the act5 region instead -- fp32 with its BatchNorm applied
+// (Dst::kF32) in fp32 and bf16x3, its bf16 ReLU output with the BatchNorm left to the pooling (Dst::kAct) in plain bf16.
 int plan_stack(const xvec_handle* h, const float* x_rows, int ldx, const int64_t* offs_dev, int B, int fixed_T, const Plan& p,
-               int dtype, char* ws, LayerPlan (&lp)[XVEC_NUM_TDNN]) {
+               int dtype, char* ws, LayerPlan (&lp)[XVEC_NUM_TDNN], bool l5_rows = false) {
     const Prec prec = dtype == XVEC_F32 ? Prec::kF32 : dtype == XVEC_BF16 ? Prec::kBf16 : Prec::kBf16x3;
     if (prec != Prec::kF32 && p.total > 0x7fffffff) return g_err.fail(XVEC_ERR_TOO_LARGE, "too many frames for one bf16 batch; split it");
     const int nh = h->geo[0].n_pad;
@@ -512,7 +515,11 @@ int plan_stack(const xvec_handle* h, const float* x_rows, int ldx, const int64_t
         c.layer = l;
         c.map.cum += h->geo[l].ctx_span;
         c.rows_out = p.total - (int64_t)B * c.map.cum;
-        if (l == XVEC_NUM_TDNN - 1) {
+        if (l == XVEC_NUM_TDNN - 1 && l5_rows) {
+            c.mode.dst = prec == Prec::kBf16 ? Dst::kAct : Dst::kF32;
+            c.Y = ws + p.act5;
+            c.y_plane = 0;
+        } else if (l == XVEC_NUM_TDNN - 1) {
             c.mode.dst = Dst::kPool;
             c.Y = nullptr;
             c.y_plane = 0;
@@ -532,12 +539,43 @@ int plan_stack(const xvec_handle* h, const float* x_rows, int ldx, const int64_t
     return XVEC_OK;
 }
 
+// The segment layers of `mode` (not XVEC_MODE_POOLED) on pooled[M, 3000]: s6 / s7 hold [M, x_vector_size] each, scr is scratch
+// the split-K forms may overwrite.
+int segment_layers(xvec_handle* h, const float* pooled, int M, float* s6, float* s7, float* scr, size_t scr_bytes, int mode,
+                   int dtype, float* out, hipStream_t s) {
+    const int xv = h->cfg.x_vector_size, K6 = 2 * XVEC_POOL_CHANNELS;
+    // plain bf16 (parity bar 1e-2): the segment layers' products as bf16x3 (affine.hip); XVEC_BF16X3 promises the fp32
+    // bar end to end and keeps the fp32 MFMAs here (x3 segment layers measured 3x the fp32 ones' error: 6e-6)
+    const bool w3 = dtype == XVEC_BF16;
+    if (mode == XVEC_MODE_XVEC6) {
+        StageTimer t(h, T_SEG6, s);
+        HIP_TRY(launch_affine_f32(pooled, h->affW[0], h->affB[0], out, M, xv, K6, 0, s, scr, scr_bytes, w3 ? h->affW3[0] : nullptr));
+        return XVEC_OK;
+    }
+    {
+        StageTimer t(h, T_SEG6, s);
+        HIP_TRY(launch_affine_f32(pooled, h->affW[0], h->affB[0], s6, M, xv, K6, 1, s, scr, scr_bytes, w3 ? h->affW3[0] : nullptr));
+    }
+    if (mode == XVEC_MODE_XVEC7) {
+        StageTimer t(h, T_SEG7, s);
+        HIP_TRY(launch_affine_f32(s6, h->affW[1], h->affB[1], out, M, xv, xv, 0, s, scr, scr_bytes, w3 ? h->affW3[1] : nullptr));
+        return XVEC_OK;
+    }
+    {
+        StageTimer t(h, T_SEG7, s);
+        HIP_TRY(launch_affine_f32(s6, h->affW[1], h->affB[1], s7, M, xv, xv, 1, s, scr, scr_bytes, w3 ? h->affW3[1] : nullptr));
+    }
+    {
+        StageTimer t(h, T_OUT, s);
+        HIP_TRY(launch_affine_f32(s7, h->affW[2], h->affB[2], out, M, h->cfg.num_classes, xv, 0, s, scr, scr_bytes, w3 ? h->affW3[2] : nullptr));
+    }
+    return XVEC_OK;
+}
+
 // Run the planned stack (x_rows, ldx as planned) and the segment layers of `mode`.
 int forward_rows(xvec_handle* h, const LayerPlan (&lp)[XVEC_NUM_TDNN], const float* x_rows, int ldx, int B, const Plan& p,
                  int mode, int dtype, float* out, char* ws, hipStream_t s) {
     float* pooled = mode == XVEC_MODE_POOLED ? out : reinterpret_cast<float*>(ws + p.pooled);
-    float* s6 = reinterpret_cast<float*>(ws + p.seg6);
-    float* s7 = reinterpret_cast<float*>(ws + p.seg7);
     int rc;
     if (lp[0].mode.src == Src::kRows16) {    // [total, ldx] fp32 -> bf16 hi and lo planes (same row stride in elements)
         StageTimer t(h, T_PACK, s);
@@ -550,36 +588,31 @@ int forward_rows(xvec_handle* h, const LayerPlan (&lp)[XVEC_NUM_TDNN], const flo
         if ((rc = finalize_pool(h, lp[XVEC_NUM_TDNN - 1], pooled, s))) return rc;
     }
     if (mode == XVEC_MODE_POOLED) return XVEC_OK;
-    const int xv = h->cfg.x_vector_size, K6 = 2 * XVEC_POOL_CHANNELS;
-    // plain bf16 (parity bar 1e-2): the segment layers' products as bf16x3 (affine.hip); XVEC_BF16X3 promises the fp32
-    // bar end to end and keeps the fp32 MFMAs here (x3 segment layers measured 3x the fp32 ones' error: 6e-6)
-    const bool w3 = dtype == XVEC_BF16;
-    // the frame-level activations are dead from here on: layers 1-4's buffers serve as split-K scratch
-    float* scr = reinterpret_cast<float*>(ws + p.actA);
-    const size_t scr_bytes = (p.actB - p.actA) * 2;                 // actA and actB are adjacent
-    if (mode == XVEC_MODE_XVEC6) {
-        StageTimer t(h, T_SEG6, s);
-        HIP_TRY(launch_affine_f32(pooled, h->affW[0], h->affB[0], out, B, xv, K6, 0, s, scr, scr_bytes, w3 ? h->affW3[0] : nullptr));
-        return XVEC_OK;
-    }
-    {
-        StageTimer t(h, T_SEG6, s);
-        HIP_TRY(launch_affine_f32(pooled, h->affW[0], h->affB[0], s6, B, xv, K6, 1, s, scr, scr_bytes, w3 ? h->affW3[0] : nullptr));
-    }
-    if (mode == XVEC_MODE_XVEC7) {
-        StageTimer t(h, T_SEG7, s);
-        HIP_TRY(launch_affine_f32(s6, h->affW[1], h->affB[1], out, B, xv, xv, 0, s, scr, scr_bytes, w3 ? h->affW3[1] : nullptr));
-        return XVEC_OK;
-    }
-    {
-        StageTimer t(h, T_SEG7, s);
-        HIP_TRY(launch_affine_f32(s6, h->affW[1], h->affB[1], s7, B, xv, xv, 1, s, scr, scr_bytes, w3 ? h->affW3[1] : nullptr));
-    }
-    {
-        StageTimer t(h, T_OUT, s);
-        HIP_TRY(launch_affine_f32(s7, h->affW[2], h->affB[2], out, B, h->cfg.num_classes, xv, 0, s, scr, scr_bytes, w3 ? h->affW3[2] : nullptr));
-    }
-    return XVEC_OK;
+    // the frame-level activations are dead from here on: layers 1-4's buffers serve as split-K scratch (actA and actB are adjacent)
+    return segment_layers(h, pooled, B, reinterpret_cast<float*>(ws + p.seg6), reinterpret_cast<float*>(ws + p.seg7),
+                          reinterpret_cast<float*>(ws + p.actA), (p.actB - p.actA) * 2, mode, dtype, out, s);
+}
+
+// Workspace of xvec_forward_segments: the plan of the batch, and behind it the segments' rows, pooled statistics and
+// segment-layer activations (M = n_segments rows each).
+struct SegPlan {
+    Plan p;
+    size_t seg_row, seg_n, pooled, seg6, seg7, bytes;
+};
+
+constexpr int64_t kMaxSegments = 65535 * 16;   // per call: the segment layers' direct form puts ceil(M / 16) on grid.y
+
+SegPlan make_seg_plan(const xvec_handle* h, int64_t total, int B, int64_t n_segments) {
+    SegPlan sp;
+    sp.p = make_plan(h, total, B);
+    size_t o = sp.p.bytes;
+    sp.seg_row = o; o += align256((size_t)n_segments * 8);
+    sp.seg_n = o;   o += align256((size_t)n_segments * 4);
+    sp.pooled = o;  o += align256((size_t)n_segments * 2 * XVEC_POOL_CHANNELS * 4);
+    sp.seg6 = o;    o += align256((size_t)n_segments * h->cfg.x_vector_size * 4);
+    sp.seg7 = o;    o += align256((size_t)n_segments * h->cfg.x_vector_size * 4);
+    sp.bytes = o;
+    return sp;
 }
 
 // host offsets -> device (stream ordered, via the handle's ring of two pinned staging slots).
@@ -915,6 +948,117 @@ int xvec_forward_packed(xvec_handle* h, const float* x_packed, const int64_t* of
         HIP_TRY(launch_pack_rows(x_packed, nullptr, 1, (int)total, C, h->cin_pad, xp, false, s));
     }
     return forward_rows(h, lp, rows, h->cin_pad, B, p, mode, dtype, out, ws, s);
+}
+
+size_t xvec_segments_workspace_bytes(const xvec_handle* h, int64_t total_frames, int32_t n_utts, int64_t n_segments) {
+    if (!h || total_frames < 1 || n_utts < 1 || n_segments < 1 || n_segments > kMaxSegments) return 0;
+    return make_seg_plan(h, total_frames, n_utts, n_segments).bytes;
+}
+
+int xvec_stat_pool_segments(const void* y, int elem, int64_t rows, int32_t ldy, int32_t C, const int64_t* seg_row_dev,
+                            const int32_t* seg_n_dev, int64_t n_segments, const float* scale_dev, const float* shift_dev,
+                            float* out, xvec_stream stream) {
+    if (!y || !seg_row_dev || !seg_n_dev || !out) return g_err.fail(XVEC_ERR_ARG, "null tensor pointer");
+    if (elem != 0 && elem != 1) return g_err.fail(XVEC_ERR_ARG, "elem must be 0 (fp32) or 1 (bf16), got %d", elem);
+    if (rows < 1 || C < 1 || ldy < C) return g_err.fail(XVEC_ERR_ARG, "need rows >= 1 and 1 <= C <= ldy (got rows=%lld C=%d ldy=%d)", (long long)rows, C, ldy);
+    if (n_segments < 1 || n_segments > 0x7fffffff) return g_err.fail(XVEC_ERR_ARG, "n_segments must be in [1, 2^31) (got %lld)", (long long)n_segments);
+    if (!scale_dev != !shift_dev) return g_err.fail(XVEC_ERR_ARG, "scale and shift go together");
+    if (reinterpret_cast<uintptr_t>(y) % (elem ? 2 : 4)) return g_err.fail(XVEC_ERR_ARG, "y is not aligned to its element size");
+    PoolSegArgs a;
+    memset(&a, 0, sizeof(a));
+    a.y = y;
+    a.elem = elem;
+    a.rows = rows;
+    a.ldy = ldy;
+    a.C = C;
+    a.row0 = seg_row_dev;
+    a.n = seg_n_dev;
+    a.n_segments = n_segments;
+    a.scale = scale_dev;
+    a.shift = shift_dev;
+    a.out = out;
+    HIP_TRY(launch_pool_segments(a, static_cast<hipStream_t>(stream)));
+    return XVEC_OK;
+}
+
+int xvec_stat_pool_segments_vector(const void* y, int elem, int32_t ldy, int32_t C) {
+    if (!y || (elem != 0 && elem != 1) || C < 1 || ldy < C) return -1;
+    return pool_segments_vector(y, elem, ldy, C) ? 1 : 0;
+}
+
+int xvec_forward_segments(xvec_handle* h, const float* x_packed, const int64_t* offsets_host, int32_t B,
+                          const int32_t* seg_utt_dev, const int32_t* seg_start_dev, const int32_t* seg_len_dev,
+                          int64_t n_segments, int mode, int dtype, float* out, void* workspace, size_t workspace_bytes,
+                          xvec_stream stream) {
+    int rc = common_checks(h, x_packed, B, mode, dtype, out, workspace);
+    if (rc) return rc;
+    if (!offsets_host) return g_err.fail(XVEC_ERR_ARG, "null offsets");
+    if (!seg_utt_dev || !seg_start_dev || !seg_len_dev) return g_err.fail(XVEC_ERR_ARG, "null segment array");
+    if (n_segments < 1) return g_err.fail(XVEC_ERR_ARG, "n_segments must be at least 1 (got %lld)", (long long)n_segments);
+    if (n_segments > kMaxSegments)
+        return g_err.fail(XVEC_ERR_TOO_LARGE, "at most %lld segments per call (got %lld); split the list", (long long)kMaxSegments,
+                          (long long)n_segments);
+    DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
+    HIP_TRY(guard.enter(h->cfg.device));
+    if (offsets_host[0] != 0) return g_err.fail(XVEC_ERR_ARG, "offsets[0] must be 0");
+    for (int i = 0; i < B; ++i) {
+        const int64_t n = offsets_host[i + 1] - offsets_host[i];
+        if (n <= XVEC_TOTAL_CONTEXT)
+            return g_err.fail(XVEC_ERR_ARG, "recording %d has %lld frames; need at least %d", i, (long long)n, XVEC_TOTAL_CONTEXT + 1);
+    }
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    char* ws = static_cast<char*>(workspace);
+    const int64_t total = offsets_host[B];
+    const SegPlan sp = make_seg_plan(h, total, B, n_segments);
+    const Plan& p = sp.p;
+    if (workspace_bytes < sp.bytes)
+        return g_err.fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu", workspace_bytes, sp.bytes);
+    const int C = h->cfg.input_size;
+    int64_t* offs_dev = reinterpret_cast<int64_t*>(ws + p.offs);
+    float* xp = reinterpret_cast<float*>(ws + p.xpad);
+    const bool pad = h->cin_pad != C;
+    if (pad && total > 0x7fffffff) return g_err.fail(XVEC_ERR_ARG, "too many frames");
+    const float* rows = pad ? xp : x_packed;
+    // everything is planned before anything is enqueued: layer 5 writes its rows (act5) instead of pooling partials
+    LayerPlan lp[XVEC_NUM_TDNN];
+    if ((rc = plan_stack(h, rows, h->cin_pad, offs_dev, B, 0, p, dtype, ws, lp, true))) return rc;
+    if ((rc = stage_offsets(h, offsets_host, nullptr, B, offs_dev, s))) return rc;
+    if (pad) {
+        StageTimer t(h, T_PACK, s);
+        HIP_TRY(launch_pack_rows(x_packed, nullptr, 1, (int)total, C, h->cin_pad, xp, false, s));
+    }
+    if (lp[0].mode.src == Src::kRows16) {    // [total, ldx] fp32 -> bf16 hi and lo planes (same row stride in elements)
+        StageTimer t(h, T_PACK, s);
+        HIP_TRY(launch_pack_rows_split(rows, p.total, h->cin_pad, h->cin_pad, lp[0].a.x_plane_bytes / 2, ws + p.x16, s));
+    }
+    for (const LayerPlan& l : lp)
+        if ((rc = launch_layer(h, l, s))) return rc;
+    float* pooled = mode == XVEC_MODE_POOLED ? out : reinterpret_cast<float*>(ws + sp.pooled);
+    {
+        StageTimer t(h, T_POOL, s);
+        const LayerPlan& l5 = lp[XVEC_NUM_TDNN - 1];
+        const int n5 = h->geo[4].n_pad;
+        const bool b16 = dtype == XVEC_BF16;                 // its layer 5 left relu(z + bias'): BatchNorm goes to the statistics
+        PoolSegArgs a;
+        memset(&a, 0, sizeof(a));
+        a.y = l5.a.Y;
+        a.elem = b16 ? 1 : 0;
+        a.rows = total - (int64_t)B * XVEC_TOTAL_CONTEXT;
+        a.ldy = l5.a.ldy;
+        a.C = XVEC_POOL_CHANNELS;
+        a.row0 = reinterpret_cast<int64_t*>(ws + sp.seg_row);
+        a.n = reinterpret_cast<int32_t*>(ws + sp.seg_n);
+        a.n_segments = n_segments;
+        a.scale = b16 ? h->vec[4] + n5 : nullptr;
+        a.shift = b16 ? h->vec[4] + 2 * n5 : nullptr;
+        a.out = pooled;
+        HIP_TRY(launch_segment_rows(seg_utt_dev, seg_start_dev, seg_len_dev, n_segments, offs_dev, B, XVEC_TOTAL_CONTEXT,
+                                    reinterpret_cast<int64_t*>(ws + sp.seg_row), reinterpret_cast<int32_t*>(ws + sp.seg_n), s));
+        HIP_TRY(launch_pool_segments(a, s));
+    }
+    if (mode == XVEC_MODE_POOLED) return XVEC_OK;
+    return segment_layers(h, pooled, (int)n_segments, reinterpret_cast<float*>(ws + sp.seg6), reinterpret_cast<float*>(ws + sp.seg7),
+                          reinterpret_cast<float*>(ws + p.actA), (p.actB - p.actA) * 2, mode, dtype, out, s);
 }
 
 int xvec_tdnn_layer(xvec_handle* h, int layer, const float* x, int32_t B, int32_t T, int dtype, float* y,

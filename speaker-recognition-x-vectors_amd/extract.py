@@ -187,6 +187,16 @@ def to_records(x_vecs: torch.Tensor, labels, ids) -> List[tuple]:
     return [(i, int(l), np.array(v, dtype=np.float64)) for v, l, i in zip(host, labels, ids)]
 
 
+def window_records(model, x: torch.Tensor, ids, labels, win: int, hop: int, lengths=None, min_tail=None, **kw) -> List[tuple]:
+    """to_records rows of the x-vectors over sliding windows of every recording (XVectorModel.extract_windows): a window of
+    recording `id` is recorded as f"{id}@{start}+{len}" with the recording's label, so write_x_vector_csv / read_x_vector_csv
+    carry them unchanged."""
+    vectors, windows = model.extract_windows(x, win, hop, lengths=lengths, min_tail=min_tail, **kw)
+    if torch.is_tensor(labels):
+        labels = labels.detach().cpu().numpy()
+    return to_records(vectors, [labels[u] for u, _, _ in windows], [f"{ids[u]}@{s}+{n}" for u, s, n in windows])
+
+
 _SIDE = {}
 
 

@@ -87,6 +87,11 @@ _SIGS = {
                                C.c_size_t, _vp]),
     "xvec_forward_packed": (C.c_int, [_vp, _f32p, C.POINTER(_i64), _i32, C.c_int, C.c_int, _f32p, _vp,
                                       C.c_size_t, _vp]),
+    "xvec_segments_workspace_bytes": (C.c_size_t, [_vp, _i64, _i32, _i64]),
+    "xvec_forward_segments": (C.c_int, [_vp, _f32p, C.POINTER(_i64), _i32, _vp, _vp, _vp, _i64, C.c_int, C.c_int, _f32p, _vp,
+                                        C.c_size_t, _vp]),
+    "xvec_stat_pool_segments": (C.c_int, [_vp, C.c_int, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _f32p, _vp]),
+    "xvec_stat_pool_segments_vector": (C.c_int, [_vp, C.c_int, _i32, _i32]),
     "xvec_tdnn_layer": (C.c_int, [_vp, C.c_int, _f32p, _i32, _i32, C.c_int, _f32p, _vp, C.c_size_t, _vp]),
     "xvec_tdnn_pool_layer": (C.c_int, [_vp, _f32p, _i32, _i32, C.c_int, _f32p, _vp, C.c_size_t, _vp]),
     "xvec_stat_pool": (C.c_int, [_f32p, _vp, _i32, _i32, _i32, _f32p, _vp]),

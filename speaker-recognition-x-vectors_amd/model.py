@@ -14,8 +14,9 @@ missing library or training mode raise.
 from __future__ import annotations
 
 import ctypes as C
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -43,6 +44,84 @@ def _require_gpu(x: torch.Tensor, what: str):
                            "this package has no CPU path (the CPU oracle lives in oracle/ for tests only)")
 
 
+# ---------------------------------------------------------------------- segments of recordings: host planning
+def sliding_windows(lengths: Sequence[int], win: int, hop: int, min_tail: Optional[int] = None) -> np.ndarray:
+    """int32 [n, 3] rows (utt, start, len), ordered by utterance, then start: per recording of T frames the full windows at
+    0, hop, 2 hop, ... while start + win <= T.  With `min_tail`, one last shorter window [n_full * hop, T) when frames past
+    the last full window remain and it has at least `min_tail` frames -- also the single window of a recording shorter than
+    `win`.  (A window needs 15 frames: the TDNN stack consumes 14.)"""
+    win, hop = int(win), int(hop)
+    if win <= TOTAL_CONTEXT:
+        raise ValueError(f"win={win}: a window needs at least {TOTAL_CONTEXT + 1} frames")
+    if hop < 1:
+        raise ValueError(f"hop={hop}: must be at least 1")
+    if min_tail is not None and int(min_tail) <= TOTAL_CONTEXT:
+        raise ValueError(f"min_tail={min_tail}: a window needs at least {TOTAL_CONTEXT + 1} frames")
+    rows = []
+    for u, T in enumerate(int(v) for v in lengths):
+        n_full = (T - win) // hop + 1 if T >= win else 0
+        rows += [(u, k * hop, win) for k in range(n_full)]
+        covered = (n_full - 1) * hop + win if n_full else 0
+        tail = T - n_full * hop
+        if min_tail is not None and T > covered and tail >= int(min_tail):
+            rows.append((u, n_full * hop, tail))
+    return np.asarray(rows, dtype=np.int32).reshape(-1, 3)
+
+
+class SegmentCall(NamedTuple):
+    """One library call of a segments job: `pieces` [(utt, lo, hi)] are the frame ranges of recordings the call packs, in order;
+    `segs` int64 [m, 4] rows (index in the caller's list, piece of this call, start inside the piece, len)."""
+    pieces: list
+    segs: np.ndarray
+
+    @property
+    def frames(self) -> int:
+        return sum(hi - lo for _, lo, hi in self.pieces)
+
+
+MAX_SEGMENTS_PER_CALL = 65535 * 16          # xvec_forward_segments' limit (include/xvec_hip.h)
+
+
+def plan_segment_calls(segments, max_frames: int, max_pieces: int = 65535,
+                       max_segments: int = MAX_SEGMENTS_PER_CALL) -> List[SegmentCall]:
+    """Cut a list of (utt, start, len) segments into library calls of at most `max_frames` input frames (the frame-level
+    activations cost about 10 KB of workspace per frame), `max_pieces` pieces and `max_segments` segments.  Pure host
+    arithmetic.  Per recording the segments are taken in start order and cut into runs; a run's piece is exactly the hull
+    [min start, max end) of its segments, closed as soon as the next segment would stretch it past `max_frames` or be its
+    `max_segments + 1`-th (dense or repeated segments over few frames) -- a recording that fits is one piece, a longer one
+    several, and frames no segment covers at either end are never computed.  Pieces fill calls in order.  Every segment
+    lands in exactly one piece, inside it.  A single segment longer than `max_frames` raises ValueError."""
+    seg = np.asarray(segments, dtype=np.int64).reshape(-1, 3)
+    max_frames, max_segments = int(max_frames), int(max_segments)
+    if max_segments < 1 or max_pieces < 1:
+        raise ValueError(f"max_segments={max_segments}, max_pieces={max_pieces}: a call holds at least one of each")
+    order = np.lexsort((seg[:, 1] + seg[:, 2], seg[:, 1], seg[:, 0]))      # by utterance, start, end
+    pieces = []                                    # (utt, lo, hi, [segment indices])
+    for i in order:
+        u, st, ln = (int(v) for v in seg[i])
+        if ln > max_frames:
+            raise ValueError(f"segment {int(i)} has {ln} frames, more than the {max_frames} a call may hold (max_frames)")
+        if (pieces and pieces[-1][0] == u and max(pieces[-1][2], st + ln) - pieces[-1][1] <= max_frames
+                and len(pieces[-1][3]) < max_segments):
+            pieces[-1][2] = max(pieces[-1][2], st + ln)
+            pieces[-1][3].append(int(i))
+        else:
+            pieces.append([u, st, st + ln, [int(i)]])
+    calls, cur, cur_frames, cur_segs = [], [], 0, 0
+    for pc in pieces + [None]:
+        if pc is None or (cur and (cur_frames + pc[2] - pc[1] > max_frames or len(cur) >= max_pieces
+                                   or cur_segs + len(pc[3]) > max_segments)):
+            if cur:
+                rows = [(i, k, int(seg[i, 1]) - lo, int(seg[i, 2])) for k, (_, lo, _, idx) in enumerate(cur) for i in idx]
+                calls.append(SegmentCall([(u, lo, hi) for u, lo, hi, _ in cur], np.asarray(rows, dtype=np.int64).reshape(-1, 4)))
+            cur, cur_frames, cur_segs = [], 0, 0
+        if pc is not None:
+            cur.append(pc)
+            cur_frames += pc[2] - pc[1]
+            cur_segs += len(pc[3])
+    return calls
+
+
 class _Engine:
     """One libxvec_hip handle per (model, device) plus its cached workspace."""
 
@@ -62,6 +141,15 @@ class _Engine:
         if need == 0:
             raise _hip.XvecError(_hip.ERR_ARG, "xvec_workspace_bytes returned 0")
         return int(need)
+
+    def ensure_segments_workspace(self, total_frames: int, n_utts: int, n_segments: int):
+        need = int(_hip.lib.xvec_segments_workspace_bytes(self.h, total_frames, n_utts, n_segments))
+        if need == 0:
+            raise _hip.XvecError(_hip.ERR_ARG, "xvec_segments_workspace_bytes returned 0")
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = None          # release before growing
+            self.workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self.workspace.data_ptr(), self.workspace.numel()
 
     def __del__(self):
         h, self.h = getattr(self, "h", None), None
@@ -412,6 +500,130 @@ class XVectorModel(nn.Module):
             _hip.check(_hip.lib.xvec_forward_packed(eng.h, x.data_ptr(), arr, B, mode, _DTYPES[self.precision],
                                                     out.data_ptr(), ws, ws_bytes, _stream_ptr(x.device)))
         return out
+
+    # ------------------------------------------------------------------ segments and sliding windows of recordings
+    def extract_segments(self, x: torch.Tensor, segments, lengths=None, logits: bool = False, pooled: bool = False,
+                         max_frames: int = 262144, offsets: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """One result per segment (utt, start, len) -- in INPUT frames of recording utt, len >= 15 -- of a batch of recordings:
+        to rounding, `extract_x_vec(x[utt, start:start+len][None])` (logits / the pooled [3000] statistics with `logits` /
+        `pooled`), row i for segment i.  Segments may overlap, repeat, come in any order and skip frames.  The frame-level
+        stack runs ONCE over the frames the segments cover (its layers are valid convolutions, so a crop's layer-5 rows are
+        rows of the recording's) and each segment pools its own rows: overlapping windows do not multiply the matrix work.
+        x is [B, T, C] (with `lengths`: valid frames per recording) or packed rows [sum len, C] with `offsets`.  The segments
+        are checked on the host before anything is launched and uploaded once; `max_frames` bounds the frames of one library
+        call (about 10 KB of workspace per frame): recordings are grouped into calls, a longer recording is cut into pieces
+        (plan_segment_calls)."""
+        seg = np.asarray(segments.detach().cpu().numpy() if torch.is_tensor(segments) else segments)
+        if seg.ndim != 2 or seg.shape[1] != 3 or seg.shape[0] < 1 or seg.dtype.kind not in "iu":
+            raise ValueError(f"extract_segments: segments must be an integer array [n >= 1, 3] of (utt, start, len), got "
+                             f"{seg.dtype} {tuple(seg.shape)}")
+        seg = seg.astype(np.int64)
+        if logits and pooled:
+            raise ValueError("extract_segments: logits and pooled exclude each other")
+        if offsets is not None:
+            offs = [int(v) for v in offsets]
+            if x.dim() != 2 or len(offs) < 2 or offs[0] != 0 or offs[-1] != x.shape[0] or lengths is not None:
+                raise ValueError("extract_segments: packed input needs x[sum(len),C], offsets[0]=0, offsets[-1]=rows and no lengths")
+            lens = [b - a for a, b in zip(offs[:-1], offs[1:])]
+            starts = offs[:-1]
+        else:
+            if x.dim() != 3 or x.shape[0] < 1:
+                raise ValueError(f"extract_segments: expected x[B,T,C] (or packed rows with offsets=), got shape {tuple(x.shape)}")
+            B, T = int(x.shape[0]), int(x.shape[1])
+            lens = self._lengths_arg(lengths, B, T)[1] or [T] * B
+            if max(lens) > T:
+                raise ValueError(f"lengths must lie in [15, T={T}]")
+            starts = [b * T for b in range(B)]
+        if min(lens) <= TOTAL_CONTEXT:
+            raise ValueError(f"every recording needs at least {TOTAL_CONTEXT + 1} frames")
+        if x.shape[-1] != self.hparams["input_size"]:
+            raise ValueError(f"expected {self.hparams['input_size']} input channels, got {x.shape[-1]}")
+        nrec = len(lens)
+        if seg[:, 0].min() < 0 or seg[:, 0].max() >= nrec:
+            raise ValueError(f"extract_segments: utt outside the batch of {nrec} recordings")
+        if seg[:, 2].min() <= TOTAL_CONTEXT:
+            raise ValueError(f"extract_segments: a segment needs at least {TOTAL_CONTEXT + 1} frames (the TDNN stack consumes "
+                             f"{TOTAL_CONTEXT})")
+        bad = (seg[:, 1] < 0) | (seg[:, 1] + seg[:, 2] > np.asarray(lens, dtype=np.int64)[seg[:, 0]])
+        if bad.any():
+            i = int(np.flatnonzero(bad)[0])
+            raise ValueError(f"extract_segments: segment {i} {tuple(int(v) for v in seg[i])} leaves its recording of "
+                             f"{lens[int(seg[i, 0])]} frames")
+        _require_gpu(x, "extract_segments")
+        self._check_mode()
+        rows = x.detach().float().contiguous().reshape(-1, x.shape[-1])
+        mode = (_hip.MODE_LOGITS if logits else _hip.MODE_POOLED if pooled else
+                _hip.MODE_XVEC7 if self.x_vec_extract_layer == 7 else _hip.MODE_XVEC6)
+        n_out = (self.hparams["num_classes"] if logits else 2 * POOL_CHANNELS if pooled else self.hparams["x_vector_size"])
+        res, perm = self._run_segments(rows, starts, seg, np.arange(len(seg)), mode, n_out, int(max_frames))
+        inv = np.empty(len(seg), dtype=np.int64)
+        inv[perm] = np.arange(len(seg))
+        return res if np.array_equal(inv, np.arange(len(seg))) else res[torch.from_numpy(inv).to(res.device)]
+
+    def _run_segments(self, rows, starts, seg, index, mode, n_out, max_frames, max_segments=MAX_SEGMENTS_PER_CALL):
+        """The planned calls of seg (rows `index` of the caller's list) -> (results in call order, the caller's index of
+        each result row).  rows: all recordings' frames as [., C]; recording u starts at row starts[u]."""
+        calls = plan_segment_calls(seg, max_frames, self.MAX_UTTS_PER_CALL, max_segments)
+        dev = rows.device
+        eng = self._engine(dev)
+        local = np.concatenate([c.segs for c in calls])                     # (index, piece, start in the piece, len)
+        seg_dev = torch.from_numpy(np.ascontiguousarray(local[:, 1:].T.astype(np.int32))).to(dev)      # ONE upload: [3, n]
+        res = torch.empty((len(local), n_out), dtype=torch.float32, device=dev)
+        parts, perm, at, halved = [], [], 0, False
+        for c in calls:
+            m = len(c.segs)
+            # the call's pieces as runs of rows; neighbours in memory merge, and one run needs no copy
+            runs = []
+            for u, lo, hi in c.pieces:
+                a, b = starts[u] + lo, starts[u] + hi
+                if runs and runs[-1][1] == a:
+                    runs[-1][1] = b
+                else:
+                    runs.append([a, b])
+            xp = rows[runs[0][0]:runs[0][1]] if len(runs) == 1 else torch.cat([rows[a:b] for a, b in runs], 0)
+            if xp.data_ptr() % 16:                  # (a view into rows of an odd width: the library wants 16-byte alignment)
+                xp = xp.clone()
+            offs = [0]
+            for _, lo, hi in c.pieces:
+                offs.append(offs[-1] + hi - lo)
+            nb = len(c.pieces)
+            ws, ws_bytes = eng.ensure_segments_workspace(offs[-1], nb, m)
+            arr = (C.c_int64 * (nb + 1))(*offs)
+            ptr = [seg_dev[k, at:at + m].data_ptr() for k in range(3)]
+            with torch.cuda.device(dev):
+                rc = _hip.lib.xvec_forward_segments(eng.h, xp.data_ptr(), arr, nb, ptr[0], ptr[1], ptr[2], m, mode,
+                                                    _DTYPES[self.precision], res[at:at + m].data_ptr(), ws, ws_bytes,
+                                                    _stream_ptr(dev))
+            sub_index = index[c.segs[:, 0]]
+            if rc == _hip.ERR_TOO_LARGE and m > 1:
+                # a per-call size limit of the library the plan did not foresee: the same segments in calls of half the
+                # segments and, as far as the longest segment allows, half the frames
+                sub, sub_perm = self._run_segments(rows, starts, seg[c.segs[:, 0]], sub_index, mode, n_out,
+                                                   max(c.frames // 2, int(c.segs[:, 3].max())), (m + 1) // 2)
+                parts.append(sub)
+                halved = True
+                perm.append(sub_perm)
+            else:
+                _hip.check(rc)
+                parts.append(res[at:at + m])
+                perm.append(sub_index)
+            at += m
+        return (torch.cat(parts, 0) if halved else res), np.concatenate(perm)
+
+    def extract_windows(self, x: torch.Tensor, win: int, hop: int, lengths=None, min_tail: Optional[int] = None, **kw):
+        """x-vectors over sliding windows of every recording: (vectors [n, .], windows int32 [n, 3] of (utt, start, len)),
+        windows as sliding_windows gives them for the recordings' lengths; `kw` goes to extract_segments."""
+        if kw.get("offsets") is not None:
+            offs = [int(v) for v in kw["offsets"]]
+            lens = [b - a for a, b in zip(offs[:-1], offs[1:])]
+        elif x.dim() == 3:
+            lens = self._lengths_arg(lengths, int(x.shape[0]), int(x.shape[1]))[1] or [int(x.shape[1])] * int(x.shape[0])
+        else:
+            raise ValueError(f"extract_windows: expected x[B,T,C] (or packed rows with offsets=), got shape {tuple(x.shape)}")
+        windows = sliding_windows(lens, win, hop, min_tail)
+        if not len(windows):
+            raise ValueError(f"extract_windows: no recording holds a window of {win} frames (min_tail={min_tail})")
+        return self.extract_segments(x, windows, lengths=lengths, **kw), windows
 
     # ------------------------------------------------------------------ per-stage entry points
     def _tdnn_layer(self, index: int, x: torch.Tensor) -> torch.Tensor:
