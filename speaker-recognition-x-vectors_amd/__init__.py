@@ -9,7 +9,8 @@ from . import synth  # noqa: F401  (numpy only)
 __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontEnd", "PldaScorer", "hip", "extract",
            "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject", "evaluate", "TrialList", "TrialResult",
            "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan",
-           "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam", "sliding_windows", "plan_segment_calls"]
+           "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam", "sliding_windows", "plan_segment_calls", "snorm",
+           "ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm"]
 
 
 def __getattr__(name):
@@ -29,13 +30,16 @@ def __getattr__(name):
     if name in ("TrialList", "TrialResult", "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm"):
+        from . import snorm
+        return getattr(snorm, name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
     if name in ("XVectorTrainer", "tdnn_layer_train", "DeviceAdam"):
         from . import train
         return getattr(train, name)
-    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train"):
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -283,12 +283,18 @@ class plda_score_stat_object:
             self._plda_scores = Scores(self.en_stat.modelset, self.te_stat.modelset, self._scoremat.cpu().numpy())
         return self._plda_scores
 
-    def test_plda(self, plda, veri_test_file_path):
+    def test_plda(self, plda, veri_test_file_path, cohort=None, top_k=0):
         """Scores every test x-vector against every other one with `plda` (.mean, .F, .Sigma) and collects the trials of the
-        VoxCeleb trial file."""
+        VoxCeleb trial file.  With `cohort` ([C, D] x-vectors; not in the reference) the score matrix is S-normalised on the
+        device against it before the trials are gathered (adaptive S-norm over the `top_k` largest cohort scores of every
+        vector when top_k > 0: snorm.ScoreNormalizer); the default leaves every attribute as the reference computes it."""
         from .scoring import PldaScorer
         scorer = PldaScorer(plda.mean, plda.F, plda.Sigma, device=self.device)
         self._scoremat = scorer.score(self.x_vec_test)       # en_stat and te_stat hold the same vectors: the self path
+        if cohort is not None:
+            from .snorm import ScoreNormalizer
+            norm = ScoreNormalizer(scorer, cohort, top_k=top_k, device=self.device)
+            norm.normalize(self._scoremat, self.x_vec_test, mode="s", out=self._scoremat)
         self._plda_scores = 0
         modelset, segset = self.en_stat.modelset, self.te_stat.modelset
         self._trials = trials = TrialList.from_file(veri_test_file_path, modelset, segset)

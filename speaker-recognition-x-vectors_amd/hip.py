@@ -133,6 +133,11 @@ _SIGS = {
     "xvec_eval_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp,
                                       C.c_size_t, _vp]),
     "xvec_eval_sorted_keys": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    # include/xvec_snorm.h
+    "xvec_snorm_last_error": (C.c_char_p, []),
+    "xvec_snorm_workspace_bytes": (C.c_size_t, [_i64, _i64]),
+    "xvec_snorm_row_stats": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "xvec_snorm_apply": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     # include/xvec_augment.h
     "xvec_aug_last_error": (C.c_char_p, []),
     "xvec_aug_mix_workspace_bytes": (C.c_size_t, [_i32, _i64, _i64]),
