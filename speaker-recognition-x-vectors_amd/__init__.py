@@ -10,7 +10,7 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "frontend", "scoring", "plda", "PldaStats", "PLDA", "StatObject", "evaluate", "TrialList", "TrialResult",
            "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan",
            "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam", "sliding_windows", "plan_segment_calls", "snorm",
-           "ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm"]
+           "ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm", "lda", "LDA", "LdaStats", "EmbeddingTransform"]
 
 
 def __getattr__(name):
@@ -33,13 +33,16 @@ def __getattr__(name):
     if name in ("ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm"):
         from . import snorm
         return getattr(snorm, name)
+    if name in ("LDA", "LdaStats", "EmbeddingTransform"):
+        import importlib
+        return getattr(importlib.import_module(".lda", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
     if name in ("XVectorTrainer", "tdnn_layer_train", "DeviceAdam"):
         from . import train
         return getattr(train, name)
-    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm"):
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -158,6 +158,45 @@ class StatObject:
         self.start = np.array([None] * n) if start is None else start
         self.stop = np.array([None] * n) if stop is None else stop
 
+    # speechbrain's StatObject_SB conditioning methods.  Each runs on the device (include/xvec_lda.h, xvector_amd.lda) and,
+    # where speechbrain changes stat1 in place, stores a numpy float64 result.
+
+    def _stats(self, device):
+        return PldaStats(self.stat1, self.modelset, device=device)
+
+    def _transform(self, mean, w, normalize, device):
+        from .lda import embed_transform
+        self.stat1 = embed_transform(self.stat1, mean, w, normalize, device=device).cpu().numpy()
+
+    def get_mean_stat1(self, device="cuda:0"):
+        """[D] mean of stat1."""
+        return self._stats(device).mean
+
+    def get_total_covariance_stat1(self, device="cuda:0"):
+        """[D, D] biased centred covariance of stat1."""
+        return self._stats(device).sigma_obs
+
+    def center_stat1(self, mu, device="cuda:0"):
+        self._transform(mu, None, False, device)
+
+    def rotate_stat1(self, R, device="cuda:0"):
+        self._transform(None, R, False, device)
+
+    def norm_stat1(self, device="cuda:0"):
+        """Every row divided by max(its 2-norm, 1e-8)."""
+        self._transform(None, None, True, device)
+
+    def whiten_stat1(self, mu, sigma, device="cuda:0"):
+        """Centre by mu and rotate by V diag(1 / sqrt(lam)) of a 2-D sigma (eigenvalues descending), or scale by
+        1 / sqrt(sigma) for a 1-D (diagonal) sigma."""
+        from .lda import whitening_matrix
+        self._transform(mu, whitening_matrix(sigma), False, device)
+
+    def get_lda_matrix_stat1(self, rank, device="cuda:0"):
+        """[D, rank] LDA matrix of stat1 with modelset as the classes (lda.LdaStats.matrix)."""
+        from .lda import LdaStats
+        return LdaStats(self.stat1, self.modelset, device=device).matrix(rank)
+
 
 def get_train_x_vec(train_xv, train_label, x_id_train):
     """plda_classifier.get_train_x_vec: modelset 'id<label>', segset the x-vector ids."""
@@ -203,6 +242,12 @@ def train_plda(plda, xvectors_stat):
     """plda_classifier.train_plda"""
     plda.plda(xvectors_stat)
     return plda
+
+
+def lda(x_vec_stat, reduced_dim=2, device="cuda:0"):
+    """plda_classifier.lda (xvector_amd.lda.lda)"""
+    from .lda import lda as _lda
+    return _lda(x_vec_stat, reduced_dim=reduced_dim, device=device)
 
 
 def save_plda(plda, file_name):
