@@ -5,7 +5,7 @@
  *   reverb     augment_rir: the signal plus its convolution with a room impulse response, peak-matched
  *   normalize  dataset.py:217-219: (x - min) / max(x - min), applied to every sample, augmented or not
  * All randomness stays on the host: the device does arithmetic on the draws it is handed (which clip, which start,
- * which SNR).  Resampling (resampy) and file reading are not part of this unit.
+ * which SNR).  Resampling (resampy) is the unit in front of this one (xvec_resample.h); file reading is not part of the library.
  *
  * Conventions as xvec_eval.h: DEVICE pointers unless a parameter says HOST, asynchronous on the caller's stream, no
  * allocation (the caller passes a workspace of the queried size), return codes as xvec_hip.h (0 = OK) with the message

@@ -154,6 +154,13 @@ _SIGS = {
     "xvec_aug_reverb_workspace_bytes": (C.c_size_t, [_i32, _i64, _i64]),
     "xvec_aug_reverb": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _i32, _i64, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "xvec_aug_normalize": (C.c_int, [_vp, _i64, _i32, _i64, _vp]),
+    # include/xvec_resample.h
+    "xvec_resample_last_error": (C.c_char_p, []),
+    "xvec_resample_out_len": (_i64, [_i64, C.c_double]),
+    "xvec_resample_tile_span": (_i64, [C.c_double, _i64, _i32]),
+    "xvec_resample_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "xvec_resample": (C.c_int, [_vp, _i32, _i64, _i32, _i64, _vp, _i32, C.POINTER(C.c_double), _i32, _vp, _i64, _i32, _i32, _vp,
+                                _i32, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
     # include/xvec_train.h
     "xvec_train_last_error": (C.c_char_p, []),
     "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
