@@ -205,6 +205,14 @@ int xvec_stat_pool_segments_vector(const void* y, int elem, int32_t ldy, int32_t
  * (main.py:72-75,87-90): x[M,in] -> y[M,out]. */
 int xvec_affine(xvec_handle* h, int which, const float* x, int32_t M, int relu, float* y,
                 xvec_stream stream);
+/* The same layer exactly as xvec_forward and xvec_forward_segments run it, on a caller-given x[M,in] -> y[M,out]: in
+ * the arithmetic of `dtype` (XVEC_BF16: bf16x3 products where the handle has the layer's weights as bf16 pairs, that is
+ * in % 4 == 0; fp32 MFMAs otherwise) and with a caller-given scratch window of scratch_bytes bytes (16-byte aligned; NULL
+ * with 0 bytes: none), which the split-K forms may overwrite and which stands for the dead activation buffers the whole
+ * path offers.  Which kernel form runs depends on (M, out, in), on the alignment of x and y and on scratch_bytes:
+ * xvec_get_affine_dispatch.  Nothing is written past scratch_bytes or outside y[M,out]. */
+int xvec_segment_layer(xvec_handle* h, int which, const float* x, int32_t M, int relu, int dtype, float* y,
+                       void* scratch, size_t scratch_bytes, xvec_stream stream);
 
 /* ---- test introspection -------------------------------------------------------------
  * Where the regions of a workspace lie that a test may want to look into after a call (tests/test_segmx_exact_gpu.py reads
@@ -213,7 +221,11 @@ int xvec_affine(xvec_handle* h, int which, const float* x, int32_t M, int relu, 
  *   part:     pooling partials [part_slots][3 planes K | S1 | S2][pool_n_pad] fp32 (csrc/tdnn_common.h; which slot holds
  *             what depends on the kernel layer 5 went to: xvec_get_dispatch)
  *   part_cnt: int32 frames behind each segment partial of the large-batch kernel (csrc/tdnn_pp16.hip)
- *   act_a / act_b: the two frame-level activation buffers, rows_alloc rows each (the per-stage entries stage their input in act_a) */
+ *   act_a / act_b: the two frame-level activation buffers, rows_alloc rows each (the per-stage entries stage their input in act_a)
+ *
+ * xvec_segment_layer (above) runs one segment layer in every kernel form the whole path can dispatch it to, and
+ * xvec_get_affine_dispatch (below, with the other dispatch getters) tells which form a launch took
+ * (tests/test_affine_forms_gpu.py, tests/test_segments_gpu.py).  Nothing in the product calls either. */
 typedef struct {
     size_t act_a, act_b, part, part_cnt, pooled, bytes;
     int64_t rows_alloc, part_slots;
@@ -257,6 +269,26 @@ int xvec_get_tdnn_form(const xvec_handle* h, int* forms, int* n);
  * at xvec_create keeps the Winograd form on fp32 operands. */
 enum { XVEC_OPERANDS_FP32 = 0, XVEC_OPERANDS_BF16 = 1, XVEC_OPERANDS_BF16X3 = 2, XVEC_OPERANDS_BF16_SPLIT3 = 3 };
 int xvec_get_tdnn_operands(const xvec_handle* h, int* operands, int* n);
+/* Which kernel form the LAST launch of segment_layer6 / segment_layer7 / output took and over how many K ranges it split
+ * the product: forms[0..2], ranges[0..2], *n = 3 (XVEC_AFFINE_NONE, 0: not launched yet).  Set by the whole-path entries,
+ * xvec_segment_layer and xvec_affine alike.  The rule is csrc/affine_plan.h:
+ *   TILE16 / TILE16_ELEMENTWISE  one 16 x 16 output tile per block, the block's waves split K (ranges = 1); element-wise
+ *                                loads when in % 4 != 0 or x is not 16-byte aligned.  Taken without scratch (xvec_affine),
+ *                                when out % 4 != 0, and when the scratch holds fewer than two partial results [M,out]
+ *                                while there are fewer than 256 tiles of 64 x 64
+ *   SPLITK / SPLITK_BF16X3       64 x 64 tiles x `ranges` K ranges (2..16) into scratch, summed in range order by a second
+ *                                kernel: fp32 MFMAs / bf16x3 products (XVEC_BF16)
+ *   DIRECT / DIRECT_BF16X3       from 256 tiles of 64 x 64 on: the same kernels over the whole K, written to y (ranges = 1) */
+enum {
+    XVEC_AFFINE_NONE = 0,
+    XVEC_AFFINE_TILE16 = 1,
+    XVEC_AFFINE_TILE16_ELEMENTWISE = 2,
+    XVEC_AFFINE_SPLITK = 3,
+    XVEC_AFFINE_SPLITK_BF16X3 = 4,
+    XVEC_AFFINE_DIRECT = 5,
+    XVEC_AFFINE_DIRECT_BF16X3 = 6
+};
+int xvec_get_affine_dispatch(const xvec_handle* h, int* forms, int* ranges, int* n);
 
 /* ---- next row N3: MFCC front end (the step in front of the path) ----------------------------
  * python_speech_features.mfcc as the reference calls it in its DataLoader workers

@@ -9,7 +9,6 @@
 // row and instruction); they are small enough to stay in L2.
 #include "xvec_internal.h"
 #include "tdnn_common.h"
-#include <algorithm>
 
 namespace xvec {
 
@@ -389,42 +388,41 @@ __global__ __launch_bounds__(256) void affine_reduce_kernel(const float* __restr
 }
 
 hipError_t launch_affine_f32(const float* x, const float* W, const float* b, float* y, int M, int N,
-                             int K, int relu, hipStream_t s, float* scratch, size_t scratch_bytes, const void* W3) {
+                             int K, int relu, hipStream_t s, float* scratch, size_t scratch_bytes, const void* W3,
+                             affine_plan::Plan* ran) {
+    if (ran) *ran = affine_plan::Plan{affine_plan::kNone, 0, 0, 0, 0, 0};
     if (M <= 0 || N <= 0) return hipSuccess;
     const bool vec16 = (K % 4 == 0) && (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(W)) & 15) == 0);
+    const bool out_ok = scratch && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(b)) & 15) == 0;
     const int64_t MN = (int64_t)M * N;
-    if (scratch && vec16 && N % 4 == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(b)) & 15) == 0) {
-        const int tm = (M + 63) / 64, tn = (N + 63) / 64, trips = (K + 63) / 64;
-        int S = (512 + tm * tn - 1) / (tm * tn);                     // about two blocks per CU
-        S = std::min(S, std::max(trips / 2, 1));                     // at least two trips per range
-        S = (int)std::min<int64_t>(std::min(S, 16), (int64_t)(scratch_bytes / 4) / MN);
-        const uint4* w3 = static_cast<const uint4*>(W3);      // bf16x3 form: see affine_splitk_x3_kernel
-        if (S <= 1 && tm * tn >= 256) {
-            if (w3)
-                affine_splitk_x3_kernel<<<dim3(tn * tm), 256, 0, s>>>(x, w3, b, y, M, N, K, relu, trips, tn, tn * tm, 1);
-            else
-                affine_splitk_kernel<true><<<dim3(tn * tm), 256, 0, s>>>(x, W, b, y, M, N, K, relu, trips, tn, tn * tm, 1);
-            return hipGetLastError();
-        }
-        if (S > 1) {
-            const int tps = (trips + S - 1) / S;
-            S = (trips + tps - 1) / tps;
-            const int s_pad = (S + 7) & ~7;                       // ranges s_pad-S..: blocks that exit at once
-            if (w3)
-                affine_splitk_x3_kernel<<<dim3(s_pad * tn * tm), 256, 0, s>>>(x, w3, b, scratch, M, N, K, relu, tps, tn,
-                                                                               tn * tm, S);
-            else
-                affine_splitk_kernel<false><<<dim3(s_pad * tn * tm), 256, 0, s>>>(x, W, b, scratch, M, N, K, relu, tps, tn,
-                                                                                   tn * tm, S);
-            affine_reduce_kernel<<<(unsigned)((MN / 4 + 255) / 256), 256, 0, s>>>(scratch, b, y, MN, N, S, relu);
-            return hipGetLastError();
-        }
-    }
-    dim3 grid((N + 15) / 16, (M + 15) / 16);
-    if (vec16)
+    // the form, the K ranges and the grid: csrc/affine_plan.h, nothing here decides
+    const affine_plan::Plan p = affine_plan::plan(M, N, K, vec16, out_ok, (int64_t)(scratch_bytes / 4), W3 != nullptr);
+    if (ran) *ran = p;
+    const int tm = (M + 63) / 64, tn = (N + 63) / 64;
+    const uint4* w3 = static_cast<const uint4*>(W3);      // bf16x3 form: see affine_splitk_x3_kernel
+    const dim3 grid((unsigned)p.grid_x, (unsigned)p.grid_y);
+    switch (p.form) {
+    case affine_plan::kDirectX3:
+        affine_splitk_x3_kernel<<<grid, 256, 0, s>>>(x, w3, b, y, M, N, K, relu, p.trips_per_range, tn, tn * tm, 1);
+        break;
+    case affine_plan::kDirect:
+        affine_splitk_kernel<true><<<grid, 256, 0, s>>>(x, W, b, y, M, N, K, relu, p.trips_per_range, tn, tn * tm, 1);
+        break;
+    case affine_plan::kSplitKX3:
+        affine_splitk_x3_kernel<<<grid, 256, 0, s>>>(x, w3, b, scratch, M, N, K, relu, p.trips_per_range, tn, tn * tm, p.S);
+        affine_reduce_kernel<<<(unsigned)((MN / 4 + 255) / 256), 256, 0, s>>>(scratch, b, y, MN, N, p.S, relu);
+        break;
+    case affine_plan::kSplitK:
+        affine_splitk_kernel<false><<<grid, 256, 0, s>>>(x, W, b, scratch, M, N, K, relu, p.trips_per_range, tn, tn * tm, p.S);
+        affine_reduce_kernel<<<(unsigned)((MN / 4 + 255) / 256), 256, 0, s>>>(scratch, b, y, MN, N, p.S, relu);
+        break;
+    case affine_plan::kTile16:
         affine_f32_kernel<true><<<grid, 64 * kAffWaves, 0, s>>>(x, W, b, y, M, N, K, relu);
-    else
+        break;
+    default:
         affine_f32_kernel<false><<<grid, 64 * kAffWaves, 0, s>>>(x, W, b, y, M, N, K, relu);
+        break;
+    }
     return hipGetLastError();
 }
 

@@ -129,6 +129,8 @@ struct xvec_handle {
     int last_kernel[XVEC_NUM_TDNN];    // XVEC_KERNEL_* the last launch of each frame-level layer went to (xvec_get_dispatch)
     int last_form[XVEC_NUM_TDNN];      // XVEC_FORM_* of that launch (xvec_get_tdnn_form)
     int last_operands[XVEC_NUM_TDNN];  // XVEC_OPERANDS_* of that launch (xvec_get_tdnn_operands)
+    int last_aff_form[3];              // XVEC_AFFINE_* the last launch of segment_layer6 / 7 / output took, and its K ranges
+    int last_aff_ranges[3];            // (xvec_get_affine_dispatch)
     // profiling
     bool profiling;
     hipEvent_t ev0[T_COUNT], ev1[T_COUNT];
@@ -539,35 +541,50 @@ int plan_stack(const xvec_handle* h, const float* x_rows, int ldx, const int64_t
     return XVEC_OK;
 }
 
+static_assert(affine_plan::kNone == XVEC_AFFINE_NONE && affine_plan::kTile16 == XVEC_AFFINE_TILE16 &&
+              affine_plan::kTile16Elem == XVEC_AFFINE_TILE16_ELEMENTWISE && affine_plan::kSplitK == XVEC_AFFINE_SPLITK &&
+              affine_plan::kSplitKX3 == XVEC_AFFINE_SPLITK_BF16X3 && affine_plan::kDirect == XVEC_AFFINE_DIRECT &&
+              affine_plan::kDirectX3 == XVEC_AFFINE_DIRECT_BF16X3, "csrc/affine_plan.h and include/xvec_hip.h number the forms alike");
+
+// Segment layer i (0: segment_layer6, 1: segment_layer7, 2: output) on x[M, in]: the one launch_affine_f32 call of the segment
+// layers, whoever asks for them.  scr is scratch the split-K forms may overwrite.
+int segment_affine(xvec_handle* h, int i, const float* x, int M, int relu, int dtype, float* y, float* scr, size_t scr_bytes,
+                   hipStream_t s) {
+    // plain bf16 (parity bar 1e-2): the segment layers' products as bf16x3 (affine.hip); XVEC_BF16X3 promises the fp32
+    // bar end to end and keeps the fp32 MFMAs here (x3 segment layers measured 3x the fp32 ones' error: 6e-6)
+    const bool w3 = dtype == XVEC_BF16;
+    affine_plan::Plan ran;
+    HIP_TRY(launch_affine_f32(x, h->affW[i], h->affB[i], y, M, h->affN[i], h->affK[i], relu, s, scr, scr_bytes,
+                              w3 ? h->affW3[i] : nullptr, &ran));
+    h->last_aff_form[i] = ran.form;
+    h->last_aff_ranges[i] = ran.S;
+    return XVEC_OK;
+}
+
 // The segment layers of `mode` (not XVEC_MODE_POOLED) on pooled[M, 3000]: s6 / s7 hold [M, x_vector_size] each, scr is scratch
 // the split-K forms may overwrite.
 int segment_layers(xvec_handle* h, const float* pooled, int M, float* s6, float* s7, float* scr, size_t scr_bytes, int mode,
                    int dtype, float* out, hipStream_t s) {
-    const int xv = h->cfg.x_vector_size, K6 = 2 * XVEC_POOL_CHANNELS;
-    // plain bf16 (parity bar 1e-2): the segment layers' products as bf16x3 (affine.hip); XVEC_BF16X3 promises the fp32
-    // bar end to end and keeps the fp32 MFMAs here (x3 segment layers measured 3x the fp32 ones' error: 6e-6)
-    const bool w3 = dtype == XVEC_BF16;
     if (mode == XVEC_MODE_XVEC6) {
         StageTimer t(h, T_SEG6, s);
-        HIP_TRY(launch_affine_f32(pooled, h->affW[0], h->affB[0], out, M, xv, K6, 0, s, scr, scr_bytes, w3 ? h->affW3[0] : nullptr));
-        return XVEC_OK;
+        return segment_affine(h, 0, pooled, M, 0, dtype, out, scr, scr_bytes, s);
     }
+    int rc;
     {
         StageTimer t(h, T_SEG6, s);
-        HIP_TRY(launch_affine_f32(pooled, h->affW[0], h->affB[0], s6, M, xv, K6, 1, s, scr, scr_bytes, w3 ? h->affW3[0] : nullptr));
+        if ((rc = segment_affine(h, 0, pooled, M, 1, dtype, s6, scr, scr_bytes, s))) return rc;
     }
     if (mode == XVEC_MODE_XVEC7) {
         StageTimer t(h, T_SEG7, s);
-        HIP_TRY(launch_affine_f32(s6, h->affW[1], h->affB[1], out, M, xv, xv, 0, s, scr, scr_bytes, w3 ? h->affW3[1] : nullptr));
-        return XVEC_OK;
+        return segment_affine(h, 1, s6, M, 0, dtype, out, scr, scr_bytes, s);
     }
     {
         StageTimer t(h, T_SEG7, s);
-        HIP_TRY(launch_affine_f32(s6, h->affW[1], h->affB[1], s7, M, xv, xv, 1, s, scr, scr_bytes, w3 ? h->affW3[1] : nullptr));
+        if ((rc = segment_affine(h, 1, s6, M, 1, dtype, s7, scr, scr_bytes, s))) return rc;
     }
     {
         StageTimer t(h, T_OUT, s);
-        HIP_TRY(launch_affine_f32(s7, h->affW[2], h->affB[2], out, M, h->cfg.num_classes, xv, 0, s, scr, scr_bytes, w3 ? h->affW3[2] : nullptr));
+        if ((rc = segment_affine(h, 2, s7, M, 0, dtype, out, scr, scr_bytes, s))) return rc;
     }
     return XVEC_OK;
 }
@@ -1152,8 +1169,35 @@ int xvec_affine(xvec_handle* h, int which, const float* x, int32_t M, int relu, 
     if (!h->aff_loaded[i]) return g_err.fail(XVEC_ERR_STATE, "affine %d weights not loaded", which);
     DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
     HIP_TRY(guard.enter(h->cfg.device));
+    affine_plan::Plan ran;
     HIP_TRY(launch_affine_f32(x, h->affW[i], h->affB[i], y, M, h->affN[i], h->affK[i], relu,
-                              static_cast<hipStream_t>(stream)));
+                              static_cast<hipStream_t>(stream), nullptr, 0, nullptr, &ran));
+    h->last_aff_form[i] = ran.form;
+    h->last_aff_ranges[i] = ran.S;
+    return XVEC_OK;
+}
+
+int xvec_segment_layer(xvec_handle* h, int which, const float* x, int32_t M, int relu, int dtype, float* y, void* scratch,
+                       size_t scratch_bytes, xvec_stream stream) {
+    const int i = aff_index(which);
+    if (!h || i < 0) return g_err.fail(XVEC_ERR_ARG, "bad handle or affine id %d", which);
+    if (!x || !y || M < 1) return g_err.fail(XVEC_ERR_ARG, "bad x/y/M");
+    if (dtype != XVEC_F32 && dtype != XVEC_BF16 && dtype != XVEC_BF16X3) return g_err.fail(XVEC_ERR_ARG, "bad dtype %d", dtype);
+    if (!scratch && scratch_bytes) return g_err.fail(XVEC_ERR_ARG, "null scratch of %zu bytes", scratch_bytes);
+    if (reinterpret_cast<uintptr_t>(scratch) & 15) return g_err.fail(XVEC_ERR_ARG, "scratch is not 16-byte aligned");
+    if (!h->aff_loaded[i]) return g_err.fail(XVEC_ERR_STATE, "affine %d weights not loaded", which);
+    DeviceGuard guard;                 // launches go to the handle's device whatever the caller's current one is
+    HIP_TRY(guard.enter(h->cfg.device));
+    return segment_affine(h, i, x, M, relu, dtype, y, static_cast<float*>(scratch), scratch_bytes, static_cast<hipStream_t>(stream));
+}
+
+int xvec_get_affine_dispatch(const xvec_handle* h, int* forms, int* ranges, int* n) {
+    if (!h || !forms || !ranges || !n) return g_err.fail(XVEC_ERR_ARG, "null argument");
+    for (int i = 0; i < 3; ++i) {
+        forms[i] = h->last_aff_form[i];
+        ranges[i] = h->last_aff_ranges[i];
+    }
+    *n = 3;
     return XVEC_OK;
 }
 

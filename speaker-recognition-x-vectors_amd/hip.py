@@ -39,6 +39,8 @@ SEG6, SEG7, OUTPUT = 6, 7, 8
 KERNEL_NAMES = {0: None, 1: "tile128", 2: "pp", 3: "first"}      # XVEC_KERNEL_*
 FORM_NAMES = {0: "direct", 1: "winograd_f23", 2: "bf16_split3"}     # XVEC_FORM_*
 OPERAND_NAMES = {0: "fp32", 1: "bf16", 2: "bf16x3", 3: "bf16_split3"}     # XVEC_OPERANDS_*
+AFFINE_FORM_NAMES = {0: None, 1: "tile16", 2: "tile16_elementwise", 3: "splitk", 4: "splitk_bf16x3", 5: "direct",
+                     6: "direct_bf16x3"}                                     # XVEC_AFFINE_*
 TIMING_NAMES = ("tdnn1", "tdnn2", "tdnn3", "tdnn4", "tdnn5_pool", "pool_finalize",
                 "segment6", "segment7", "output", "pack")
 
@@ -98,11 +100,13 @@ _SIGS = {
     "xvec_tdnn_pool_layer": (C.c_int, [_vp, _f32p, _i32, _i32, C.c_int, _f32p, _vp, C.c_size_t, _vp]),
     "xvec_stat_pool": (C.c_int, [_f32p, _vp, _i32, _i32, _i32, _f32p, _vp]),
     "xvec_affine": (C.c_int, [_vp, C.c_int, _f32p, _i32, C.c_int, _f32p, _vp]),
+    "xvec_segment_layer": (C.c_int, [_vp, C.c_int, _f32p, _i32, C.c_int, C.c_int, _f32p, _vp, C.c_size_t, _vp]),
     "xvec_set_profiling": (C.c_int, [_vp, C.c_int]),
     "xvec_get_timings": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "xvec_get_dispatch": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_get_tdnn_form": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_get_tdnn_operands": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "xvec_get_affine_dispatch": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_mfcc_create": (C.c_int, [C.POINTER(MfccCfg), C.POINTER(_vp)]),
     "xvec_mfcc_destroy": (None, [_vp]),
     "xvec_mfcc_last_error": (C.c_char_p, []),
@@ -207,3 +211,11 @@ check = _checker(lib.xvec_last_error)
 
 def version() -> str:
     return lib.xvec_version().decode()
+
+
+def affine_dispatch(handle) -> list:
+    """[(form name, K ranges)] of the last launch of segment_layer6 / segment_layer7 / output on `handle`
+    (xvec_get_affine_dispatch; test introspection, nothing in the product calls it)."""
+    forms, ranges, n = (C.c_int * 3)(), (C.c_int * 3)(), C.c_int(0)
+    check(lib.xvec_get_affine_dispatch(handle, forms, ranges, C.byref(n)))
+    return [(AFFINE_FORM_NAMES[int(forms[i])], int(ranges[i])) for i in range(n.value)]

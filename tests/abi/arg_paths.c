@@ -53,6 +53,11 @@ int main(void) {
     EXPECT(xvec_tdnn_layer(0, 0, buf, 1, 32, XVEC_F32, buf, buf, sizeof buf, 0) == XVEC_ERR_ARG);
     EXPECT(xvec_tdnn_pool_layer(0, buf, 1, 32, XVEC_F32, buf, buf, sizeof buf, 0) == XVEC_ERR_ARG);
     EXPECT(xvec_affine(0, XVEC_SEG6, buf, 1, 0, buf, 0) == XVEC_ERR_ARG);
+    EXPECT(xvec_segment_layer(0, XVEC_SEG6, buf, 1, 0, XVEC_F32, buf, buf, sizeof buf, 0) == XVEC_ERR_ARG);
+    {
+        int forms[3], ranges[3];
+        EXPECT(xvec_get_affine_dispatch(0, forms, ranges, &n) == XVEC_ERR_ARG);
+    }
     EXPECT(xvec_set_profiling(0, 1) == XVEC_ERR_ARG);
     {
         xvec_ws_layout lay;

@@ -17,6 +17,8 @@ needs_hipcc_and_make = pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.wh
 # csrc/Makefile's CXXFLAGS without the host half (tests/test_support_modules.py ties the two)
 DEVICE_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "--cuda-device-only", "-fno-slp-vectorize", "-Wno-unused-function",
                 "-Wno-pass-failed", "-Wno-inline-asm"]
+HOST_CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+needs_host_cxx = pytest.mark.skipif(HOST_CXX is None, reason="needs a C++ compiler")
 _REPORT = (("scratch", r"ScratchSize \[bytes/lane\]: (\d+)"), ("vgprs", r" VGPRs: (\d+)"), ("spill", r"VGPRs Spill: (\d+)"),
            ("agprs", r" AGPRs: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)"),
            ("lds", r"LDS Size \[bytes/block\]: (\d+)"))
@@ -48,3 +50,21 @@ def kernel_resources(src):
 def kernel_asm(src):
     """The gfx950 assembly of csrc/`src`."""
     return _hipcc("-S", src, "-o", "-").stdout
+
+
+def host_program(name, out_dir, *flags):
+    """tests/abi/`name`.cpp (a stand-alone program over a host-only header of csrc/) compiled with the host compiler into
+    `out_dir`; returns ask(request lines) -> the program's answer lines, one per request."""
+    exe = os.path.join(str(out_dir), name)
+    src = os.path.join(ROOT, "tests", "abi", name + ".cpp")
+    out = subprocess.run([HOST_CXX, "-std=c++17", "-O1", "-Wall", *flags, "-I", CSRC, src, "-o", exe], capture_output=True, text=True,
+                         timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+
+    def ask(requests):
+        res = subprocess.run([exe], input="\n".join(requests) + "\n", capture_output=True, text=True, timeout=120)
+        assert res.returncode == 0, res.stderr[-500:]
+        lines = res.stdout.splitlines()
+        assert len(lines) == len(requests)
+        return lines
+    return ask

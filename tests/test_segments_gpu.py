@@ -247,3 +247,45 @@ def test_workspace_bound_and_handle_state(models, recs, precision):
     assert torch.isnan(out[3]).all() and torch.equal(out[keep], good[keep])
     # the handle is as it was: the whole-utterance path gives the same bits
     assert torch.equal(m.extract_x_vec(x, lengths=LENS), before)
+
+
+# ---------------------------------------------------------------------------------- many segments over few frames
+# The segment layers split K into the dead activation buffers, whose size follows the recording's FRAMES, while their M is the
+# number of SEGMENTS: one 333-frame recording offers 648 rows x 512 channels x 2 buffers = 663 552 floats, which holds two
+# partial results of 500 segments (split-K, two ranges), not two of 1000 (tile16: 16 x 8 = 128 tiles of 64 x 64) and not
+# two of 4100 either, where the 65 x 8 = 520 tiles fill the chip without a split (the direct form).  csrc/affine_plan.h;
+# tests/test_affine_forms_gpu.py runs the same forms on operands of their own.  None of the three lists is cut by the planner.
+DOZEN = np.asarray([(0, 0, 40), (0, 293, 40), (0, 0, 333), (0, 7, 55), (0, 100, 150), (0, 150, 16), (0, 33, 300), (0, 200, 99),
+                    (0, 61, 17), (0, 250, 83), (0, 120, 64), (0, 1, 128)], dtype=np.int32)
+MANY = {500: ("splitk", 2), 1000: ("tile16", 1), 4100: ("direct", 1)}
+
+
+@pytest.fixture(scope="module")
+def dozen_refs(sd42, recs):
+    p = float_params(sd42)
+    with torch.no_grad():
+        return torch.cat([oracle.extract_x_vec(recs[2, s:s + n][None], p) for _, s, n in DOZEN.tolist()])
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_many_segments_of_one_short_recording(models, recs, dozen_refs, precision):
+    from xvector_amd import hip, plan_segment_calls
+    m, bar = models[precision], BARS[precision]
+    assert LENS[2] == 333
+    x = recs[2:3].to(DEV)
+    eng = m._engine(torch.device(DEV))
+    base = m.extract_segments(x, DOZEN)
+    assert_parity(base, dozen_refs, what=f"{precision} the dozen windows vs oracle", **bar)
+    for n, (form, S) in MANY.items():
+        idx = np.random.default_rng(n).permutation(np.arange(n) % len(DOZEN))
+        seg = DOZEN[idx]
+        calls = plan_segment_calls(seg, 262144)
+        assert len(calls) == 1 and calls[0].pieces == [(0, 0, 333)], "the list is one call over the whole recording"
+        got = m.extract_segments(x, seg)
+        x3 = precision == "bf16" and form != "tile16"
+        assert hip.affine_dispatch(eng.h)[0] == (form + "_bf16x3" if x3 else form, S), (n, hip.affine_dispatch(eng.h))
+        assert got.shape == (n, 512)
+        first = np.asarray([int(np.flatnonzero(idx == k)[0]) for k in range(len(DOZEN))])
+        distinct = got[torch.from_numpy(first).to(DEV)]
+        assert torch.equal(got, distinct[torch.from_numpy(idx).to(DEV)]), f"{n} segments: duplicates of a window give different rows"
+        assert_parity(distinct, base, what=f"{precision} {n} segments vs the dozen windows alone", **bar)
