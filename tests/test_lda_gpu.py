@@ -46,7 +46,8 @@ def _on_device(x, dtype):
 
 
 def _stats_plan(rows, dim):
-    """(slices, rows_per_slice) of make_scatter_plan (csrc/lda.hip), from the same formulas."""
+    """(slices, rows_per_slice) of make_scatter_plan (csrc/class_scatter.h) at the 32 rows a slice of csrc/lda.hip, from the same
+    formulas."""
     tiles = (dim + 63) // 64
     n_tri = tiles * (tiles + 1) // 2
     slices = min(max(1, 1024 // n_tri), max(1, (rows + 31) // 32))

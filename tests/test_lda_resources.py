@@ -1,5 +1,5 @@
-"""Resource budget of the embedding-conditioning kernels (csrc/lda.hip), compiled for gfx950 on the CPU: every kernel of the file
-is there, none uses scratch or spills, and the LDS of each and the waves per SIMD it leaves are what DESIGN.md ("Embedding
+"""Resource budget of the embedding-conditioning kernels (csrc/lda.hip with the statistics kernels of csrc/class_scatter.h it
+instantiates), compiled for gfx950 on the CPU: every kernel of the file is there, none uses scratch or spills, and the LDS of each and the waves per SIMD it leaves are what DESIGN.md ("Embedding
 conditioning") states: two double-buffered 16 x 80 images for the scatter, a 64 x 18 and a 16 x 80 image for the transform."""
 import os
 import re
@@ -12,10 +12,10 @@ EMBED_LDS = 2 * 64 * 18 * 8 + 2 * 16 * 80 * 8   # sX: two buffers of 64 rows x 1
 # kernel -> (instances, LDS bytes per block, waves per SIMD)
 KERNELS = {
     "lda_class_sum_kernel": (2, 0, 8),
-    "lda_mean_kernel": (1, 16 * 16 * 8, 8),
+    "stats_mean_kernel": (1, 16 * 16 * 8, 8),
     "lda_class_mean_kernel": (1, 0, 8),
-    "lda_scatter_kernel": (4, SCATTER_LDS, 4),
-    "lda_scatter_reduce_kernel": (1, 0, 8),
+    "class_scatter_kernel": (4, SCATTER_LDS, 4),
+    "class_scatter_reduce_kernel": (1, 0, 8),
     "embed_transform_kernel": (4, EMBED_LDS, 4),
     "embed_centre_kernel": (2, 0, 8),
 }

@@ -32,7 +32,8 @@ def _data(n, dim, n_classes, seed):
 
 
 def _stats_plan(n, dim):
-    """(slices, rows_per_slice) of make_stats_plan (csrc/plda_train.hip), from the same formulas."""
+    """(slices, rows_per_slice) of make_scatter_plan (csrc/class_scatter.h) at the 256 rows a slice of csrc/plda_train.hip, from
+    the same formulas."""
     tiles = (dim + 63) // 64
     n_tri = tiles * (tiles + 1) // 2
     slices = min(max(1, 1024 // n_tri), max(1, (n + 255) // 256))

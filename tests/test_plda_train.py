@@ -2,6 +2,7 @@
 speechbrain's loop (tests/plda_em_ref.py, unpinned), the speechbrain-shaped surface, the C ABI's argument checks and the
 kernels' resources.  The device half is tests/test_plda_train_gpu.py."""
 import pickle
+import re
 
 import numpy as np
 import pytest
@@ -145,3 +146,11 @@ def test_plda_kernels_use_no_scratch():
     for k, r in kernels.items():
         assert r.get("scratch", 0) == 0 and r.get("spill", 0) == 0, f"{k}: {r}"
         assert r.get("vgprs", 0) + r.get("agprs", 0) <= 256, f"{k}: {r}"
+    # the kernels of csrc/class_scatter.h as this file instantiates them; the scatter kernel's two double-buffered 16 x 80
+    # images and __launch_bounds__(256, 4), as in tests/test_lda_resources.py
+    scatter = [k for k in kernels if re.search(r"\dclass_scatter_kernelI[fd]Lb[01]ELb0EE", k)]      # <T, VEC, PER_ROW = false>
+    assert len(scatter) == 4 and not any("class_scatter_kernel" in k for k in set(kernels) - set(scatter)), sorted(kernels)
+    for k in scatter:
+        assert kernels[k]["lds"] == 2 * 2 * 16 * 80 * 8 == 40960 and kernels[k]["occupancy"] == 4, f"{k}: {kernels[k]}"
+    for want in ("plda_class_sum_kernelI", "stats_mean_kernelE", "class_scatter_reduce_kernelE"):
+        assert any(re.search(rf"\d{want}", k) for k in kernels), (want, sorted(kernels))
