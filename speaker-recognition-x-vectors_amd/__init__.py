@@ -11,7 +11,8 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "evaluate_trials", "evaluate_all_pairs", "plda_score_stat_object", "augment", "WaveAugmenter", "AugmentPlan",
            "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam", "sliding_windows", "plan_segment_calls", "snorm",
            "ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm", "lda", "LDA", "LdaStats", "EmbeddingTransform",
-           "resample", "Resampler", "speed_perturb"]
+           "resample", "Resampler", "speed_perturb", "identify", "SpeakerModels", "SpeakerIdentifier", "enroll",
+           "open_set_scores", "identification_rate"]
 
 
 def __getattr__(name):
@@ -40,13 +41,16 @@ def __getattr__(name):
     if name in ("Resampler", "speed_perturb"):
         import importlib
         return getattr(importlib.import_module(".resample", __name__), name)
+    if name in ("SpeakerModels", "SpeakerIdentifier", "enroll", "open_set_scores", "identification_rate"):
+        import importlib
+        return getattr(importlib.import_module(".identify", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
     if name in ("XVectorTrainer", "tdnn_layer_train", "DeviceAdam"):
         from . import train
         return getattr(train, name)
-    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample"):
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

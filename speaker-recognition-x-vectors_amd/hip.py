@@ -32,6 +32,7 @@ OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_WORKSPACE, ERR_TOO_LARGE = 0, 1, 2, 3, 4, 5
 F32, BF16, BF16X3 = 0, 1, 2
 PLDA_X_F32, PLDA_X_F64 = 0, 1                                   # XVEC_PLDA_X_*
 LDA_X_F32, LDA_X_F64 = 0, 1                                     # XVEC_LDA_X_*
+IDENT_X_F32, IDENT_X_F64 = 0, 1                                 # XVEC_IDENT_X_*
 EMBED_MAX_DIM, EMBED_ROW_GROUP = 65536, 64                      # XVEC_EMBED_*
 AUG_POOL_F32, AUG_POOL_I16 = 0, 1                               # XVEC_AUG_POOL_*
 MODE_LOGITS, MODE_POOLED, MODE_XVEC6, MODE_XVEC7 = 0, 5, 6, 7
@@ -144,6 +145,13 @@ _SIGS = {
     "xvec_snorm_workspace_bytes": (C.c_size_t, [_i64, _i64]),
     "xvec_snorm_row_stats": (C.c_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     "xvec_snorm_apply": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # include/xvec_ident.h
+    "xvec_ident_last_error": (C.c_char_p, []),
+    "xvec_model_mean_workspace_bytes": (C.c_size_t, [_i32]),
+    "xvec_model_mean": (C.c_int, [_vp, _i32, _i64, _i32, _i64, _vp, C.POINTER(_i64), _i32, _vp, _vp, C.c_size_t, _vp]),
+    "xvec_ident_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32]),
+    "xvec_open_set_scores": (C.c_int, [_vp, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "xvec_identify_topk": (C.c_int, [_vp, _i64, _i64, _i64, _i32, C.c_double, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
     # include/xvec_lda.h
     "xvec_lda_last_error": (C.c_char_p, []),
     "xvec_lda_stats_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),

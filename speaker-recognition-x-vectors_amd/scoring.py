@@ -164,16 +164,21 @@ def fast_PLDA_scoring(enroll, test, ndx, mu, F, Sigma, p_known=0.0, scaling_fact
     """Drop-in for the call at plda_classifier.py:86.  enroll / test: objects with `.modelset`,
     `.segset`, `.stat1` (the reference's StatObject_SB); ndx: object with `.modelset`, `.segset`
     (and optionally `.trialmask`) or None.  Models and segments are scored in ndx order; names
-    missing from the stats are dropped, as the package's check_missing does."""
+    missing from the stats are dropped, as the package's check_missing does.  Several enrolment vectors under one model name
+    are averaged per model first (the package's mean_stat_per_model, `identify.enroll`): the models are then the sorted unique
+    names.  The open-set scores of p_known != 0 are `identify.open_set_scores` on the device matrix."""
     if p_known != 0:
-        raise NotImplementedError("open-set scoring (p_known != 0) is not on the reference's path (it passes 0.0)")
+        raise NotImplementedError("open-set scoring (p_known != 0) is not on the reference's path (it passes 0.0): score with "
+                                  "p_known=0.0 and call xvector_amd.identify.open_set_scores(S, p_known) on the device matrix")
     e_names = np.asarray(enroll.modelset)
     t_names = np.asarray(test.segset)
     e_x = np.asarray(enroll.stat1, dtype=np.float64)
     t_x = np.asarray(test.stat1, dtype=np.float64)
-    if len(set(e_names.tolist())) != len(e_names):
-        raise NotImplementedError("several enrolment vectors per model (per-model averaging) is not on the "
-                                  "reference's path: it enrols every utterance under its own id")
+    averaged = len(set(e_names.tolist())) != len(e_names)
+    if averaged:
+        from .identify import enroll as _enroll
+        models = _enroll(e_x, e_names, device=device)
+        e_names, e_x = models.names, models.vectors      # [M, D] on the device
     mask = None
     if ndx is not None:
         e_pos = {n: i for i, n in enumerate(e_names.tolist())}
@@ -190,7 +195,8 @@ def fast_PLDA_scoring(enroll, test, ndx, mu, F, Sigma, p_known=0.0, scaling_fact
         e_names, t_names = m_names, s_names
     # the reference scores the test set against ITSELF through two stat objects built from the same arrays
     # (plda_score_stat.py:19-20): same names and same vectors take the library's self path (upper triangle of tiles only)
-    same = e_names.tolist() == t_names.tolist() and (e_x is t_x or (e_x.shape == t_x.shape and np.array_equal(e_x, t_x)))
+    same = not averaged and e_names.tolist() == t_names.tolist() and (
+        e_x is t_x or (e_x.shape == t_x.shape and np.array_equal(e_x, t_x)))
     scorer = PldaScorer(mu, F, Sigma, scaling_factor=scaling_factor, device=device)
     mat = scorer.score(e_x, None if same else t_x)
     return Scores(e_names, t_names, mat.cpu().numpy(), mask)
