@@ -249,7 +249,7 @@ __device__ __forceinline__ float max1(float x, float m) {
 // sample of the same channel the sums are of deviations: the loss is ~1e-7*(1 + ((mean - K)/std)^2), and K is
 // within a few std of the mean.
 // Round 4: ONE pivot per (block, channel) -- the block's first frame (this utterance's or a neighbour's frame of
-// the same channel) -- and it rides in the accumulators: from the block's second tile on they start at
+// the same channel), cut to 8 significant bits (process_tile: why) -- and it rides in the accumulators: from the block's second tile on they start at
 // bias - K (tdnn_layer.hip, process_tile), so v = z + bias - K and a deviation is d = max(v, -K): one v_max, one
 // v_add and one v_fma per value (round 3: a per-group pivot subtracted here, after bias and ReLU: five).
 // negk = -K; both lane halves hold it.

@@ -345,7 +345,7 @@ struct Regs {
     float4 sA0_1, sA1_1, sA2_1, sA3_1, sB0_1, sB1_1, sB2_1, sB3_1;
     float4 fa0_0, fa1_0, fa2_0, fa3_0, fb_0, fa0_1, fa1_1, fa2_1, fa3_1, fb_1;
     float4 gb0_0, gb1_0, gb2_0, gb3_0, gb0_1, gb1_1, gb2_1, gb3_1;   // bf16: B fragments of two chunks, from global
-    float4 w3[2][6];     // bf16_split3: weight fragments of two chunks, [chunk parity][k-step * 3 + plane]
+    float4 w3[6];        // bf16_split3: the weight fragments of one chunk, [k-step * 3 + plane], reloaded in place
 };
 
 struct Lane {
@@ -362,14 +362,23 @@ struct Lane {
 // (the three dropped ones are below 2^-26 |x||w|) on v_mfma_f32_32x32x16_bf16 into ONE accumulator: the MFMA adds its
 // 16 products in two groups of 8 and rounds into the accumulator once per group (profiles/experiments/mfma_bf16_rounding.hip,
 // DESIGN 3.1c).  Six 32-cycle MFMAs replace eight 64-cycle fp32 ones per 32x32x16 block: 0.375 of the matrix-pipe time.
-//   * K chunks stay 32 fp32 wide (the fp32 staging path, two staging sets, loads ~1.5 chunks ahead).  An LDS buffer holds
-//     the chunk's three planes, 8 KiB each: rows of 64 B (32 k), 16-byte pieces XOR-swizzled by (row >> 2) & 3, so the
-//     ds_write_b64 stores and the ds_read_b128 fragment reads (lane (r, h) of k-step s: row r, k 16s + 8h .. +7) are
-//     bank-conflict free.
+//   * K chunks stay 32 fp32 wide (the fp32 staging path).  An LDS buffer holds the chunk's three planes, 8 KiB each: rows of
+//     64 B (32 k), 16-byte pieces XOR-swizzled by (row >> 2) & 3, so the ds_write_b64 stores and the ds_read_b128 fragment
+//     reads (lane (r, h) of k-step s: row r, k 16s + 8h .. +7) are bank-conflict free.
 //   * the weight planes go from global memory straight into the MFMA B operand (one KiB per plane and k-step of a
-//     32-channel column, hi | mid | lo), loaded one chunk ahead.
+//     32-channel column, hi | mid | lo), loaded one chunk ahead into the registers their last product has just left.
+//   * three blocks per CU: 168 registers -- 64 accumulators, ONE staging set of 16 (a chunk of lead, as bf16x3:
+//     with three waves per SIMD a chunk lasts several load latencies), six weight fragments reloaded in place, two rolling
+//     sets of three activation fragments -- and kS3LdsBytes of LDS, the buffers packed at their 24 KiB.
 // ---------------------------------------------------------------------------------------------
 constexpr int kPlaneBytes = kBM * kBK * 2;   // one bf16 plane of a 128 x 32 chunk
+// LDS of the split form: two buffers of three planes, then the constants table -- 50 688 B, three blocks per CU (the fp32 /
+// bf16 instantiations keep kLdsBytes, two 32 KiB buffers)
+constexpr int kS3BufBytes = 3 * kPlaneBytes;
+constexpr int kS3LdsBytes = 2 * kS3BufBytes + kConstFloats * 4;
+// first float of the constants table (bias | scale | shift) in a block's LDS
+template <bool S3>
+constexpr int kCstFloat = S3 ? 2 * kS3BufBytes / 4 : 2 * kStageFloats;
 
 // staging registers of row group i (fp32, 16 bytes) -> the three planes of LDS buffer B
 __device__ __forceinline__ void s3_store(char* B, int st3, int i, const float4& v) {
@@ -391,39 +400,53 @@ __device__ __forceinline__ void s3_gld(const TdnnArgs& a, const Ctx& cx, float4&
     if constexpr (NG > 3) d3 = buf_load16(cx.xrsrc, cx.xo3, soff + 3 * rs);
 }
 
-// the six weight fragments (2 k-steps x hi | mid | lo) of chunk c of this wave's column; the stream wraps to chunk 0
-// past the tile's last chunk (the next tile of the block is in the same channel column)
-__device__ __forceinline__ void s3_wld(const Ctx& cx, float4* w, int c, int n_chunks) {
+// the three weight fragments (hi | mid | lo) of k-step s of chunk c of this wave's column -> w[3s ..]; the stream wraps to
+// chunk 0 past the tile's last chunk (the next tile of the block is in the same channel column)
+__device__ __forceinline__ void s3_wld(const Ctx& cx, float4* w, int c, int s, int n_chunks) {
     if (c >= n_chunks) c -= n_chunks;
 #pragma unroll
-    for (int j = 0; j < 6; ++j) w[j] = buf_load16(cx.wfrsrc, cx.wf_voff, (6 * c + j) * 1024);
+    for (int j = 0; j < 3; ++j) w[3 * s + j] = buf_load16(cx.wfrsrc, cx.wf_voff, (6 * c + 3 * s + j) * 1024);
 }
 
-// One K-chunk: chunk `it` is in LDS buffer P (weights in rg.w3[P]); staging set N holds chunk it + 1, which goes to
+// the three plane fragments of row group i, k-step s of the chunk in LDS buffer S
+__device__ __forceinline__ void s3_frag(const char* S, int rd3, int i, int s, float4* xf) {
+#pragma unroll
+    for (int pl = 0; pl < 3; ++pl)
+        xf[pl] = *reinterpret_cast<const float4*>(S + pl * kPlaneBytes + i * 32 * 64 + (rd3 ^ (32 * s)));
+}
+
+// Item N of a chunk's 2 G (k-step s = N / G, row group i = N % G): the fragments of item N + 1 go into the other of the two
+// rolling sets, then the six products of item N; behind a k-step's last row group its three weight registers are free and
+// take the same k-step of chunk c_next (tdnn_wino_s3.hip reloads U the same way), so ONE set of six holds the stream.
+template <int G, int N>
+__device__ __forceinline__ void s3_item(const Ctx& cx, const char* S, int rd3, f32x16& acc, float4 (&xf)[2][3], float4* w,
+                                        int c_next, int n_chunks) {
+    constexpr int s = N / G, i = N % G;
+    if constexpr (N + 1 < 2 * G) s3_frag(S, rd3, (N + 1) % G, (N + 1) / G, xf[(N + 1) & 1]);
+    s3_mfma6(acc, xf[N & 1], w + 3 * s);
+    if constexpr (i == G - 1) s3_wld(cx, w, c_next, s, n_chunks);
+}
+
+// One K-chunk: chunk `it` is in LDS buffer P, its weights in rg.w3; staging set N holds chunk it + 1, which goes to
 // buffer N (free: every wave passed the previous chunk's barrier after its last fragment read), then set N is refilled
-// with the chunk the stream points at next and rg.w3[N] with the weights of chunk it + 1.
+// with the chunk the stream points at next.  The order of the products into each accumulator is the chunk's k-steps in
+// turn, whatever the order of the row groups around them.
+#define XV_S3_ITEM(i_, s_, IT_)                                                                           \
+    if constexpr (G > i_) { s3_item<G, s_ * G + i_>(cx, S, ln.rd3, acc##i_, xf, rg.w3, (IT_) + 1, n_chunks); SB(); }
 #define XV_S3_CHUNK(P_, N_, IT_)                                                                          \
     {                                                                                                     \
-        const char* S = reinterpret_cast<const char*>(smem) + P_ * kStageFloats * 4;                      \
-        char* Sn = reinterpret_cast<char*>(smem) + N_ * kStageFloats * 4;                                 \
-        if constexpr (G > 0) s3_store(Sn, ln.st3, 0, rg.sA0_##N_);                                         \
-        if constexpr (G > 1) s3_store(Sn, ln.st3, 1, rg.sA1_##N_);                                         \
-        if constexpr (G > 2) s3_store(Sn, ln.st3, 2, rg.sA2_##N_);                                         \
-        if constexpr (G > 3) s3_store(Sn, ln.st3, 3, rg.sA3_##N_);                                         \
+        const char* S = reinterpret_cast<const char*>(smem) + P_ * kS3BufBytes;                           \
+        char* Sn = reinterpret_cast<char*>(smem) + N_ * kS3BufBytes;                                      \
+        float4 xf[2][3];                                                                                  \
+        s3_frag(S, ln.rd3, 0, 0, xf[0]);                                                                  \
+        if constexpr (G > 0) s3_store(Sn, ln.st3, 0, rg.sA0_0);                                           \
+        if constexpr (G > 1) s3_store(Sn, ln.st3, 1, rg.sA1_0);                                           \
+        if constexpr (G > 2) s3_store(Sn, ln.st3, 2, rg.sA2_0);                                           \
+        if constexpr (G > 3) s3_store(Sn, ln.st3, 3, rg.sA3_0);                                           \
         advance<GUARD, false>(a, cx, n_chunks);                                                           \
-        s3_gld<G>(a, cx, rg.sA0_##N_, rg.sA1_##N_, rg.sA2_##N_, rg.sA3_##N_);                              \
-        s3_wld(cx, rg.w3[N_], (IT_) + 1, n_chunks);                                                       \
-        _Pragma("unroll") for (int s3 = 0; s3 < 2; ++s3) {                                                \
-            const int rd = ln.rd3 ^ (32 * s3);                                                            \
-            float4 xf[4][3];                                                                              \
-            _Pragma("unroll") for (int i = 0; i < G; ++i)                                                 \
-                _Pragma("unroll") for (int pl = 0; pl < 3; ++pl)                                          \
-                    xf[i][pl] = *reinterpret_cast<const float4*>(S + pl * kPlaneBytes + i * 32 * 64 + rd); \
-            if constexpr (G > 0) s3_mfma6(acc0, xf[0], rg.w3[P_] + 3 * s3);                                \
-            if constexpr (G > 1) s3_mfma6(acc1, xf[1], rg.w3[P_] + 3 * s3);                                \
-            if constexpr (G > 2) s3_mfma6(acc2, xf[2], rg.w3[P_] + 3 * s3);                                \
-            if constexpr (G > 3) s3_mfma6(acc3, xf[3], rg.w3[P_] + 3 * s3);                                \
-        }                                                                                                 \
+        s3_gld<G>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);                                         \
+        XV_S3_ITEM(0, 0, IT_) XV_S3_ITEM(1, 0, IT_) XV_S3_ITEM(2, 0, IT_) XV_S3_ITEM(3, 0, IT_)           \
+        XV_S3_ITEM(0, 1, IT_) XV_S3_ITEM(1, 1, IT_) XV_S3_ITEM(2, 1, IT_) XV_S3_ITEM(3, 1, IT_)           \
         __syncthreads(); /* chunk it+1 complete in LDS; chunk it's buffer is free */                     \
     }
 
@@ -435,12 +458,11 @@ __device__ __forceinline__ void block_prologue(const TdnnArgs& a, float* smem, C
     constexpr int G = 4;   // fetch all four row groups: rows past a short first tile are allocated
     constexpr int ES = INBF ? 2 : 4, BKE = 128 / ES;
     const int h = ln.h, sw = ln.sw, a_rd = ln.a_rd, b_rd = ln.b_rd, st_off = ln.st_off, c = ln.c;
-    if constexpr (S3) {      // chunk 0 -> LDS buffer 0 (split), chunk 1 in staging set 1, chunk 2 in set 0, weights of chunk 0
+    if constexpr (S3) {      // chunk 0 -> LDS buffer 0 (split), chunk 1 in flight in the one staging set, weights of chunk 0
         char* B0 = reinterpret_cast<char*>(smem);
         s3_gld<4>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);
-        advance<GUARD, false>(a, cx, n_chunks);
-        s3_gld<4>(a, cx, rg.sA0_1, rg.sA1_1, rg.sA2_1, rg.sA3_1);
-        s3_wld(cx, rg.w3[0], 0, n_chunks);
+        s3_wld(cx, rg.w3, 0, 0, n_chunks);
+        s3_wld(cx, rg.w3, 0, 1, n_chunks);
         s3_store(B0, ln.st3, 0, rg.sA0_0);
         s3_store(B0, ln.st3, 1, rg.sA1_0);
         s3_store(B0, ln.st3, 2, rg.sA2_0);
@@ -490,7 +512,7 @@ __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx
     constexpr bool SWAP = INBF && OUTBF && !X3 && STORE && !POOL;
     f32x16 acc0, acc1, acc2, acc3;
     // this wave's 32 channels, the lane half's 4 of every 8 (SWAP): bias | scale | shift tables in LDS
-    const float* cstw = smem + 2 * kStageFloats + (ln.col - n0 - (int)(threadIdx.x & 31)) + 4 * ln.h;
+    const float* cstw = smem + kCstFloat<S3> + (ln.col - n0 - (int)(threadIdx.x & 31)) + 4 * ln.h;
     if constexpr (SWAP) {      // accumulators start at the bias of their register's channel
 #pragma unroll
         for (int gq = 0; gq < 4; ++gq) {
@@ -502,7 +524,7 @@ __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx
         // accumulators start at bias - K, K = the block's pooling pivot of this lane's channel (at 0 in the block's
         // first tile, whose epilogue picks K and adds bias - K: a large bias must not sit in the accumulator while
         // the K loop adds small terms to it -- every MFMA would round at ulp(bias)): tdnn_common.h, pool_group_impl
-        const float b0 = smem[2 * kStageFloats + kBN + (ln.col - n0)];
+        const float b0 = smem[kCstFloat<S3> + kBN + (ln.col - n0)];
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc0[e] = b0;
         acc1 = acc0; acc2 = acc0; acc3 = acc0;
@@ -541,15 +563,21 @@ __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx
     const int col = ln.col;
     // epilogue constants of this lane's channel: three LDS reads per tile instead of three registers held
     // across the K loop (the pooling and first-layer variants were 3-6 registers over the 256 budget)
-    float* cst = smem + 2 * kStageFloats + (col - n0);
+    float* cst = smem + kCstFloat<S3> + (col - n0);
     const float bi = cst[0], sc = cst[kBN], sh = cst[2 * kBN];
     // pooling variants: the three slots are bias | bias - K | -K (this wave's own channels: no barrier)
     float negk = sh;
     if constexpr (POOL) {
         if (!cx.pivot_set) {       // block-uniform: the block's first tile, whose accumulators started at 0
-            const float piv = lower_half(fmaxf(acc0[0] + bi, 0.f));     // r of the block's first frame
+            // r of the block's first frame, cut to its upper 8 significant bits, and -K itself in the table.  A channel that is
+            // off in an utterance of a block whose first frame (another utterance's) has it on contributes n equal terms -K: with
+            // 8 bits their sums and the sums of their squares are exact in fp32 over a 32-row partial, so pool_finalize gets a
+            // second moment of exactly 0 wherever the block boundaries fall (with 24 bits: ~3e-4 K of std or 0, by the last
+            // bits of K -- and where the boundaries fall changes with the blocks per CU and from form to form).  Every form of
+            // this body cuts alike, so the forms agree on such channels; tdnn_pp16.hip's pivots are bf16 too.
+            const float piv = __uint_as_float(__float_as_uint(lower_half(fmaxf(acc0[0] + bi, 0.f))) & 0xffff0000u);
             const float bmk = bi - piv;
-            negk = bmk - bi;                                      // minus the pivot the tiles really carry
+            negk = -piv;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 acc0[e] += bmk;
@@ -671,9 +699,9 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
     ln.st3 = ln.r0 * 64 + ((((ln.c >> 1) ^ ((ln.r0 >> 2) & 3)) * 16) | ((ln.c & 1) * 8));
     ln.rd3 = r * 64 + ((ln.h ^ ((r >> 2) & 3)) * 16);
     if (tid < kBN) {
-        smem[2 * kStageFloats + tid] = a.bias[n0 + tid];
-        smem[2 * kStageFloats + kBN + tid] = POOL ? 0.f : a.scale[n0 + tid];
-        smem[2 * kStageFloats + 2 * kBN + tid] = POOL ? 0.f : a.shift[n0 + tid];
+        smem[kCstFloat<S3> + tid] = a.bias[n0 + tid];
+        smem[kCstFloat<S3> + kBN + tid] = POOL ? 0.f : a.scale[n0 + tid];
+        smem[kCstFloat<S3> + 2 * kBN + tid] = POOL ? 0.f : a.shift[n0 + tid];
     }
 
     Ctx cx;
@@ -731,12 +759,12 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
 }
 
 template <typename K>
-static hipError_t launch_kernel(K kern, const TdnnArgs& a, hipStream_t s, LdsOptIn& opt) {
+static hipError_t launch_kernel(K kern, const TdnnArgs& a, hipStream_t s, LdsOptIn& opt, int lds_bytes = kLdsBytes) {
     if (a.groups_total <= 0 || a.blocks_per_col <= 0 || a.blocks_per_col > a.groups_total || (a.cpt & 1))
         return hipErrorInvalidValue;
-    if (hipError_t e = opt.ensure(reinterpret_cast<const void*>(kern), kLdsBytes); e != hipSuccess) return e;
+    if (hipError_t e = opt.ensure(reinterpret_cast<const void*>(kern), lds_bytes); e != hipSuccess) return e;
     const int grid = a.blocks_per_col * a.n_tiles;
-    kern<<<dim3(grid), dim3(256), kLdsBytes, s>>>(a);
+    kern<<<dim3(grid), dim3(256), lds_bytes, s>>>(a);
     return hipGetLastError();
 }
 

@@ -44,7 +44,8 @@ constexpr int kWinoS3MinRowsPerCu = 64;
 
 // The dispatch knobs, read from the environment once, when a handle is created (A/B runs and crossover sweeps, profiles/)
 struct Policy {
-    int blocks_per_cu;      // XVEC_BLOCKS_PER_CU: persistent TDNN blocks per CU (2: what the LDS allows)
+    int blocks_per_cu;      // XVEC_BLOCKS_PER_CU: persistent TDNN blocks per CU for every kernel, capped at what the kernel holds
+                            // (blocks_per_cu below); 0 = unset: each kernel's own (bf16_split3 three, the rest two)
     bool pp;                // XVEC_PP=0 disables the large-batch bf16 mapping (tdnn_pp16.hip) and the streaming layer 1
     int pp_min_tenths;      // XVEC_PP_MIN_TENTHS: ... taken from this many tenths of a 64-frame unit per CU on (18)
     int pp_cu_pct;          // XVEC_PP_CU_PCT (diagnostic): percentage of the CUs the large-batch kernel's grid covers (0 = all)
@@ -63,7 +64,7 @@ int env_int(const char* name, int unset) {
 Policy read_policy() {
     const int tenths = env_int("XVEC_PP_MIN_TENTHS", 18), s3_rows = env_int("XVEC_SPLIT3_MIN_ROWS", kSplit3MinRowsPerCu);
     const int ws3_rows = env_int("XVEC_WINO_SPLIT3_MIN_ROWS", kWinoS3MinRowsPerCu);
-    return {std::max(1, env_int("XVEC_BLOCKS_PER_CU", 2)), env_int("XVEC_PP", 1) != 0, tenths > 0 ? tenths : 18,
+    return {std::max(0, env_int("XVEC_BLOCKS_PER_CU", 0)), env_int("XVEC_PP", 1) != 0, tenths > 0 ? tenths : 18,
             env_int("XVEC_PP_CU_PCT", 0), env_int("XVEC_WINOGRAD", 1) != 0, env_int("XVEC_SPLIT3", 1) != 0,
             s3_rows >= 0 ? s3_rows : kSplit3MinRowsPerCu, env_int("XVEC_WINO_SPLIT3", 1) != 0,
             ws3_rows >= 0 ? ws3_rows : kWinoS3MinRowsPerCu};
@@ -125,6 +126,7 @@ struct xvec_handle {
     bool offs_pending[2];
     int offs_next;
     int num_cu;
+    int split3_blocks_cu;              // blocks of tdnn_split3_kernel the device holds per CU, at most 3 (asked once, xvec_create)
     Policy pol;
     int last_kernel[XVEC_NUM_TDNN];    // XVEC_KERNEL_* the last launch of each frame-level layer went to (xvec_get_dispatch)
     int last_form[XVEC_NUM_TDNN];      // XVEC_FORM_* of that launch (xvec_get_tdnn_form)
@@ -258,13 +260,21 @@ int pp_blocks_per_col(const xvec_handle* h, int n_pad, int64_t rows_out) {
     return (bpc >= 1 && units >= bpc && 10 * units >= pol.pp_min_tenths * (int64_t)bpc) ? bpc : 0;
 }
 
-// Persistent grid of the 128x128 family (direct, bf16_split3, Winograd): blocks per 128-channel column, and the period of the
-// CU-pair-aware range sizes, which need the full 2-blocks-per-CU grid and whole XCD runs per half (0: off).  The kernels
-// split groups_total over these blocks with group_range (tdnn_common.h).
-void persistent_grid(const xvec_handle* h, int n_tiles, int64_t groups_total, int* blocks_per_col, int* pair_period) {
-    const int per_col = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cu * h->pol.blocks_per_cu / n_tiles, groups_total));
+// Blocks per CU of a persistent kernel of the 128x128 family: what the kernel holds (bf16_split3: three if the device said so
+// when the handle was created, the rest two), or XVEC_BLOCKS_PER_CU capped at that
+int blocks_per_cu(const xvec_handle* h, bool split3) {
+    const int holds = split3 ? h->split3_blocks_cu : 2;
+    return h->pol.blocks_per_cu > 0 ? std::min(h->pol.blocks_per_cu, holds) : holds;
+}
+
+// Persistent grid of the 128x128 family (direct, bf16_split3, Winograd) at `per_cu` blocks per CU: blocks per 128-channel
+// column, and the period of the CU-pair-aware range sizes, which need the full 2-blocks-per-CU grid and whole XCD runs per
+// half (0: off, and always at three blocks per CU).  The kernels split groups_total over these blocks with group_range
+// (tdnn_common.h).
+void persistent_grid(const xvec_handle* h, int per_cu, int n_tiles, int64_t groups_total, int* blocks_per_col, int* pair_period) {
+    const int per_col = (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)h->num_cu * per_cu / n_tiles, groups_total));
     const int nwg = per_col * n_tiles;
-    const bool ok = h->pol.blocks_per_cu == 2 && nwg == 2 * h->num_cu && nwg % 16 == 0 && (nwg / 8) % (2 * n_tiles) == 0;
+    const bool ok = per_cu == 2 && nwg == 2 * h->num_cu && nwg % 16 == 0 && (nwg / 8) % (2 * n_tiles) == 0;
     *blocks_per_col = per_col;
     *pair_period = ok ? (nwg / 8) / n_tiles : 0;
 }
@@ -332,7 +342,7 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
     a.k_pad = x3 ? 2 * g.k_pad : g.k_pad;
     a.n_tiles = g.n_pad / 128;
     a.groups_total = (c.rows_out + 31) / 32;
-    persistent_grid(h, a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
+    persistent_grid(h, blocks_per_cu(h, false), a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
     a.pool_part = c.part;
     a.pool_cnt = c.part_cnt;
     a.out_map = c.map;
@@ -369,6 +379,8 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
         lp.operands = XVEC_OPERANDS_BF16_SPLIT3;
         a.terms = 3;
         a.Wf = h->Wp3[l];
+        // three blocks per CU (50 688 B of LDS, 168 registers): a third instruction stream per SIMD for the matrix pipe
+        persistent_grid(h, blocks_per_cu(h, true), a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
     } else if (!bf && from_act && !pool && h->pol.wino && h->Wu[l] && tdnn_wino_applicable(g, c.ldx)) {
         // fp32, three equally spaced taps: Winograd F(2,3) along time (tdnn_wino.hip), 2/3 of the direct form's products; the
         // same kernel family (persistent fp32, 128 x 128 output tiles)
@@ -381,7 +393,7 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
         const int64_t pairs = c.map.offsets ? (c.rows_out >> 1) + (int64_t)c.map.n_utts * g.tap_rows     // pair_base(n_utts)
                                             : (int64_t)c.map.n_utts * a.p_fixed;
         a.groups_total = (pairs + 31) / 32;
-        persistent_grid(h, a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
+        persistent_grid(h, blocks_per_cu(h, false), a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
         if (h->pol.wino_split3 && h->Wu3[l] && tdnn_wino_s3_applicable(g, c.ldx) &&
             c.rows_out >= (int64_t)h->pol.wino_s3_min_rows * h->num_cu) {
             // large batch: the same pairs and grid with bf16_split3 operands (tdnn_wino_s3.hip), 0.375 of the fp32 MFMA time
@@ -749,6 +761,14 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
     h->cfg = *cfg;
     h->num_cu = device_cu_count();
     h->pol = read_policy();
+    // three persistent blocks of the split form per CU only where the device really holds them: 768 blocks on a CU that takes
+    // two at a time would run in two rounds
+    int s3_blocks = 0;
+    if (hipError_t e = tdnn_split3_max_blocks_per_cu(&s3_blocks); e != hipSuccess) {
+        delete h;
+        return g_err.fail(XVEC_ERR_HIP, "occupancy query of tdnn_split3_kernel failed: %s", hipGetErrorString(e));
+    }
+    h->split3_blocks_cu = std::max(1, std::min(3, s3_blocks));
     h->cin_pad = round_up(cfg->input_size, 4);
     fill_geometry(h, h->geo, 2 * kBK);
     fill_geometry(h, h->geo16, 4 * kBK);

@@ -126,6 +126,8 @@ struct TdnnMode { Prec prec; Src src; Dst dst; };
 hipError_t launch_tdnn(const TdnnArgs& a, TdnnMode m, hipStream_t s);
 // bf16_split3 form of an fp32 one-tap layer (terms == 3), store or pooling epilogue: tdnn_split3.hip
 hipError_t launch_tdnn_split3(const TdnnArgs& a, bool pool, hipStream_t s);
+// blocks of it (the fewer of its two variants) the current device keeps resident per CU, at its block and LDS size
+hipError_t tdnn_split3_max_blocks_per_cu(int* blocks);
 // Large-batch bf16 mapping (tdnn_pp16.hip, v_mfma_f32_16x16x32_bf16): 256-channel columns, 64-frame units.  Reads TdnnArgs with
 //   W = K-tile major bf16 [n_pad/256][k_pad/64][256][64] (K order as the fp32 packing, 64-element chunks), n_tiles = n_pad / 256,
 //   groups_total = ceil(rows / 64) units, blocks_per_col ranges per column (>= 1.8 units each: the measured crossover with the 128x128 kernel).
