@@ -12,7 +12,8 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "train", "XVectorTrainer", "tdnn_layer_train", "DeviceAdam", "sliding_windows", "plan_segment_calls", "snorm",
            "ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm", "lda", "LDA", "LdaStats", "EmbeddingTransform",
            "resample", "Resampler", "speed_perturb", "identify", "SpeakerModels", "SpeakerIdentifier", "enroll",
-           "open_set_scores", "identification_rate"]
+           "open_set_scores", "identification_rate", "diarize", "Diarizer", "Diarization", "Clustering", "cluster", "turns",
+           "write_rttm"]
 
 
 def __getattr__(name):
@@ -44,13 +45,17 @@ def __getattr__(name):
     if name in ("SpeakerModels", "SpeakerIdentifier", "enroll", "open_set_scores", "identification_rate"):
         import importlib
         return getattr(importlib.import_module(".identify", __name__), name)
+    if name in ("Diarizer", "Diarization", "Clustering", "cluster", "turns", "write_rttm"):
+        import importlib
+        return getattr(importlib.import_module(".diarize", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
     if name in ("XVectorTrainer", "tdnn_layer_train", "DeviceAdam"):
         from . import train
         return getattr(train, name)
-    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify"):
+    if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
+                "diarize"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

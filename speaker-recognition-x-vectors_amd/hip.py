@@ -152,6 +152,11 @@ _SIGS = {
     "xvec_ident_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32]),
     "xvec_open_set_scores": (C.c_int, [_vp, _i64, _i64, _i64, C.c_double, _vp, _i64, _vp, C.c_size_t, _vp]),
     "xvec_identify_topk": (C.c_int, [_vp, _i64, _i64, _i64, _i32, C.c_double, _vp, _vp, _vp, _vp, C.c_size_t, _vp]),
+    # include/xvec_diar.h
+    "xvec_diar_last_error": (C.c_char_p, []),
+    "xvec_ahc_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i32]),
+    "xvec_ahc_cluster": (C.c_int, [_vp, _i64, C.POINTER(_i64), _i32, C.c_double, _i32, C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp,
+                                   _vp, C.c_size_t, _vp]),
     # include/xvec_lda.h
     "xvec_lda_last_error": (C.c_char_p, []),
     "xvec_lda_stats_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),
