@@ -73,6 +73,36 @@ __device__ __forceinline__ void wave_lds_sync() {
 
 constexpr int kWavesPerBlock = kThreads / 64;
 
+// Both kernels transform a PAIR of frames as one complex signal (frame A real part, frame B imaginary part) and split the two
+// spectra afterwards.  In fp32 the split hands each frame the OTHER frame's rounding noise (~1e-7 of ITS amplitude): a frame
+// 80 dB under its partner came out 1.2e-3 off row-wise, room noise beside speech in 16-bit PCM.  So the quieter frame is brought to its
+// partner's level before the transform, by the power of two that makes the exponents of the two peaks (largest |sample|) equal,
+// and its power is scaled back by the square afterwards -- exact both ways, and the noise a frame receives is relative to its own level
+// again.  Peaks fewer than kPairGap binades apart are left alone (neighbouring frames of one signal: the common case computes
+// what it always did); a frame of exact zeros next to a live one gets power scale 0, so that it comes out as the package's
+// log(eps) and not as the log of the partner's noise.
+constexpr int kPairGap = 4;      // binades between the peaks from which the quiet frame is scaled (residual gap: under 24 dB)
+constexpr int kPairMax = 60;     // largest shift: 2^-120 on the power is still a normal number
+struct PairScale {
+    float sa, sb;                // sample scales (one of them 1)
+    float ka, kb;                // power scales: 1 / s^2, or 0 for an all-zero frame
+    bool special;                // any of the four is not 1
+};
+// exp_a, exp_b: biased exponents of the two peaks (any monotone 8-bit code of them does)
+__device__ __forceinline__ PairScale pair_scale(int exp_a, int exp_b, bool live_a, bool live_b) {
+    PairScale s{1.f, 1.f, live_a ? 1.f : 0.f, live_b ? 1.f : 0.f, live_a != live_b};
+    int g = exp_a - exp_b;       // > 0: frame B is the quiet one
+    if (live_a && live_b && (g >= kPairGap || g <= -kPairGap)) {
+        g = g > kPairMax ? kPairMax : g < -kPairMax ? -kPairMax : g;
+        const int m = g > 0 ? g : -g;
+        const float up = __uint_as_float((unsigned)(127 + m) << 23), down = __uint_as_float((unsigned)(127 - 2 * m) << 23);
+        if (g > 0) s.sb = up, s.kb = down;
+        else s.sa = up, s.ka = down;
+        s.special = true;
+    }
+    return s;
+}
+
 // One WAVE per PAIR of frames (eight frames per 256-thread block).  The block first copies the
 // small tables (twiddles, DCT x lifter rows, the non-zero filterbank weights) into LDS.  Each wave
 // then packs its two real frames into ONE complex signal (frame A real part, frame B imaginary
@@ -121,6 +151,7 @@ __global__ __launch_bounds__(kThreads) void mfcc_kernel(const void* __restrict__
     const int used = d.frame_len < nfft ? d.frame_len : nfft;   // rfft(frame, nfft) truncates long frames
 
     // ---- the two pre-emphasised frames, zero padded to nfft, as one complex signal in bit-reversed order
+    float peak_a = 0.f, peak_b = 0.f;
 #pragma unroll
     for (int n = lane; n < nfft; n += 64) {
         float va = 0.f, vb = 0.f;
@@ -129,9 +160,26 @@ __global__ __launch_bounds__(kThreads) void mfcc_kernel(const void* __restrict__
             if (ga < n_samples) va = (ga == 0) ? smp(s0) : smp(s0 + ga) - d.preemph * smp(s0 + ga - 1);
             if (has_b && gb < n_samples) vb = smp(s0 + gb) - d.preemph * smp(s0 + gb - 1);
         }
+        peak_a = fmaxf(peak_a, fabsf(va));
+        peak_b = fmaxf(peak_b, fabsf(vb));
         z[zpos((int)bitrev((unsigned)n, log2n))] = make_float2(va, vb);
     }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        peak_a = fmaxf(peak_a, __shfl_xor(peak_a, o));
+        peak_b = fmaxf(peak_b, __shfl_xor(peak_b, o));
+    }
     wave_lds_sync();
+    // the quieter frame at its partner's level, an all-zero frame at power 0 (pair_scale)
+    const unsigned bits_a = __float_as_uint(peak_a), bits_b = __float_as_uint(peak_b);
+    const PairScale ps = pair_scale((int)(bits_a >> 23), (int)(bits_b >> 23), bits_a != 0u, bits_b != 0u);
+    if (ps.sa != 1.f || ps.sb != 1.f) {                               // (uniform, rare)
+        for (int n = lane; n < nfft; n += 64) {
+            const float2 v = z[zpos(n)];
+            z[zpos(n)] = make_float2(v.x * ps.sa, v.y * ps.sb);
+        }
+        wave_lds_sync();
+    }
 
     // ---- decimation-in-time FFT on the bit-reversed image, two radix-2 stages per pass: the four
     // points {p, p+h, p+2h, p+3h} (h = 4^pass, bits of weight h and 2h clear in p) form a closed
@@ -185,7 +233,9 @@ __global__ __launch_bounds__(kThreads) void mfcc_kernel(const void* __restrict__
     for (int k = lane; k < d.nbins; k += 64) {
         const float2 p = z[zpos(k)], q = z[zpos((nfft - k) & (nfft - 1))];
         const float ar = p.x + q.x, ai = p.y - q.y, br = p.y + q.y, bi = q.x - p.x;
-        const float pa = (ar * ar + ai * ai) * scale, pb = (br * br + bi * bi) * scale;
+        float pa = (ar * ar + ai * ai) * scale, pb = (br * br + bi * bi) * scale;
+        pa = ps.ka == 0.f ? 0.f : pa * ps.ka;                     // (1 but for a scaled or an all-zero frame)
+        pb = ps.kb == 0.f ? 0.f : pb * ps.kb;
         work[k] = pa;
         work[nb_pad + k] = pb;
         ea += pa;
@@ -318,6 +368,22 @@ __device__ __forceinline__ float wave_sum(float v) {
     b = a;
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));          // halves {lo|lo}, {hi|hi}
     return a + b;
+}
+
+// Maximum over the 64 lanes, uniform, without LDS: within each row of 16 lanes by the DPP steps of wave_sum (every lane of a
+// row then holds the row's maximum), then row_bcast15 / row_bcast31 hand rows 0 and 2 to rows 1 and 3 and row 1 to rows 2 and
+// 3, so lane 63 holds all four (a row the step leaves out reads 0, the maximum's identity).  Six v_max_u32 with a DPP operand
+// and one v_readlane; on the bits of a non-negative float the unsigned order is the float order.
+__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
+#define MF_DPP_MAX(ctrl_, rows_) v = max(v, (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, ctrl_, rows_, 0xf, false));
+    MF_DPP_MAX(0x140, 0xf)     // row_mirror
+    MF_DPP_MAX(0x141, 0xf)     // row_half_mirror
+    MF_DPP_MAX(0xb1, 0xf)      // quad_perm [1,0,3,2]
+    MF_DPP_MAX(0x4e, 0xf)      // quad_perm [2,3,0,1]
+    MF_DPP_MAX(0x142, 0xa)     // row_bcast15 into rows 1, 3
+    MF_DPP_MAX(0x143, 0xc)     // row_bcast31 into rows 2, 3
+#undef MF_DPP_MAX
+    return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
 // natural-order DFT-8, forward sign (W_8 = exp(-2 pi i / 8)): 28 packed instructions
@@ -548,16 +614,28 @@ __global__ __launch_bounds__(256, 5) void mfcc512_kernel(const void* __restrict_
             for (int a = 0; a < 8; ++a) x[a] = c32{cur_a[a], cur_b[a]} - c32{prev_a[a], prev_b[a]} * d.preemph;
             // An all-zero frame (digital silence, or a frame that starts past the end of the signal) must come out as
             // exact zeros -- the package substitutes eps for 0 before the log, -36.04 -- but packed with a live frame it
-            // picks up that frame's rounding noise through the split (1e-14 of its power: log ~ -30).  Its power
-            // scale is therefore 0 (uniform: one OR over the lane's samples and a ballot per frame).
-            unsigned ora = 0u, orb = 0u;
+            // picks up that frame's rounding noise through the split (1e-14 of its power: log ~ -30), and a frame that is only
+            // QUIET beside its partner picks up the same noise on top of its own spectrum.  pair_scale: power scale 0 for the
+            // first, the quiet frame at its partner's level for the second (uniform: the two peaks over the wave, wave_max_u32).
+            float ma = 0.f, mb = 0.f;
 #pragma unroll
             for (int a = 0; a < 8; ++a) {
-                ora |= __float_as_uint(x[a].x);
-                orb |= __float_as_uint(x[a].y);
+                ma = fmaxf(ma, fabsf(x[a].x));
+                mb = fmaxf(mb, fabsf(x[a].y));
             }
-            const bool live_a = __ballot((ora & 0x7fffffffu) != 0u) != 0ull, live_b = __ballot((orb & 0x7fffffffu) != 0u) != 0ull;
-            const bool mixed = live_a != live_b;                    // (uniform, rare) an all-zero frame packed with a live one
+            // (the peaks over the wave only for a pair some lane of which suspects: peaks kPairGap binades apart differ by more
+            //  than 2^(kPairGap - 1), and so do, in the lane that holds the larger peak, that lane's own two -- two compares and
+            //  a ballot for every other pair: 1 % of the pairs of white noise suspect, 14 % of a speech-like signal's)
+            constexpr float kSuspect = float(1 << (kPairGap - 1));
+            PairScale ps{1.f, 1.f, 1.f, 1.f, false};
+            if (__ballot(ma > kSuspect * mb || mb > kSuspect * ma) != 0ull) {
+                const unsigned peak_a = wave_max_u32(__float_as_uint(ma)), peak_b = wave_max_u32(__float_as_uint(mb));
+                ps = pair_scale((int)(peak_a >> 23), (int)(peak_b >> 23), peak_a != 0u, peak_b != 0u);
+                if (ps.special) {                                   // (uniform, rare; an all-zero frame: times 1)
+#pragma unroll
+                    for (int a = 0; a < 8; ++a) x[a] = x[a] * c32{ps.sa, ps.sb};
+                }
+            }
             // lane = 8b + c holds x[64a + 8b + c], a = 0..7
             dft8(x);                                                // over a -> k0
             twiddle<1>(x, w1);                                      // W_512^((8b + c) k0)
@@ -593,9 +671,9 @@ __global__ __launch_bounds__(256, 5) void mfcc512_kernel(const void* __restrict_
             // (second pair: into this wave's exchange region -- its last read of the region is in program order before these writes)
             float* pw = pp ? smem + wave * (2 * kEx + kExRow) + kExRow0 : P0 + 2 * wave * kPS;
             float ea = 0.f, eb = 0.f;
-            // (one uniform branch per pair, not one per bin: the mixed form is the rare one)
-            auto power_rows = [&](auto mixed_c) {
-                constexpr bool MIXED = decltype(mixed_c)::value;
+            // (one uniform branch per pair, not one per bin: the form with power scales is the rare one)
+            auto power_rows = [&](auto scaled_c) {
+                constexpr bool SCALED = decltype(scaled_c)::value;
 #pragma unroll
                 for (int k2 = 0; k2 < 4; ++k2) {
                     c32 z;           // Z[512 - k]: lane 0 pairs 64 k2 with 64 (8 - k2)
@@ -604,9 +682,9 @@ __global__ __launch_bounds__(256, 5) void mfcc512_kernel(const void* __restrict_
                     const c32 sa2 = cadd_conj(x[k2], z), sb2 = csub_conj(x[k2], z);   // 2A, 2iB
                     const c32 qa = sa2 * sa2, qb = sb2 * sb2;
                     float pa = qa.x + qa.y, pb = qb.x + qb.y;       // half the power (see kTwoM6)
-                    if constexpr (MIXED) {
-                        pa = live_a ? pa : 0.f;
-                        pb = live_b ? pb : 0.f;
+                    if constexpr (SCALED) {
+                        pa = ps.ka == 0.f ? 0.f : pa * ps.ka;
+                        pb = ps.kb == 0.f ? 0.f : pb * ps.kb;
                     }
                     pw[bin0 + 64 * k2] = pa;
                     pw[kPS + bin0 + 64 * k2] = pb;
@@ -615,11 +693,11 @@ __global__ __launch_bounds__(256, 5) void mfcc512_kernel(const void* __restrict_
                 }
                 if (lane == 0) {     // bin 256 = Z[256] = lane 0's x[4], its own partner: A[256] = Re, B[256] = Im (energies only)
                     const float ta = 4.f * x[4].x * x[4].x, tb = 4.f * x[4].y * x[4].y;
-                    ea += MIXED && !live_a ? 0.f : ta;
-                    eb += MIXED && !live_b ? 0.f : tb;
+                    ea += !SCALED ? ta : ps.ka == 0.f ? 0.f : ta * ps.ka;
+                    eb += !SCALED ? tb : ps.kb == 0.f ? 0.f : tb * ps.kb;
                 }
             };
-            if (mixed) power_rows(std::true_type{});
+            if (ps.special) power_rows(std::true_type{});
             else power_rows(std::false_type{});
             ea = wave_sum(ea);                                     // (vector-ALU cross-lane adds: __shfl_xor is six LDS round trips per value)
             eb = wave_sum(eb);
