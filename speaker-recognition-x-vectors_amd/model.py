@@ -309,10 +309,15 @@ class XVectorModel(nn.Module):
             yield lin.weight
             yield lin.bias
 
+    def _signature(self):
+        """What an engine's packed weights were made from: the parameter tensors (load_state_dict, .to() and in-place edits
+        change data_ptr or bump tensor._version) and every layer's BatchNorm eps (a plain attribute: norm.eps = ...)."""
+        return (tuple((t.data_ptr(), t._version) for t in self._hot_tensors()),
+                tuple(float(layer.norm.eps) if layer.batch_norm else 0.0 for layer in self.time_context_layers))
+
     def _sync_weights(self, eng: _Engine):
-        """(Re)pack parameters into the engine when any of them changed (load_state_dict,
-        .to(), in-place edits bump tensor._version)."""
-        sig = tuple((t.data_ptr(), t._version) for t in self._hot_tensors())
+        """(Re)pack parameters into the engine when its signature changed."""
+        sig = self._signature()
         if sig == eng.signature:
             return
         dev = eng.device

@@ -102,7 +102,7 @@ def test_layers_loaded_on_different_streams_in_any_order(sd42, synth):
     for which, lin in ((hip.SEG6, m.segment_layer6), (hip.SEG7, m.segment_layer7), (hip.OUTPUT, m.output)):
         hip.check(hip.lib.xvec_load_affine(eng.h, which, lin.weight.data_ptr(), lin.bias.data_ptr(), streams[5].cuda_stream))
     torch.cuda.synchronize()
-    eng.signature = tuple((t.data_ptr(), t._version) for t in m._hot_tensors())
+    eng.signature = m._signature()                           # (or the model would re-pack on one stream and hide the test)
     m._engines[(dev.type, dev.index)] = eng
     assert torch.equal(m.extract_x_vec(x), want)
     assert m._engines[(dev.type, dev.index)] is eng          # the hand-loaded engine is the one that ran
