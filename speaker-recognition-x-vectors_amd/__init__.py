@@ -13,7 +13,7 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm", "lda", "LDA", "LdaStats", "EmbeddingTransform",
            "resample", "Resampler", "speed_perturb", "identify", "SpeakerModels", "SpeakerIdentifier", "enroll",
            "open_set_scores", "identification_rate", "diarize", "Diarizer", "Diarization", "Clustering", "cluster", "turns",
-           "write_rttm"]
+           "write_rttm", "vad", "VadCmvn", "energy_vad", "sliding_cmvn", "select_voiced", "speech_runs", "run_windows"]
 
 
 def __getattr__(name):
@@ -48,6 +48,9 @@ def __getattr__(name):
     if name in ("Diarizer", "Diarization", "Clustering", "cluster", "turns", "write_rttm"):
         import importlib
         return getattr(importlib.import_module(".diarize", __name__), name)
+    if name in ("VadCmvn", "energy_vad", "sliding_cmvn", "select_voiced", "speech_runs", "run_windows"):
+        import importlib
+        return getattr(importlib.import_module(".vad", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -55,7 +58,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize"):
+                "diarize", "vad"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

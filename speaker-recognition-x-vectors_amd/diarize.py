@@ -12,6 +12,8 @@ tests/test_diarize.py holds against scipy.cluster.hierarchy.linkage.  The score 
     d = Diarizer(model, scorer, transform, win=150, hop=75, threshold=0.0)
     res = d.diarize(x, lengths)                             # Diarization: .windows, .labels, .n_clusters, .turns (host)
     write_rttm(res.turns, names, "out.rttm")
+    d = Diarizer(model, scorer, transform, frontend=vad.VadCmvn(), max_gap=10)      # the recipe's front end: sliding CMVN, and
+                                                                                    # windows inside the runs of speech only
 
 Largest score first, equal scores by the lowest pair of cluster indices, NaN never; clusters are numbered in the order of
 their first window.  There is no CPU path.
@@ -148,12 +150,14 @@ class Diarization(NamedTuple):
 class Diarizer:
     """extract_windows -> transform -> score -> cluster on one HIP device.  `model`: an XVectorModel on the device; `scorer`:
     a `PldaScorer` or the string "cosine"; `transform`: an optional `EmbeddingTransform`; `win` / `hop` / `min_tail`: the
-    sliding windows in frames (the recipe's 1.5 s every 0.75 s).  Recordings are grouped into calls whose windows total at most
+    sliding windows in frames (the recipe's 1.5 s every 0.75 s); `frontend`: an optional `vad.VadCmvn` -- the recordings are
+    then normalised and windowed inside their runs of speech only (`max_gap`: the silence in frames a run bridges), as the
+    recipe does, and the turns stay in the recordings' own frames.  Recordings are grouped into calls whose windows total at most
     `max_score_rows`: one call scores all its windows against each other (the scorer has no launch for the diagonal blocks
     alone), so the bound caps the cells computed between different recordings."""
 
     def __init__(self, model, scorer, transform=None, win=150, hop=75, threshold=None, max_speakers=None, min_tail=None,
-                 max_score_rows=8192, device="cuda:0"):
+                 max_score_rows=8192, device="cuda:0", frontend=None, max_gap=0):
         self.device = require_device(device, "diarization")
         if isinstance(scorer, str):
             if scorer != "cosine":
@@ -167,6 +171,11 @@ class Diarizer:
         self.model, self.scorer, self.transform = model, scorer, transform
         self.win, self.hop, self.min_tail = int(win), int(hop), min_tail
         self.threshold, self.max_speakers, self.max_score_rows = threshold, max_speakers, int(max_score_rows)
+        if frontend is not None and not callable(getattr(frontend, "with_select", None)):
+            raise TypeError("Diarizer: frontend must be a vad.VadCmvn")
+        if int(max_gap) < 0:
+            raise ValueError(f"Diarizer: max_gap = {max_gap} must not be negative")
+        self.frontend, self.max_gap = frontend, int(max_gap)
         self._ws = None
 
     def _scores(self, v) -> torch.Tensor:
@@ -174,6 +183,20 @@ class Diarizer:
             from .scoring import cosine_scores
             return cosine_scores(v, device=self.device)
         return self.scorer.score(v)
+
+    def _speech_windows(self, x, lengths):
+        """extract_windows behind the front end: the recordings normalised where they lie (nothing selected, so a frame keeps
+        its index), the windows inside the runs of speech -- gaps of at most max_gap frames closed, runs too short for a
+        window dropped.  Without a VAD in the front end the windows cover the recordings."""
+        from .vad import run_windows, speech_runs
+        p = self.frontend.with_select(False)(x, lengths)
+        if isinstance(p, torch.Tensor):
+            return self.model.extract_windows(p, self.win, self.hop, lengths=lengths, min_tail=self.min_tail)
+        shortest = self.win if self.min_tail is None else min(self.win, int(self.min_tail))
+        windows = run_windows(speech_runs(p.mask, p.lengths, self.max_gap, shortest), self.win, self.hop, self.min_tail)
+        if not len(windows):
+            raise ValueError(f"Diarizer: no run of speech holds a window of {self.win} frames (min_tail={self.min_tail})")
+        return self.model.extract_segments(p.feats, windows, lengths=p.lengths), windows
 
     def calls(self, rec_start):
         """[(first recording, one past the last)] of the scoring calls: consecutive recordings while their windows total at
@@ -191,7 +214,10 @@ class Diarizer:
         for all or one per recording of the batch (0 = by threshold); without it the Diarizer's threshold decides."""
         if self.threshold is None and n_speakers is None:
             raise ValueError("Diarizer: give a threshold at construction or n_speakers here")
-        vecs, windows = self.model.extract_windows(x, self.win, self.hop, lengths=lengths, min_tail=self.min_tail)
+        if self.frontend is None:
+            vecs, windows = self.model.extract_windows(x, self.win, self.hop, lengths=lengths, min_tail=self.min_tail)
+        else:
+            vecs, windows = self._speech_windows(x, lengths)
         if self.transform is not None:
             vecs = self.transform.apply(vecs)
         vecs = dev_f64(vecs, self.device)

@@ -70,6 +70,15 @@ class Cfg(C.Structure):
                 ("x_vector_size", C.c_int32), ("batch_norm", C.c_int32), ("device", C.c_int32)]
 
 
+class VadOptions(C.Structure):                                  # xvec_vad_options
+    _fields_ = [("energy_threshold", C.c_double), ("energy_mean_scale", C.c_double), ("proportion_threshold", C.c_double),
+                ("frames_context", C.c_int32), ("energy_col", C.c_int32)]
+
+
+class CmvnOptions(C.Structure):                                 # xvec_cmvn_options
+    _fields_ = [("cmn_window", C.c_int32), ("min_window", C.c_int32), ("center", C.c_int32), ("norm_vars", C.c_int32)]
+
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         f"{LIB_PATH} is missing: build the HIP library first "
@@ -178,6 +187,14 @@ _SIGS = {
     "xvec_resample_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "xvec_resample": (C.c_int, [_vp, _i32, _i64, _i32, _i64, _vp, _i32, C.POINTER(C.c_double), _i32, _vp, _i64, _i32, _i32, _vp,
                                 _i32, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
+    # include/xvec_vad.h
+    "xvec_vad_last_error": (C.c_char_p, []),
+    "xvec_vad_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "xvec_vad_energy": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, C.POINTER(VadOptions), _vp, _i64, _vp, _vp, _vp]),
+    "xvec_cmvn_sliding": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, C.POINTER(CmvnOptions), _vp, _i64, _vp, _i64, _i64,
+                                    _vp, _vp, C.c_size_t, _vp]),
+    "xvec_vad_cmvn": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, C.POINTER(VadOptions), C.POINTER(CmvnOptions), _i32, _vp,
+                                _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
     # include/xvec_train.h
     "xvec_train_last_error": (C.c_char_p, []),
     "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),

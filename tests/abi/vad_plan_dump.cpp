@@ -1,0 +1,76 @@
+// Dumps csrc/vad_plan.h for tests/test_vad.py (host compiler only).  One request per line of standard input:
+//   window <L> <cmn_window> <min_window> <center>  -> window <lo_0> <hi_0> <lo_1> <hi_1> ...        every frame t of L
+//   span <cmn_window> <min_window> <center>        -> span <frames>                                  (span off: no normalisation)
+//   tile <C> <span>                                -> tile <frames> <channels> <rows> <lds bytes> <run> | refused
+//   grid <B> <T> <C> <span>                        -> grid <blocks>
+//   layout <B> <T>                                 -> layout <prefix> <count> <total>                byte offsets
+//   shape <B> <T> <C> <row stride> <utt stride>    -> ok | refused <message>                         check_shape
+//   maskstride <stride> <T>                        -> ok | refused <message>
+//   vad <thr> <scale> <prop> <ctx> <col> <C>       -> ok | refused <message>                         check_vad (vad null: null)
+//   cmvn <cmn_window> <min_window>                 -> ok | refused <message>                         check_cmvn
+#include <cstdio>
+#include <cstdlib>
+#include <iostream>
+#include <sstream>
+#include <string>
+#include <vector>
+
+#include "vad_plan.h"
+
+int main() {
+    using namespace xvec::vad_plan;
+    std::string line;
+    while (std::getline(std::cin, line)) {
+        std::istringstream in(line);
+        std::string what;
+        if (!(in >> what)) return 2;
+        std::vector<std::string> a;
+        for (std::string x; in >> x;) a.push_back(x);
+        auto I = [&](size_t k) { return std::strtoll(a.at(k).c_str(), nullptr, 10); };
+        auto D = [&](size_t k) { return std::strtod(a.at(k).c_str(), nullptr); };
+        char msg[256] = "";
+        auto verdict = [&](int bad) {
+            if (bad) std::printf("refused %s\n", msg); else std::printf("ok\n");
+        };
+        if (what == "window" && a.size() == 4) {
+            std::printf("window");
+            for (int t = 0; t < (int)I(0); ++t) {
+                int lo, hi;
+                window(t, (int)I(0), (int)I(1), (int)I(2), (int)I(3), &lo, &hi);
+                std::printf(" %d %d", lo, hi);
+            }
+            std::printf("\n");
+        } else if (what == "span" && a.size() == 1 && a[0] == "off") {
+            std::printf("span %d\n", span(nullptr));
+        } else if (what == "span" && a.size() == 3) {
+            const xvec_cmvn_options o{(int32_t)I(0), (int32_t)I(1), (int32_t)I(2), 0};
+            std::printf("span %d\n", span(&o));
+        } else if (what == "tile" && a.size() == 2) {
+            Tile t{};
+            if (plan_tile((int32_t)I(0), (int32_t)I(1), &t)) std::printf("refused\n");
+            else std::printf("tile %d %d %d %zu %d\n", t.frames, t.channels, t.rows, t.lds_bytes, t.run);
+        } else if (what == "grid" && a.size() == 4) {
+            Tile t{};
+            if (plan_tile((int32_t)I(2), (int32_t)I(3), &t)) return 3;
+            std::printf("grid %lld\n", (long long)grid_blocks((int32_t)I(0), (int32_t)I(1), (int32_t)I(2), t));
+        } else if (what == "layout" && a.size() == 2) {
+            const Layout l = make_layout((int32_t)I(0), (int32_t)I(1));
+            std::printf("layout %zu %zu %zu\n", l.prefix, l.count, l.total);
+        } else if (what == "shape" && a.size() == 5) {
+            verdict(check_shape((int32_t)I(0), (int32_t)I(1), (int32_t)I(2), I(3), I(4), "x:", msg, sizeof(msg)));
+        } else if (what == "maskstride" && a.size() == 2) {
+            verdict(check_mask_stride(I(0), (int32_t)I(1), msg, sizeof(msg)));
+        } else if (what == "vad" && a.size() == 1 && a[0] == "null") {
+            verdict(check_vad(nullptr, 1, msg, sizeof(msg)));
+        } else if (what == "vad" && a.size() == 6) {
+            const xvec_vad_options o{D(0), D(1), D(2), (int32_t)I(3), (int32_t)I(4)};
+            verdict(check_vad(&o, (int32_t)I(5), msg, sizeof(msg)));
+        } else if (what == "cmvn" && a.size() == 2) {
+            const xvec_cmvn_options o{(int32_t)I(0), (int32_t)I(1), 0, 0};
+            verdict(check_cmvn(&o, msg, sizeof(msg)));
+        } else {
+            return 2;
+        }
+    }
+    return 0;
+}
