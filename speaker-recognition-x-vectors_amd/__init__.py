@@ -13,7 +13,8 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "ScoreNormalizer", "CohortStats", "cohort_stats", "apply_norm", "lda", "LDA", "LdaStats", "EmbeddingTransform",
            "resample", "Resampler", "speed_perturb", "identify", "SpeakerModels", "SpeakerIdentifier", "enroll",
            "open_set_scores", "identification_rate", "diarize", "Diarizer", "Diarization", "Clustering", "cluster", "turns",
-           "write_rttm", "vad", "VadCmvn", "energy_vad", "sliding_cmvn", "select_voiced", "speech_runs", "run_windows"]
+           "write_rttm", "vad", "VadCmvn", "energy_vad", "sliding_cmvn", "select_voiced", "speech_runs", "run_windows", "visualize",
+           "Tsne", "tsne_map", "tsne_affinities", "pca_map", "scatter_maps"]
 
 
 def __getattr__(name):
@@ -51,6 +52,9 @@ def __getattr__(name):
     if name in ("VadCmvn", "energy_vad", "sliding_cmvn", "select_voiced", "speech_runs", "run_windows"):
         import importlib
         return getattr(importlib.import_module(".vad", __name__), name)
+    if name in ("Tsne", "tsne_map", "tsne_affinities", "pca_map", "scatter_maps"):
+        import importlib
+        return getattr(importlib.import_module(".visualize", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -58,7 +62,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize", "vad"):
+                "diarize", "vad", "visualize"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -35,6 +35,7 @@ LDA_X_F32, LDA_X_F64 = 0, 1                                     # XVEC_LDA_X_*
 IDENT_X_F32, IDENT_X_F64 = 0, 1                                 # XVEC_IDENT_X_*
 EMBED_MAX_DIM, EMBED_ROW_GROUP = 65536, 64                      # XVEC_EMBED_*
 AUG_POOL_F32, AUG_POOL_I16 = 0, 1                               # XVEC_AUG_POOL_*
+TSNE_X_F32, TSNE_X_F64 = 0, 1                                   # XVEC_TSNE_X_*
 MODE_LOGITS, MODE_POOLED, MODE_XVEC6, MODE_XVEC7 = 0, 5, 6, 7
 SEG6, SEG7, OUTPUT = 6, 7, 8
 KERNEL_NAMES = {0: None, 1: "tile128", 2: "pp", 3: "first"}      # XVEC_KERNEL_*
@@ -195,6 +196,14 @@ _SIGS = {
                                     _vp, _vp, C.c_size_t, _vp]),
     "xvec_vad_cmvn": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i64, _vp, C.POINTER(VadOptions), C.POINTER(CmvnOptions), _i32, _vp,
                                 _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, C.c_size_t, _vp]),
+    # include/xvec_tsne.h
+    "xvec_tsne_last_error": (C.c_char_p, []),
+    "xvec_tsne_workspace_bytes": (C.c_size_t, [_i32, _i32]),
+    "xvec_tsne_plan": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "xvec_tsne_sqdist": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp, C.c_size_t, _vp]),
+    "xvec_tsne_affinities": (C.c_int, [_vp, _i64, _i32, C.c_double, _vp, _i64, _vp, _vp, C.c_size_t, _vp]),
+    "xvec_tsne_steps": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, C.c_double, C.c_double, C.c_double,
+                                  C.c_double, _vp, _vp, _vp, C.c_size_t, _vp]),
     # include/xvec_train.h
     "xvec_train_last_error": (C.c_char_p, []),
     "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
