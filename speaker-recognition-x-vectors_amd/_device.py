@@ -1,5 +1,6 @@
-"""Host plumbing shared by the modules that call the library (model, frontend, scoring, plda, evaluate): error
-checks, the raw stream pointer, the device-only guard, host data onto the device, byte workspaces."""
+"""Host plumbing shared by every module that calls the library (model, frontend, scoring, plda, evaluate, snorm, identify,
+diarize, lda, augment, resample, vad, visualize, train): error checks, the raw stream pointer, the pointer of an optional
+tensor, the device-only guard, host data onto the device, the check of a device score matrix, byte workspaces."""
 from __future__ import annotations
 
 import numpy as np
@@ -22,6 +23,11 @@ def stream(device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def ptr(t):
+    """The device pointer of `t`; None (a null pointer) for an argument that was left out."""
+    return None if t is None else t.data_ptr()
+
+
 def require_device(device, what) -> torch.device:
     device = torch.device(device)
     if device.type != "cuda":
@@ -40,8 +46,30 @@ def dev_f64(a, device, keep_f32=False) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).to(device).contiguous()
 
 
+def score_matrix(scores, what, shape="[n_rows, n_cols]", square=False) -> torch.Tensor:
+    """`scores` as the library reads a score matrix: a float64 device tensor `shape`, not empty (`square`: and square), with
+    unit column stride (copied only where it has another)."""
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise RuntimeError(f"{what} runs on a HIP device only (no CPU path): the scores must be a device tensor")
+    if scores.dim() != 2 or scores.dtype != torch.float64:
+        raise ValueError(f"{what}: expected a float64 {shape} score matrix")
+    if square and (scores.shape[0] < 1 or scores.shape[0] != scores.shape[1]):
+        raise ValueError(f"{what}: the score matrix must be square and not empty, got {tuple(scores.shape)}")
+    if scores.shape[0] < 1 or scores.shape[1] < 1:
+        raise ValueError(f"{what}: empty score matrix")
+    return scores if scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1] else scores.contiguous()
+
+
 def byte_workspace(need, device, cached=None) -> torch.Tensor:
     """`cached` if it holds `need` bytes, else a new uint8 tensor (never an empty one: its pointer would be null)."""
     if cached is not None and cached.numel() >= need:
         return cached
     return torch.empty(max(1, int(need)), dtype=torch.uint8, device=device)
+
+
+def sized_workspace(need, refusal, device, cached=None) -> torch.Tensor:
+    """byte_workspace for the `need` bytes a *_workspace_bytes query answered; 0 is the query's refusal of its arguments and
+    raises the exception that `refusal()` returns."""
+    if need == 0:
+        raise refusal()
+    return byte_workspace(int(need), device, cached)

@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, require_device, stream as _stream
+from ._device import checker, require_device, sized_workspace, stream as _stream
 
 __all__ = ["WaveAugmenter", "AugmentPlan", "KINDS"]
 
@@ -165,9 +165,8 @@ class WaveAugmenter:
         return waves.detach().to(device=self.device, dtype=torch.float32, copy=True).contiguous()
 
     def _workspace(self, need: int) -> torch.Tensor:
-        if need == 0:
-            raise ValueError("waveform augmentation: batch or length outside the supported range")
-        self._ws = byte_workspace(need, self.device, self._ws)
+        refusal = lambda: ValueError("waveform augmentation: batch or length outside the supported range")
+        self._ws = sized_workspace(need, refusal, self.device, self._ws)
         return self._ws
 
     def status(self):

@@ -332,28 +332,27 @@ extern "C" {
 const char* xvec_diar_last_error(void) { return g_derr.c_str(); }
 
 size_t xvec_ahc_workspace_bytes(const int64_t* rec_start_host, int32_t n_rec) {
-    char msg[256];
-    if (diar_plan::check_rec_start(rec_start_host, n_rec, msg, sizeof(msg))) return 0;
+    Refusal why;
+    if (diar_plan::check_rec_start(rec_start_host, n_rec, why)) return 0;
     return diar_plan::make_layout(rec_start_host, n_rec).total;
 }
 
 int xvec_ahc_cluster(const double* S, int64_t ld, const int64_t* rec_start_host, int32_t n_rec, double threshold,
                      int32_t max_clusters, const int32_t* want_host, int32_t* labels, int32_t* n_clusters, int32_t* merge_i,
                      int32_t* merge_j, double* merge_score, void* workspace, size_t workspace_bytes, xvec_stream stream) {
-    char msg[256];
-    if (diar_plan::check_rec_start(rec_start_host, n_rec, msg, sizeof(msg))) return g_derr.fail(XVEC_ERR_ARG, "%s", msg);
+    Refusal why;
+    if (diar_plan::check_rec_start(rec_start_host, n_rec, why)) return g_derr.refused(XVEC_ERR_ARG, why);
     const int64_t N = rec_start_host[n_rec];
     if (threshold != threshold) return g_derr.fail(XVEC_ERR_ARG, "threshold is NaN (+inf never merges by score, -inf always)");
     if (max_clusters < 0) return g_derr.fail(XVEC_ERR_ARG, "max_clusters = %d must not be negative (0 = no limit)", max_clusters);
-    if (diar_plan::check_want(want_host, n_rec, msg, sizeof(msg))) return g_derr.fail(XVEC_ERR_ARG, "%s", msg);
+    if (diar_plan::check_want(want_host, n_rec, why)) return g_derr.refused(XVEC_ERR_ARG, why);
     if (ld < N) return g_derr.fail(XVEC_ERR_ARG, "ld = %lld is smaller than the %lld segments", (long long)ld, (long long)N);
     if (!S || !labels || !n_clusters) return g_derr.fail(XVEC_ERR_ARG, "null pointer: S / labels / n_clusters");
     if (!(merge_i && merge_j && merge_score) && (merge_i || merge_j || merge_score))
         return g_derr.fail(XVEC_ERR_ARG, "merge_i, merge_j and merge_score: all three or none");
-    if (!workspace) return g_derr.fail(XVEC_ERR_ARG, "null pointer: workspace");
     const diar_plan::Layout l = diar_plan::make_layout(rec_start_host, n_rec);
     int rc;
-    if ((rc = workspace_ok(workspace_bytes, l.total, g_derr))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_derr))) return rc;
 
     char* ws = static_cast<char*>(workspace);
     AhcArgs g{};

@@ -5,9 +5,9 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/xvec_diar.h"
+#include "plan_support.h"
 
 #if defined(__HIPCC__)
 #define XVEC_DIAR_FN __host__ __device__ __forceinline__
@@ -18,39 +18,34 @@
 namespace xvec {
 namespace diar_plan {
 
-constexpr size_t kAlign = 256;
-
-inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
-
 // Doubles the working matrix of a recording of n segments takes: n rows of n cells, dense (row stride n), rounded up to a whole
 // number of 256-byte lines so that the next matrix starts on one.
 XVEC_DIAR_FN int64_t mat_elems(int64_t n) { return (n * n + 31) & ~(int64_t)31; }
 
 // rec_start [n_rec + 1]: from 0, every recording with 1 .. XVEC_DIAR_MAX_SEGMENTS segments, fewer than 2^31 in all.
-// 0, or 1 with the reason in msg.
-inline int check_rec_start(const int64_t* rs, int32_t n_rec, char* msg, size_t len) {
-    if (n_rec < 1) return std::snprintf(msg, len, "n_rec = %d: need at least one recording", n_rec), 1;
-    if (!rs) return std::snprintf(msg, len, "null pointer: rec_start"), 1;
-    if (rs[0] != 0) return std::snprintf(msg, len, "rec_start must begin at 0 (got %lld)", (long long)rs[0]), 1;
+// 0, or 1 with the reason in why.
+inline int check_rec_start(const int64_t* rs, int32_t n_rec, Refusal& why) {
+    if (n_rec < 1) return why.refuse("n_rec = %d: need at least one recording", n_rec);
+    if (!rs) return why.refuse("null pointer: rec_start");
+    if (rs[0] != 0) return why.refuse("rec_start must begin at 0 (got %lld)", (long long)rs[0]);
     for (int32_t r = 0; r < n_rec; ++r) {
         const int64_t n = rs[r + 1] - rs[r];
         if (n < 1)
-            return std::snprintf(msg, len, "recording %d is empty or rec_start decreases: every recording needs a segment", r), 1;
+            return why.refuse("recording %d is empty or rec_start decreases: every recording needs a segment", r);
         if (n > XVEC_DIAR_MAX_SEGMENTS)
-            return std::snprintf(msg, len, "recording %d has %lld segments, more than XVEC_DIAR_MAX_SEGMENTS = %d", r, (long long)n,
-                                 XVEC_DIAR_MAX_SEGMENTS), 1;
+            return why.refuse("recording %d has %lld segments, more than XVEC_DIAR_MAX_SEGMENTS = %d", r, (long long)n,
+                              XVEC_DIAR_MAX_SEGMENTS);
         if (rs[r + 1] > 0x7fffffff)
-            return std::snprintf(msg, len, "%lld segments up to recording %d: the total must stay below 2^31", (long long)rs[r + 1],
-                                 r), 1;
+            return why.refuse("%lld segments up to recording %d: the total must stay below 2^31", (long long)rs[r + 1], r);
     }
     return 0;
 }
 
 // want [n_rec] (may be null: no recording asks for a count): no negative entry.
-inline int check_want(const int32_t* want, int32_t n_rec, char* msg, size_t len) {
+inline int check_want(const int32_t* want, int32_t n_rec, Refusal& why) {
     if (!want) return 0;
     for (int32_t r = 0; r < n_rec; ++r)
-        if (want[r] < 0) return std::snprintf(msg, len, "want[%d] = %d must not be negative (0 = stop by threshold)", r, want[r]), 1;
+        if (want[r] < 0) return why.refuse("want[%d] = %d must not be negative (0 = stop by threshold)", r, want[r]);
     return 0;
 }
 
@@ -68,20 +63,14 @@ struct Layout {
 inline Layout make_layout(const int64_t* rs, int32_t n_rec) {
     Layout l{};
     const size_t N = (size_t)rs[n_rec];
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += align_up(bytes);
-        return at;
-    };
-    l.rec_start = take(((size_t)n_rec + 1) * sizeof(int64_t));
-    l.want = take((size_t)n_rec * sizeof(int32_t));
-    l.mat_off = take((size_t)n_rec * sizeof(int64_t));
-    l.best_v = take(N * sizeof(double));
-    l.best_i = take(N * sizeof(int32_t));
-    l.mats = off;
-    for (int32_t r = 0; r < n_rec; ++r) off += (size_t)mat_elems(rs[r + 1] - rs[r]) * sizeof(double);
-    l.total = off;
+    Carver c;
+    l.rec_start = c.take_bytes(((size_t)n_rec + 1) * sizeof(int64_t));
+    l.want = c.take_bytes((size_t)n_rec * sizeof(int32_t));
+    l.mat_off = c.take_bytes((size_t)n_rec * sizeof(int64_t));
+    l.best_v = c.take_bytes(N * sizeof(double));
+    l.best_i = c.take_bytes(N * sizeof(int32_t));
+    l.mats = l.total = c.total();
+    for (int32_t r = 0; r < n_rec; ++r) l.total += (size_t)mat_elems(rs[r + 1] - rs[r]) * sizeof(double);
     return l;
 }
 

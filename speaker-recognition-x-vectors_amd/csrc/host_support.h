@@ -1,12 +1,16 @@
-// Host-side plumbing of the C-ABI translation units (xvec_api, mfcc, score, plda_train, eval, augment): the error text behind a
-// *_last_error() export, workspace carving, the CU count.  Host code only: nothing here is called from a kernel.
+// Host-side plumbing of every C-ABI translation unit (xvec_api, mfcc, score, plda_train, eval, snorm, ident, diar, lda,
+// augment, resample, vad, tsne, tdnn_train*, train_tail*): the error text behind a *_last_error() export, the workspace check,
+// the CU count, and through plan_support.h the alignment, the workspace carver and a plan header's refusal.  Host code only:
+// nothing here is called from a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
 #include <stddef.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include "../../include/xvec_hip.h"
+#include "plan_support.h"
 
 namespace xvec {
 
@@ -21,6 +25,10 @@ struct ErrorChannel {
         va_end(ap);
         return code;
     }
+    // a plan header's refusal, as "<call>: <reason>" where the unit's messages name the call
+    int refused(int code, const Refusal& why, const char* call = nullptr) {
+        return call ? fail(code, "%s: %s", call, why.text) : fail(code, "%s", why.text);
+    }
     int launch_ok(const char* what) {      // right after a kernel launch
         const hipError_t e = hipGetLastError();
         return e == hipSuccess ? XVEC_OK : fail(XVEC_ERR_HIP, "%s launch failed: %s", what, hipGetErrorString(e));
@@ -31,26 +39,28 @@ struct ErrorChannel {
 // The channel behind xvec_train_last_error(): defined in tdnn_train.hip, shared with train_tail.hip (one header, one channel).
 ErrorChannel& train_error_channel();
 
-inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 inline int workspace_ok(size_t have, size_t need, ErrorChannel& err) {
     return have >= need ? XVEC_OK : err.fail(XVEC_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", have, need);
 }
 
-// Hands out consecutive 256-byte aligned buffers of one workspace.  A plan function is written once over a Carver: called
-// with a null base it only sizes the workspace (every pointer comes back null), with the real base it names the buffers.
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(void* ws) : base(static_cast<char*>(ws)) {}
-    template <typename T>
-    T* take(size_t count) {
-        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += align256(count * sizeof(T));
-        return p;
-    }
-    size_t total() const { return off; }
-};
+// "Workspace given, aligned and large enough".  What the entry points answer is part of the ABI (the headers' error
+// conventions; tests/test_workspace_refusals.py holds every answer), so the differences between the units are parameters:
+//   - a null workspace is XVEC_ERR_ARG "null pointer: workspace";
+//   - t-SNE alone asks for alignment (xvec_tsne.h: 8-byte aligned device pointers; align = 8, 0 = not tested): XVEC_ERR_ARG
+//     "workspace is not 8-byte aligned", and alone names the call in front of these two texts (call; null = no prefix);
+//   - a workspace below `need` bytes is "workspace too small: <have> < <need> bytes", never prefixed, with XVEC_ERR_WORKSPACE;
+//     the training units (xvec_train.h) alone answer XVEC_ERR_ARG for it (small_code).
+// The units whose single "null pointer" test names the workspace among other arguments (score, plda_train, eval, lda, augment,
+// xvec_model_mean) and xvec_resample, which checks its ratios between the two tests, call workspace_ok alone.
+inline int workspace_arg_ok(const void* ws, size_t have, size_t need, ErrorChannel& err, int small_code = XVEC_ERR_WORKSPACE,
+                            const char* call = nullptr, size_t align = 0) {
+    const char* sep = call ? ": " : "";
+    if (!call) call = "";
+    if (!ws) return err.fail(XVEC_ERR_ARG, "%s%snull pointer: workspace", call, sep);
+    if (align && reinterpret_cast<uintptr_t>(ws) % align != 0)
+        return err.fail(XVEC_ERR_ARG, "%s%sworkspace is not %zu-byte aligned", call, sep, align);
+    return have >= need ? XVEC_OK : err.fail(small_code, "workspace too small: %zu < %zu bytes", have, need);
+}
 
 // Compute units of the current device (256 where the query fails), asked once per device.
 inline int device_cu_count() {

@@ -478,10 +478,9 @@ int xvec_open_set_scores(const double* S, int64_t ld, int64_t N, int64_t T, doub
     if (out == S && ld_out != ld)
         return g_ierr.fail(XVEC_ERR_ARG, "in place (out == S) needs ld_out == ld (got %lld and %lld)", (long long)ld_out,
                            (long long)ld);
-    if (!workspace) return g_ierr.fail(XVEC_ERR_ARG, "null pointer: workspace");
     const OpenSetPlan p = make_open_set_plan(workspace, N, T);
     int rc;
-    if ((rc = workspace_ok(workspace_bytes, p.total, g_ierr))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total, g_ierr))) return rc;
     ColStatsArgs cs{};
     cs.S = S;
     cs.ld = ld;
@@ -531,10 +530,9 @@ int xvec_identify_topk(const double* S, int64_t ld, int64_t N, int64_t T, int32_
     if (k < 1 || k > kMaxK) return g_ierr.fail(XVEC_ERR_ARG, "k = %d must lie in 1 .. %d", k, kMaxK);
     if (ld < T) return g_ierr.fail(XVEC_ERR_ARG, "ld = %lld is smaller than T = %lld", (long long)ld, (long long)T);
     if (!S || !idx || !val) return g_ierr.fail(XVEC_ERR_ARG, "null pointer: S / idx / val");
-    if (!workspace) return g_ierr.fail(XVEC_ERR_ARG, "null pointer: workspace");
     const TopkPlan p = make_topk_plan(workspace, N, T, k);
     int rc;
-    if ((rc = workspace_ok(workspace_bytes, p.total, g_ierr))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total, g_ierr))) return rc;
     TopkArgs g{};
     g.S = S;
     g.ld = ld;

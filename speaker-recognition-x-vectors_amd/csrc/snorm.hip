@@ -303,9 +303,8 @@ int xvec_snorm_row_stats(const double* scores, int64_t ld, int64_t n, int64_t C,
     if (top_k < 0) return g_nerr.fail(XVEC_ERR_ARG, "top_k = %lld must not be negative (0 = every valid cell)", (long long)top_k);
     if (!scores) return g_nerr.fail(XVEC_ERR_ARG, "null pointer: scores");
     if (!mean || !std || !kth || !n_used) return g_nerr.fail(XVEC_ERR_ARG, "null pointer: mean / std / kth / n_used");
-    if (!workspace) return g_nerr.fail(XVEC_ERR_ARG, "null pointer: workspace");
     int rc;
-    if ((rc = workspace_ok(workspace_bytes, record_bytes(n), g_nerr))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, record_bytes(n), g_nerr))) return rc;
     RowStatsArgs g{};
     g.scores = scores;
     g.ld = ld;

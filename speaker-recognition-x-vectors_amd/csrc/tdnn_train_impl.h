@@ -775,11 +775,6 @@ inline Plan make_plan(void* ws, const Shape& s) {
     return p;
 }
 
-inline int workspace_arg_ok(void* ws, size_t have, size_t need) {
-    if (!ws) return terr().fail(XVEC_ERR_ARG, "null pointer: workspace");
-    return have >= need ? XVEC_OK : terr().fail(XVEC_ERR_ARG, "workspace too small: %zu < %zu bytes", have, need);
-}
-
 inline bool aligned16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
 
 template <int OP, bool RAGGED>
@@ -829,7 +824,7 @@ int train_forward(const float* x, int32_t B, int32_t T, int32_t Cin, const float
     int rc;
     if ((rc = make_shape(B, T, Cin, Cout, context_host, n_ctx, s))) return rc;
     const Plan p = make_plan(workspace, s);
-    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total, terr(), XVEC_ERR_ARG))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Lengths<RAGGED> L = make_lengths<RAGGED>(s, lengths_dev);
 
@@ -868,7 +863,7 @@ int train_backward(const float* dy, const float* x, const float* z, int32_t B, i
     int rc;
     if ((rc = make_shape(B, T, Cin, Cout, context_host, n_ctx, s))) return rc;
     const Plan p = make_plan(workspace, s);
-    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total, terr(), XVEC_ERR_ARG))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Lengths<RAGGED> L = make_lengths<RAGGED>(s, lengths_dev);
     const dim3 cols((Cout + 63) / 64);

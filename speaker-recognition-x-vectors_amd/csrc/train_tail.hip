@@ -403,11 +403,6 @@ Plan make_plan(void* ws, const Shape& s) {
     return p;
 }
 
-int workspace_arg_ok(void* ws, size_t have, size_t need) {
-    if (!ws) return terr().fail(XVEC_ERR_ARG, "null pointer: workspace");
-    return have >= need ? XVEC_OK : terr().fail(XVEC_ERR_ARG, "workspace too small: %zu < %zu bytes", have, need);
-}
-
 // out = f(A B): the sliced product into the slab, then the epilogue
 template <bool A_KC, bool B_KC>
 int product(const Product& q, const float* a, const float* b, float* slab, int mode, const float* bias, const float* act,
@@ -464,7 +459,7 @@ int train_tail_forward(const float* y5, int32_t B, int32_t Tp, int32_t C, const 
     int rc;
     if ((rc = make_shape(B, Tp, C, H, K, s))) return rc;
     const Plan p = make_plan(workspace, s);
-    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total, terr(), XVEC_ERR_ARG))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
 
     if ((rc = pool(y5, B, Tp, C, lengths_dev, pooled, st))) return rc;
@@ -492,7 +487,7 @@ int train_tail_backward(const float* dloss, const float* y5, int32_t B, int32_t 
     int rc;
     if ((rc = make_shape(B, Tp, C, H, K, s))) return rc;
     const Plan p = make_plan(workspace, s);
-    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, p.total, terr(), XVEC_ERR_ARG))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
 
     tail_dlogits_kernel<<<B, 256, 0, st>>>(logits, K, B, reinterpret_cast<const long long*>(labels), dloss, p.dlogits);

@@ -393,21 +393,9 @@ __global__ __launch_bounds__(kThreads) void tsne_finish_kernel(const StepArgs g,
 
 thread_local ErrorChannel g_terr;
 
-#define TSNE_REFUSE(check_call)                                             \
-    {                                                                       \
-        char msg_[400];                                                     \
-        if (check_call) return g_terr.fail(XVEC_ERR_ARG, "%s: %s", what, msg_); \
-    }
-
 template <typename T>
 T* part(void* ws, size_t off) {
     return reinterpret_cast<T*>(static_cast<char*>(ws) + off);
-}
-
-int check_workspace(const void* ws, size_t have, size_t need, const char* what) {
-    if (!ws) return g_terr.fail(XVEC_ERR_ARG, "%s: null pointer: workspace", what);
-    if (reinterpret_cast<uintptr_t>(ws) % 8 != 0) return g_terr.fail(XVEC_ERR_ARG, "%s: workspace is not 8-byte aligned", what);
-    return workspace_ok(have, need, g_terr);
 }
 
 }  // namespace
@@ -427,7 +415,8 @@ size_t xvec_tsne_workspace_bytes(int32_t n, int32_t d) {
 
 int xvec_tsne_plan(int32_t n, int32_t cus, int32_t* rows_per_block, int32_t* slices, int32_t* slice_cols) {
     const char* what = "xvec_tsne_plan";
-    TSNE_REFUSE(tp::check_points(n, msg_, sizeof(msg_)));
+    Refusal why;
+    if (tp::check_points(n, why)) return g_terr.refused(XVEC_ERR_ARG, why, what);
     if (!rows_per_block || !slices || !slice_cols) return g_terr.fail(XVEC_ERR_ARG, "%s: null pointer", what);
     const tp::Plan p = tp::make_plan(n, cus < 1 ? device_cu_count() : cus);
     *rows_per_block = p.rows;
@@ -440,11 +429,11 @@ int xvec_tsne_plan(int32_t n, int32_t cus, int32_t* rows_per_block, int32_t* sli
 int xvec_tsne_sqdist(const void* x, int32_t x_dtype, int32_t n, int32_t d, int64_t ldx, int32_t round_f32, double* d2,
                      int64_t ldd, void* workspace, size_t workspace_bytes, xvec_stream stream) {
     const char* what = "xvec_tsne_sqdist";
-    TSNE_REFUSE(tp::check_points(n, msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_x(x, x_dtype, d, ldx, msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_matrix(d2, ldd, n, "d2", msg_, sizeof(msg_)));
+    Refusal why;
+    if (tp::check_points(n, why) || tp::check_x(x, x_dtype, d, ldx, why) || tp::check_matrix(d2, ldd, n, "d2", why))
+        return g_terr.refused(XVEC_ERR_ARG, why, what);
     const tp::Layout l = tp::make_layout(n, d);
-    if (const int rc = check_workspace(workspace, workspace_bytes, l.total, what)) return rc;
+    if (const int rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_terr, XVEC_ERR_WORKSPACE, what, 8)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* x64 = part<double>(workspace, l.x64);
     double* sqnorm = part<double>(workspace, l.sqnorm);
@@ -462,13 +451,13 @@ int xvec_tsne_sqdist(const void* x, int32_t x_dtype, int32_t n, int32_t d, int64
 int xvec_tsne_affinities(const double* d2, int64_t ldd, int32_t n, double perplexity, double* p, int64_t ldp, double* betas,
                          void* workspace, size_t workspace_bytes, xvec_stream stream) {
     const char* what = "xvec_tsne_affinities";
-    TSNE_REFUSE(tp::check_points(n, msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_perplexity(perplexity, n, msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_matrix(d2, ldd, n, "d2", msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_matrix(p, ldp, n, "p", msg_, sizeof(msg_)));
+    Refusal why;
+    if (tp::check_points(n, why) || tp::check_perplexity(perplexity, n, why) || tp::check_matrix(d2, ldd, n, "d2", why) ||
+        tp::check_matrix(p, ldp, n, "p", why))
+        return g_terr.refused(XVEC_ERR_ARG, why, what);
     if (betas && reinterpret_cast<uintptr_t>(betas) % 8 != 0) return g_terr.fail(XVEC_ERR_ARG, "%s: betas is not 8-byte aligned", what);
     const tp::Layout l = tp::make_layout(n, 0);
-    if (const int rc = check_workspace(workspace, workspace_bytes, l.total, what)) return rc;
+    if (const int rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_terr, XVEC_ERR_WORKSPACE, what, 8)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     double* row_sum = part<double>(workspace, l.row_sum);
     double* scalars = part<double>(workspace, l.scalars);
@@ -489,16 +478,15 @@ int xvec_tsne_steps(const double* p, int64_t ldp, int32_t n, int32_t n_component
                     int64_t ldy, int32_t n_steps, double exaggeration, double momentum, double learning_rate, double min_gain,
                     double* kl_out, double* grad_norm_out, void* workspace, size_t workspace_bytes, xvec_stream stream) {
     const char* what = "xvec_tsne_steps";
-    TSNE_REFUSE(tp::check_points(n, msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_steps(n_components, n_steps, exaggeration, momentum, learning_rate, min_gain, msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_matrix(p, ldp, n, "p", msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_matrix(y, ldy, 2, "y", msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_matrix(update, ldy, 2, "update", msg_, sizeof(msg_)));
-    TSNE_REFUSE(tp::check_matrix(gains, ldy, 2, "gains", msg_, sizeof(msg_)));
+    Refusal why;
+    if (tp::check_points(n, why) || tp::check_steps(n_components, n_steps, exaggeration, momentum, learning_rate, min_gain, why) ||
+        tp::check_matrix(p, ldp, n, "p", why) || tp::check_matrix(y, ldy, 2, "y", why) ||
+        tp::check_matrix(update, ldy, 2, "update", why) || tp::check_matrix(gains, ldy, 2, "gains", why))
+        return g_terr.refused(XVEC_ERR_ARG, why, what);
     if ((kl_out && reinterpret_cast<uintptr_t>(kl_out) % 8 != 0) || (grad_norm_out && reinterpret_cast<uintptr_t>(grad_norm_out) % 8 != 0))
         return g_terr.fail(XVEC_ERR_ARG, "%s: kl_out or grad_norm_out is not 8-byte aligned", what);
     const tp::Layout l = tp::make_layout(n, 0);
-    if (const int rc = check_workspace(workspace, workspace_bytes, l.total, what)) return rc;
+    if (const int rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_terr, XVEC_ERR_WORKSPACE, what, 8)) return rc;
     const tp::Plan plan = tp::make_plan(n, device_cu_count());
     hipStream_t s = static_cast<hipStream_t>(stream);
     StepArgs g{};

@@ -5,61 +5,57 @@
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/xvec_tsne.h"
+#include "plan_support.h"
 
 namespace xvec {
 namespace tsne_plan {
 
-constexpr size_t kAlign = 256;
+// ---------------------------------------------------------------- argument checks: 0, or 1 with the reason in why
 
-inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
-
-// ---------------------------------------------------------------- argument checks: 0, or 1 with the reason in msg
-
-inline int check_points(int32_t n, char* msg, size_t len) {
-    if (n < 2) return std::snprintf(msg, len, "n = %d: need at least two points", n), 1;
+inline int check_points(int32_t n, Refusal& why) {
+    if (n < 2) return why.refuse("n = %d: need at least two points", n);
     if (n > XVEC_TSNE_MAX_POINTS)
-        return std::snprintf(msg, len, "n = %d is over XVEC_TSNE_MAX_POINTS = %d", n, XVEC_TSNE_MAX_POINTS), 1;
+        return why.refuse("n = %d is over XVEC_TSNE_MAX_POINTS = %d", n, XVEC_TSNE_MAX_POINTS);
     return 0;
 }
 
 // A matrix of doubles with `cols` columns used per row.
-inline int check_matrix(const void* p, int64_t ld, int64_t cols, const char* what, char* msg, size_t len) {
-    if (!p) return std::snprintf(msg, len, "null pointer: %s", what), 1;
-    if (reinterpret_cast<uintptr_t>(p) % 8 != 0) return std::snprintf(msg, len, "%s is not 8-byte aligned", what), 1;
+inline int check_matrix(const void* p, int64_t ld, int64_t cols, const char* what, Refusal& why) {
+    if (!p) return why.refuse("null pointer: %s", what);
+    if (reinterpret_cast<uintptr_t>(p) % 8 != 0) return why.refuse("%s is not 8-byte aligned", what);
     if (ld < cols)
-        return std::snprintf(msg, len, "%s row stride %lld is smaller than its %lld columns", what, (long long)ld, (long long)cols), 1;
+        return why.refuse("%s row stride %lld is smaller than its %lld columns", what, (long long)ld, (long long)cols);
     return 0;
 }
 
-inline int check_x(const void* x, int32_t x_dtype, int32_t d, int64_t ldx, char* msg, size_t len) {
-    if (x_dtype != XVEC_TSNE_X_F32 && x_dtype != XVEC_TSNE_X_F64) return std::snprintf(msg, len, "unknown x_dtype %d", x_dtype), 1;
-    if (d < 1 || d > XVEC_TSNE_MAX_DIM) return std::snprintf(msg, len, "d = %d must lie in 1 .. XVEC_TSNE_MAX_DIM = %d", d, XVEC_TSNE_MAX_DIM), 1;
-    if (!x) return std::snprintf(msg, len, "null pointer: x"), 1;
+inline int check_x(const void* x, int32_t x_dtype, int32_t d, int64_t ldx, Refusal& why) {
+    if (x_dtype != XVEC_TSNE_X_F32 && x_dtype != XVEC_TSNE_X_F64) return why.refuse("unknown x_dtype %d", x_dtype);
+    if (d < 1 || d > XVEC_TSNE_MAX_DIM) return why.refuse("d = %d must lie in 1 .. XVEC_TSNE_MAX_DIM = %d", d, XVEC_TSNE_MAX_DIM);
+    if (!x) return why.refuse("null pointer: x");
     const unsigned size = x_dtype == XVEC_TSNE_X_F32 ? 4 : 8;
-    if (reinterpret_cast<uintptr_t>(x) % size != 0) return std::snprintf(msg, len, "x is not %u-byte aligned", size), 1;
-    if (ldx < d) return std::snprintf(msg, len, "x row stride %lld is smaller than d = %d", (long long)ldx, d), 1;
+    if (reinterpret_cast<uintptr_t>(x) % size != 0) return why.refuse("x is not %u-byte aligned", size);
+    if (ldx < d) return why.refuse("x row stride %lld is smaller than d = %d", (long long)ldx, d);
     return 0;
 }
 
-inline int check_perplexity(double perplexity, int32_t n, char* msg, size_t len) {
+inline int check_perplexity(double perplexity, int32_t n, Refusal& why) {
     if (!std::isfinite(perplexity) || !(perplexity > 0.0) || !(perplexity < (double)n))
-        return std::snprintf(msg, len, "perplexity = %g must be finite, positive and below n = %d", perplexity, n), 1;
+        return why.refuse("perplexity = %g must be finite, positive and below n = %d", perplexity, n);
     return 0;
 }
 
 inline int check_steps(int32_t n_components, int32_t n_steps, double exaggeration, double momentum, double learning_rate,
-                       double min_gain, char* msg, size_t len) {
-    if (n_components != 2) return std::snprintf(msg, len, "n_components = %d: only two output dimensions", n_components), 1;
-    if (n_steps < 1) return std::snprintf(msg, len, "n_steps = %d: need at least one iteration", n_steps), 1;
+                       double min_gain, Refusal& why) {
+    if (n_components != 2) return why.refuse("n_components = %d: only two output dimensions", n_components);
+    if (n_steps < 1) return why.refuse("n_steps = %d: need at least one iteration", n_steps);
     if (!std::isfinite(exaggeration) || !(exaggeration > 0.0))
-        return std::snprintf(msg, len, "exaggeration = %g must be finite and positive", exaggeration), 1;
-    if (!std::isfinite(momentum) || momentum < 0.0) return std::snprintf(msg, len, "momentum = %g must be finite and not negative", momentum), 1;
+        return why.refuse("exaggeration = %g must be finite and positive", exaggeration);
+    if (!std::isfinite(momentum) || momentum < 0.0) return why.refuse("momentum = %g must be finite and not negative", momentum);
     if (!std::isfinite(learning_rate) || !(learning_rate > 0.0))
-        return std::snprintf(msg, len, "learning_rate = %g must be finite and positive", learning_rate), 1;
-    if (!std::isfinite(min_gain) || min_gain < 0.0) return std::snprintf(msg, len, "min_gain = %g must be finite and not negative", min_gain), 1;
+        return why.refuse("learning_rate = %g must be finite and positive", learning_rate);
+    if (!std::isfinite(min_gain) || min_gain < 0.0) return why.refuse("min_gain = %g must be finite and not negative", min_gain);
     return 0;
 }
 
@@ -113,21 +109,16 @@ struct Layout {
 
 inline Layout make_layout(int32_t n, int32_t d) {
     Layout l{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        const size_t at = off;
-        off += align_up(bytes);
-        return at;
-    };
+    Carver c;
     const size_t N = (size_t)n, S = (size_t)max_slices(n);
-    l.x64 = take(N * (size_t)d * sizeof(double));
-    l.sqnorm = take(N * sizeof(double));
-    l.row_sum = take(N * sizeof(double));
-    l.scalars = take(4 * sizeof(double));
-    l.partials = take(S * N * 5 * sizeof(double));
-    l.kl_part = take(S * N * sizeof(double));
-    l.norm_part = take((size_t)update_blocks(n) * sizeof(double));
-    l.total = off;
+    l.x64 = c.take_bytes(N * (size_t)d * sizeof(double));
+    l.sqnorm = c.take_bytes(N * sizeof(double));
+    l.row_sum = c.take_bytes(N * sizeof(double));
+    l.scalars = c.take_bytes(4 * sizeof(double));
+    l.partials = c.take_bytes(S * N * 5 * sizeof(double));
+    l.kl_part = c.take_bytes(S * N * sizeof(double));
+    l.norm_part = c.take_bytes((size_t)update_blocks(n) * sizeof(double));
+    l.total = c.total();
     return l;
 }
 

@@ -298,30 +298,25 @@ struct Shape {
 };
 
 int check_decide(const Shape& s, const xvec_vad_options* vad, const uint8_t* mask, int64_t mask_stride, const int32_t* counts) {
-    char msg[256];
-    if (vad_plan::check_shape(s.B, s.T, s.C, s.rs, s.us, "x:", msg, sizeof(msg))) return g_verr.fail(XVEC_ERR_ARG, "%s", msg);
-    if (vad_plan::check_vad(vad, s.C, msg, sizeof(msg))) return g_verr.fail(XVEC_ERR_ARG, "%s", msg);
-    if (vad_plan::check_mask_stride(mask_stride, s.T, msg, sizeof(msg))) return g_verr.fail(XVEC_ERR_ARG, "%s", msg);
+    Refusal why;
+    if (vad_plan::check_shape(s.B, s.T, s.C, s.rs, s.us, "x:", why) || vad_plan::check_vad(vad, s.C, why) ||
+        vad_plan::check_mask_stride(mask_stride, s.T, why))
+        return g_verr.refused(XVEC_ERR_ARG, why);
     if (!s.x || !mask || !counts) return g_verr.fail(XVEC_ERR_ARG, "null pointer: x / mask / counts");
     return XVEC_OK;
 }
 
 int check_normalise(const Shape& s, const xvec_cmvn_options* cmvn, const float* y, int64_t yrs, int64_t yus, vad_plan::Tile* tile) {
-    char msg[256];
-    if (vad_plan::check_shape(s.B, s.T, s.C, s.rs, s.us, "x:", msg, sizeof(msg))) return g_verr.fail(XVEC_ERR_ARG, "%s", msg);
-    if (vad_plan::check_shape(s.B, s.T, s.C, yrs, yus, "y:", msg, sizeof(msg))) return g_verr.fail(XVEC_ERR_ARG, "%s", msg);
-    if (vad_plan::check_cmvn(cmvn, msg, sizeof(msg))) return g_verr.fail(XVEC_ERR_ARG, "%s", msg);
+    Refusal why;
+    if (vad_plan::check_shape(s.B, s.T, s.C, s.rs, s.us, "x:", why) || vad_plan::check_shape(s.B, s.T, s.C, yrs, yus, "y:", why) ||
+        vad_plan::check_cmvn(cmvn, why))
+        return g_verr.refused(XVEC_ERR_ARG, why);
     if (!s.x || !y) return g_verr.fail(XVEC_ERR_ARG, "null pointer: x / y");
     if (vad_plan::plan_tile(s.C, vad_plan::span(cmvn), tile))
         return g_verr.fail(XVEC_ERR_ARG, "no tile of C = %d channels fits the LDS budget at this window", s.C);
     if (vad_plan::grid_blocks(s.B, s.T, s.C, *tile) > 0x7fffffffLL)
         return g_verr.fail(XVEC_ERR_TOO_LARGE, "B = %d utterances of T = %d frames are more than 2^31 - 1 blocks", s.B, s.T);
     return XVEC_OK;
-}
-
-int check_workspace(const void* workspace, size_t workspace_bytes, const vad_plan::Layout& l) {
-    if (!workspace) return g_verr.fail(XVEC_ERR_ARG, "null pointer: workspace");
-    return workspace_ok(workspace_bytes, l.total, g_verr);
 }
 
 VadArgs decide_args(const Shape& s, const xvec_vad_options& vad, uint8_t* mask, int64_t mask_stride, int32_t* counts, double* thr) {
@@ -413,11 +408,11 @@ int xvec_cmvn_sliding(const float* x, int32_t B, int32_t T, int32_t C, int64_t r
     if ((rc = check_normalise(s, cmvn, y, y_row_stride, y_utt_stride, &tile))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (!mask) return launch_cmvn(s, cmvn, tile, nullptr, 0, nullptr, nullptr, y, y_row_stride, y_utt_stride, new_lengths, st);
-    char msg[256];
-    if (vad_plan::check_mask_stride(mask_stride, T, msg, sizeof(msg))) return g_verr.fail(XVEC_ERR_ARG, "%s", msg);
+    Refusal why;
+    if (vad_plan::check_mask_stride(mask_stride, T, why)) return g_verr.refused(XVEC_ERR_ARG, why);
     if (!new_lengths) return g_verr.fail(XVEC_ERR_ARG, "null pointer: new_lengths (optional only without a mask)");
     const vad_plan::Layout l = vad_plan::make_layout(B, T);
-    if ((rc = check_workspace(workspace, workspace_bytes, l))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_verr))) return rc;
     char* ws = static_cast<char*>(workspace);
     VadArgs g{};
     g.B = B;
@@ -442,7 +437,7 @@ int xvec_vad_cmvn(const float* x, int32_t B, int32_t T, int32_t C, int64_t row_s
     if ((rc = check_decide(s, vad, mask, mask_stride, counts))) return rc;
     if ((rc = check_normalise(s, cmvn, y, y_row_stride, y_utt_stride, &tile))) return rc;
     const vad_plan::Layout l = vad_plan::make_layout(B, T);
-    if ((rc = check_workspace(workspace, workspace_bytes, l))) return rc;
+    if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_verr))) return rc;
     char* ws = static_cast<char*>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
     VadArgs g = decide_args(s, *vad, mask, mask_stride, counts, thr);

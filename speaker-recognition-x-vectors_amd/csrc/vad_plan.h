@@ -5,9 +5,9 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 
 #include "../../include/xvec_vad.h"
+#include "plan_support.h"
 
 #if defined(__HIPCC__)
 #define XVEC_VAD_FN __host__ __device__ __forceinline__
@@ -17,10 +17,6 @@
 
 namespace xvec {
 namespace vad_plan {
-
-constexpr size_t kAlign = 256;
-
-inline size_t align_up(size_t v) { return (v + kAlign - 1) & ~(kAlign - 1); }
 
 // The window [lo, hi) of frame t in an utterance of L frames (0 <= t < L), include/xvec_vad.h.  0 <= lo <= t < hi <= L and
 // hi - lo <= span(cmn_window, min_window, center); from t to t + 1 lo rises by 0 or 1 and hi never falls.
@@ -57,47 +53,44 @@ inline int span(const xvec_cmvn_options* o) {
 // The chunks of XVEC_VAD_LANES frames of an utterance of T frames.
 XVEC_VAD_FN int chunks(int T) { return (T + XVEC_VAD_LANES - 1) / XVEC_VAD_LANES; }
 
-// ---------------------------------------------------------------- argument checks: 0, or 1 with the reason in msg
+// ---------------------------------------------------------------- argument checks: 0, or 1 with the reason in why
 
-inline int check_shape(int32_t B, int32_t T, int32_t C, int64_t row_stride, int64_t utt_stride, const char* what, char* msg,
-                       size_t len) {
-    if (B < 1 || T < 1 || C < 1) return std::snprintf(msg, len, "B = %d, T = %d, C = %d: every one must be at least 1", B, T, C), 1;
+inline int check_shape(int32_t B, int32_t T, int32_t C, int64_t row_stride, int64_t utt_stride, const char* what, Refusal& why) {
+    if (B < 1 || T < 1 || C < 1) return why.refuse("B = %d, T = %d, C = %d: every one must be at least 1", B, T, C);
     if (C > XVEC_VAD_MAX_CHANNELS)
-        return std::snprintf(msg, len, "C = %d is over XVEC_VAD_MAX_CHANNELS = %d", C, XVEC_VAD_MAX_CHANNELS), 1;
-    if (row_stride < C) return std::snprintf(msg, len, "%s row stride %lld is smaller than C = %d", what, (long long)row_stride, C), 1;
+        return why.refuse("C = %d is over XVEC_VAD_MAX_CHANNELS = %d", C, XVEC_VAD_MAX_CHANNELS);
+    if (row_stride < C) return why.refuse("%s row stride %lld is smaller than C = %d", what, (long long)row_stride, C);
     const int64_t need = (int64_t)(T - 1) * row_stride + C;
     if (utt_stride < need)
-        return std::snprintf(msg, len, "%s utterance stride %lld is smaller than the %lld floats of an utterance", what,
-                             (long long)utt_stride, (long long)need), 1;
+        return why.refuse("%s utterance stride %lld is smaller than the %lld floats of an utterance", what, (long long)utt_stride,
+                          (long long)need);
     return 0;
 }
 
-inline int check_mask_stride(int64_t mask_stride, int32_t T, char* msg, size_t len) {
-    if (mask_stride < T) return std::snprintf(msg, len, "mask stride %lld is smaller than T = %d", (long long)mask_stride, T), 1;
+inline int check_mask_stride(int64_t mask_stride, int32_t T, Refusal& why) {
+    if (mask_stride < T) return why.refuse("mask stride %lld is smaller than T = %d", (long long)mask_stride, T);
     return 0;
 }
 
-inline int check_vad(const xvec_vad_options* o, int32_t C, char* msg, size_t len) {
-    if (!o) return std::snprintf(msg, len, "null pointer: vad options"), 1;
+inline int check_vad(const xvec_vad_options* o, int32_t C, Refusal& why) {
+    if (!o) return why.refuse("null pointer: vad options");
     if (o->energy_threshold != o->energy_threshold || o->energy_mean_scale != o->energy_mean_scale)
-        return std::snprintf(msg, len, "energy_threshold or energy_mean_scale is NaN"), 1;
+        return why.refuse("energy_threshold or energy_mean_scale is NaN");
     if (!(o->proportion_threshold > 0.0 && o->proportion_threshold < 1.0))
-        return std::snprintf(msg, len, "proportion_threshold = %g must lie strictly between 0 and 1", o->proportion_threshold), 1;
-    if (o->frames_context < 0) return std::snprintf(msg, len, "frames_context = %d must not be negative", o->frames_context), 1;
+        return why.refuse("proportion_threshold = %g must lie strictly between 0 and 1", o->proportion_threshold);
+    if (o->frames_context < 0) return why.refuse("frames_context = %d must not be negative", o->frames_context);
     if (o->energy_col < 0 || o->energy_col >= C)
-        return std::snprintf(msg, len, "energy_col = %d must lie in 0 .. C - 1 = %d", o->energy_col, C - 1), 1;
+        return why.refuse("energy_col = %d must lie in 0 .. C - 1 = %d", o->energy_col, C - 1);
     return 0;
 }
 
 // (a null pointer is fine: no normalisation)
-inline int check_cmvn(const xvec_cmvn_options* o, char* msg, size_t len) {
+inline int check_cmvn(const xvec_cmvn_options* o, Refusal& why) {
     if (!o) return 0;
     if (o->cmn_window < 1 || o->cmn_window > XVEC_CMVN_MAX_WINDOW)
-        return std::snprintf(msg, len, "cmn_window = %d must lie in 1 .. XVEC_CMVN_MAX_WINDOW = %d", o->cmn_window,
-                             XVEC_CMVN_MAX_WINDOW), 1;
+        return why.refuse("cmn_window = %d must lie in 1 .. XVEC_CMVN_MAX_WINDOW = %d", o->cmn_window, XVEC_CMVN_MAX_WINDOW);
     if (o->min_window < 1 || o->min_window > XVEC_CMVN_MAX_WINDOW + 1)
-        return std::snprintf(msg, len, "min_window = %d must lie in 1 .. XVEC_CMVN_MAX_WINDOW + 1 = %d", o->min_window,
-                             XVEC_CMVN_MAX_WINDOW + 1), 1;
+        return why.refuse("min_window = %d must lie in 1 .. XVEC_CMVN_MAX_WINDOW + 1 = %d", o->min_window, XVEC_CMVN_MAX_WINDOW + 1);
     return 0;
 }
 
@@ -113,9 +106,10 @@ struct Layout {
 inline Layout make_layout(int32_t B, int32_t T) {
     Layout l{};
     if (B < 1 || T < 1) return l;
-    l.prefix = 0;
-    l.count = align_up((size_t)B * (size_t)chunks(T) * sizeof(int32_t));
-    l.total = l.count + align_up((size_t)B * sizeof(int32_t));
+    Carver c;
+    l.prefix = c.take_bytes((size_t)B * (size_t)chunks(T) * sizeof(int32_t));
+    l.count = c.take_bytes((size_t)B * sizeof(int32_t));
+    l.total = c.total();
     return l;
 }
 

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import byte_workspace, checker, dev_f64, require_device, score_matrix, stream as _stream
 
 __all__ = ["cluster", "Clustering", "turns", "write_rttm", "Diarizer", "Diarization", "MAX_SEGMENTS", "THREADS_SMALL",
            "THREADS_LARGE", "RESCAN_WIDTH"]
@@ -46,13 +46,7 @@ class Clustering(NamedTuple):
 
 
 def _matrix(scores, what) -> torch.Tensor:
-    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
-        raise RuntimeError(f"{what} runs on a HIP device only (no CPU path): the scores must be a device tensor")
-    if scores.dim() != 2 or scores.dtype != torch.float64:
-        raise ValueError(f"{what}: expected a float64 [N, N] score matrix")
-    if scores.shape[0] < 1 or scores.shape[0] != scores.shape[1]:
-        raise ValueError(f"{what}: the score matrix must be square and not empty, got {tuple(scores.shape)}")
-    return scores if scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1] else scores.contiguous()
+    return score_matrix(scores, what, "[N, N]", square=True)
 
 
 def _rec_start(rec_start, n, what) -> np.ndarray:

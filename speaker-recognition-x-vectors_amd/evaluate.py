@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import checker, dev_f64, require_device, score_matrix, sized_workspace, stream as _stream
 
 __all__ = ["TrialList", "TrialResult", "evaluate_trials", "evaluate_all_pairs", "sorted_keys", "EER", "minDCF",
            "plda_score_stat_object"]
@@ -109,20 +109,12 @@ class TrialList:
 
 
 def _matrix(scoremat) -> torch.Tensor:
-    if not isinstance(scoremat, torch.Tensor) or not scoremat.is_cuda:
-        raise RuntimeError("trial evaluation runs on a HIP device only (no CPU path): the scores must be a device tensor")
-    if scoremat.dim() != 2 or scoremat.dtype != torch.float64:
-        raise ValueError("expected a float64 [n_rows, n_cols] score matrix")
-    if scoremat.shape[0] < 1 or scoremat.shape[1] < 1:
-        raise ValueError("empty score matrix")
-    return scoremat if scoremat.stride(1) == 1 and scoremat.stride(0) >= scoremat.shape[1] else scoremat.contiguous()
+    return score_matrix(scoremat, "trial evaluation")
 
 
 def _workspace(n: int, device) -> torch.Tensor:
-    need = int(_hip.lib.xvec_eval_workspace_bytes(n))
-    if need == 0:
-        raise ValueError(f"{n} trials: the count must lie in 1 .. 2^31 - 1")
-    return byte_workspace(need, device)
+    refusal = lambda: ValueError(f"{n} trials: the count must lie in 1 .. 2^31 - 1")
+    return sized_workspace(_hip.lib.xvec_eval_workspace_bytes(n), refusal, device)
 
 
 def _read_result(out: torch.Tensor, what: str) -> TrialResult:

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import byte_workspace, checker, dev_f64, require_device, score_matrix, stream as _stream
 
 __all__ = ["group_models", "SpeakerModels", "enroll", "open_set_scores", "identify", "Identification", "SpeakerIdentifier",
            "identification_rate", "COLS", "SLICE_ROWS", "BLOCK_ROWS", "TOPK_BLOCK_ROWS", "APPLY_ROWS", "APPLY_COLS", "MAX_K"]
@@ -85,13 +85,7 @@ def enroll(xvecs, names, device="cuda:0") -> SpeakerModels:
 
 
 def _matrix(scores, what) -> torch.Tensor:
-    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
-        raise RuntimeError(f"{what} runs on a HIP device only (no CPU path): the scores must be a device tensor")
-    if scores.dim() != 2 or scores.dtype != torch.float64:
-        raise ValueError(f"{what}: expected a float64 [n_models, n_tests] score matrix")
-    if scores.shape[0] < 1 or scores.shape[1] < 1:
-        raise ValueError(f"{what}: empty score matrix")
-    return scores if scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1] else scores.contiguous()
+    return score_matrix(scores, what, "[n_models, n_tests]")
 
 
 def open_set_scores(S, p_known, out=None, workspace=None) -> torch.Tensor:

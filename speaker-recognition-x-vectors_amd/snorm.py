@@ -24,7 +24,7 @@ from typing import NamedTuple
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import byte_workspace, checker, dev_f64, ptr, require_device, score_matrix as _matrix, stream as _stream
 
 __all__ = ["CohortStats", "cohort_stats", "apply_norm", "ScoreNormalizer", "THREADS", "RESIDENT_SMALL", "RESIDENT_MAX",
            "APPLY_ROWS", "APPLY_COLS"]
@@ -41,16 +41,6 @@ class CohortStats(NamedTuple):
     std: torch.Tensor        # [n] float64, unbiased
     kth: torch.Tensor        # [n] float64: the smallest selected score
     n_used: torch.Tensor     # [n] int32: the cells selected (min(top_k, valid cells))
-
-
-def _matrix(scores, what) -> torch.Tensor:
-    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
-        raise RuntimeError(f"{what} runs on a HIP device only (no CPU path): the scores must be a device tensor")
-    if scores.dim() != 2 or scores.dtype != torch.float64:
-        raise ValueError(f"{what}: expected a float64 [n_rows, n_cols] score matrix")
-    if scores.shape[0] < 1 or scores.shape[1] < 1:
-        raise ValueError(f"{what}: empty score matrix")
-    return scores if scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1] else scores.contiguous()
 
 
 def cohort_stats(cohort_scores, top_k=0, skip_col=None, workspace=None) -> CohortStats:
@@ -112,7 +102,6 @@ def apply_norm(scores, row_stats=None, col_stats=None, out=None) -> torch.Tensor
         if (not isinstance(out, torch.Tensor) or out.device != s.device or out.dtype != torch.float64
                 or out.shape != s.shape or out.stride(1) != 1 or out.stride(0) < n_cols):
             raise ValueError("apply_norm: out must be a float64 device matrix of the scores' shape with unit column stride")
-    ptr = lambda t: None if t is None else t.data_ptr()
     with torch.cuda.device(s.device):
         _check(_hip.lib.xvec_snorm_apply(s.data_ptr(), s.stride(0), n_rows, n_cols, ptr(rm), ptr(rs), ptr(cm), ptr(cs),
                                          out.data_ptr(), out.stride(0), _stream(s.device)))

@@ -29,7 +29,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip as _hip
-from ._device import byte_workspace as _byte_workspace
+from ._device import ptr, sized_workspace as _sized_workspace
 from ._device import checker as _checker
 from ._device import stream as _stream_ptr
 from .model import TOTAL_CONTEXT, TdnnLayer, XVectorModel, _require_gpu
@@ -60,13 +60,16 @@ def _host_lengths(lengths, B, lo, hi, what):
     return host
 
 
-def _workspace(device, B, T, cin, cout, ctx, n_ctx):
-    need = int(_hip.lib.xvec_tdnn_train_workspace_bytes(B, T, cin, cout, ctx, n_ctx))
-    if need == 0:
-        raise _hip.XvecError(_hip.ERR_ARG, _hip.lib.xvec_train_last_error().decode())
+def _stream_workspace(device, need):
+    """The workspace of (device, current stream), grown to the `need` bytes a size query of xvec_train.h answered."""
     key = (device.index, _stream_ptr(device))
-    ws = _workspaces[key] = _byte_workspace(need, device, _workspaces.get(key))
+    refusal = lambda: _hip.XvecError(_hip.ERR_ARG, _hip.lib.xvec_train_last_error().decode())
+    ws = _workspaces[key] = _sized_workspace(need, refusal, device, _workspaces.get(key))
     return ws
+
+
+def _workspace(device, B, T, cin, cout, ctx, n_ctx):
+    return _stream_workspace(device, _hip.lib.xvec_tdnn_train_workspace_bytes(B, T, cin, cout, ctx, n_ctx))
 
 
 class _TdnnTrain(torch.autograd.Function):
@@ -124,7 +127,6 @@ class _TdnnTrain(torch.autograd.Function):
         db = torch.empty(cout, dtype=torch.float32, device=dev)
         dgamma = torch.empty_like(db) if ctx.bn else None
         dbeta = torch.empty_like(db) if ctx.bn else None
-        ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(dev):
             ws = _workspace(dev, B, T, cin, cout, carr, n_ctx)
             args = (dy.data_ptr(), x.data_ptr(), z.data_ptr(), B, T, cin, W.data_ptr(), cout, carr, n_ctx, ptr(gamma),
@@ -141,12 +143,7 @@ class _TdnnTrain(torch.autograd.Function):
 
 
 def _tail_workspace(device, B, tp, c, h, k):
-    need = int(_hip.lib.xvec_train_tail_workspace_bytes(B, tp, c, h, k))
-    if need == 0:
-        raise _hip.XvecError(_hip.ERR_ARG, _hip.lib.xvec_train_last_error().decode())
-    key = (device.index, _stream_ptr(device))
-    ws = _workspaces[key] = _byte_workspace(need, device, _workspaces.get(key))
-    return ws
+    return _stream_workspace(device, _hip.lib.xvec_train_tail_workspace_bytes(B, tp, c, h, k))
 
 
 class _TailTrain(torch.autograd.Function):

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, stream as _stream
+from ._device import byte_workspace, checker, ptr as _ptr, stream as _stream
 
 __all__ = ["energy_vad", "sliding_cmvn", "select_voiced", "VadCmvn", "Vad", "Prepared", "speech_runs", "run_windows", "LANES",
            "MAX_CHANNELS", "MAX_WINDOW", "TILE_MAX", "TILE_MIN", "GROUP_MIN", "LDS_BYTES", "VAD_DEFAULTS", "CMVN_DEFAULTS"]
@@ -89,10 +89,6 @@ def _lengths(lengths, x) -> Optional[torch.Tensor]:
     if t.dim() != 1 or t.shape[0] != x.shape[0]:
         raise ValueError(f"lengths has shape {tuple(t.shape)} for a batch of {x.shape[0]}")
     return t
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _workspace(x, cached=None) -> torch.Tensor:

@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import checker, dev_f64, require_device, sized_workspace, stream as _stream
 
 __all__ = ["pca_matrix_from_scatter", "pca_map", "squared_distances", "tsne_affinities", "tsne_plan", "Tsne", "tsne_map", "scatter_maps",
            "MAX_POINTS"]
@@ -112,10 +112,8 @@ def tsne_plan(n, cus=0) -> tuple:
 
 
 def _workspace(n, d, device, cached=None):
-    need = int(_hip.lib.xvec_tsne_workspace_bytes(int(n), int(d)))
-    if need == 0:
-        raise ValueError(f"t-SNE: n = {n} points must lie in 2 .. {MAX_POINTS} (and d = {d} in 0 .. 65536)")
-    return byte_workspace(need, device, cached)
+    refusal = lambda: ValueError(f"t-SNE: n = {n} points must lie in 2 .. {MAX_POINTS} (and d = {d} in 0 .. 65536)")
+    return sized_workspace(_hip.lib.xvec_tsne_workspace_bytes(int(n), int(d)), refusal, device, cached)
 
 
 def squared_distances(x, round_distances=True, device="cuda:0", out=None, workspace=None) -> torch.Tensor:

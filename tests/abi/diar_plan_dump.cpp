@@ -25,7 +25,7 @@ int main() {
         if (!(in >> what)) return 2;
         std::vector<long long> v;
         for (long long x; in >> x;) v.push_back(x);
-        char msg[256] = "";
+        xvec::Refusal why;
         if (what == "start" || what == "check" || what == "layout" || what == "groups") {
             std::vector<int64_t> rs;
             if (what == "start") {
@@ -35,9 +35,9 @@ int main() {
                 for (long long n : v) rs.push_back(rs.back() + n);
             }
             const int32_t n_rec = (int32_t)rs.size() - 1;
-            const int bad = check_rec_start(rs.data(), n_rec, msg, sizeof(msg));
+            const int bad = check_rec_start(rs.data(), n_rec, why);
             if (what == "start" || what == "check") {
-                if (bad) std::printf("refused %s\n", msg); else std::printf("ok\n");
+                if (bad) std::printf("refused %s\n", why.text); else std::printf("ok\n");
             } else if (bad) {
                 return 3;
             } else if (what == "layout") {
@@ -54,7 +54,7 @@ int main() {
             }
         } else if (what == "want") {
             std::vector<int32_t> w(v.begin(), v.end());
-            if (check_want(w.data(), (int32_t)w.size(), msg, sizeof(msg))) std::printf("refused %s\n", msg); else std::printf("ok\n");
+            if (check_want(w.data(), (int32_t)w.size(), why)) std::printf("refused %s\n", why.text); else std::printf("ok\n");
         } else if (what == "threads") {
             if (v.size() != 1) return 2;
             std::printf("threads %d\n", block_threads(v[0]));

@@ -25,9 +25,9 @@ int main() {
         for (std::string x; in >> x;) a.push_back(x);
         auto I = [&](size_t k) { return (int32_t)std::strtoll(a.at(k).c_str(), nullptr, 10); };
         auto D = [&](size_t k) { return std::strtod(a.at(k).c_str(), nullptr); };      // (reads "nan" and "inf" too)
-        char msg[256] = "";
+        xvec::Refusal why;
         auto verdict = [&](int bad) {
-            if (bad) std::printf("refused %s\n", msg); else std::printf("ok\n");
+            if (bad) std::printf("refused %s\n", why.text); else std::printf("ok\n");
         };
         if (what == "plan" && a.size() == 2) {
             const Plan p = make_plan(I(0), I(1));
@@ -37,11 +37,11 @@ int main() {
             std::printf("layout %zu %zu %zu %zu %zu %zu %zu %zu %d %d\n", l.x64, l.sqnorm, l.row_sum, l.scalars, l.partials, l.kl_part,
                         l.norm_part, l.total, max_slices(I(0)), update_blocks(I(0)));
         } else if (what == "points" && a.size() == 1) {
-            verdict(check_points(I(0), msg, sizeof(msg)));
+            verdict(check_points(I(0), why));
         } else if (what == "perplexity" && a.size() == 2) {
-            verdict(check_perplexity(D(0), I(1), msg, sizeof(msg)));
+            verdict(check_perplexity(D(0), I(1), why));
         } else if (what == "steps" && a.size() == 6) {
-            verdict(check_steps(I(0), I(1), D(2), D(3), D(4), D(5), msg, sizeof(msg)));
+            verdict(check_steps(I(0), I(1), D(2), D(3), D(4), D(5), why));
         } else {
             return 2;
         }

@@ -28,9 +28,9 @@ int main() {
         for (std::string x; in >> x;) a.push_back(x);
         auto I = [&](size_t k) { return std::strtoll(a.at(k).c_str(), nullptr, 10); };
         auto D = [&](size_t k) { return std::strtod(a.at(k).c_str(), nullptr); };
-        char msg[256] = "";
+        xvec::Refusal why;
         auto verdict = [&](int bad) {
-            if (bad) std::printf("refused %s\n", msg); else std::printf("ok\n");
+            if (bad) std::printf("refused %s\n", why.text); else std::printf("ok\n");
         };
         if (what == "window" && a.size() == 4) {
             std::printf("window");
@@ -57,17 +57,17 @@ int main() {
             const Layout l = make_layout((int32_t)I(0), (int32_t)I(1));
             std::printf("layout %zu %zu %zu\n", l.prefix, l.count, l.total);
         } else if (what == "shape" && a.size() == 5) {
-            verdict(check_shape((int32_t)I(0), (int32_t)I(1), (int32_t)I(2), I(3), I(4), "x:", msg, sizeof(msg)));
+            verdict(check_shape((int32_t)I(0), (int32_t)I(1), (int32_t)I(2), I(3), I(4), "x:", why));
         } else if (what == "maskstride" && a.size() == 2) {
-            verdict(check_mask_stride(I(0), (int32_t)I(1), msg, sizeof(msg)));
+            verdict(check_mask_stride(I(0), (int32_t)I(1), why));
         } else if (what == "vad" && a.size() == 1 && a[0] == "null") {
-            verdict(check_vad(nullptr, 1, msg, sizeof(msg)));
+            verdict(check_vad(nullptr, 1, why));
         } else if (what == "vad" && a.size() == 6) {
             const xvec_vad_options o{D(0), D(1), D(2), (int32_t)I(3), (int32_t)I(4)};
-            verdict(check_vad(&o, (int32_t)I(5), msg, sizeof(msg)));
+            verdict(check_vad(&o, (int32_t)I(5), why));
         } else if (what == "cmvn" && a.size() == 2) {
             const xvec_cmvn_options o{(int32_t)I(0), (int32_t)I(1), 0, 0};
-            verdict(check_cmvn(&o, msg, sizeof(msg)));
+            verdict(check_cmvn(&o, why));
         } else {
             return 2;
         }

@@ -1,5 +1,7 @@
-"""What the CPU checks of the compiled kernels share: one hipcc command line (the build's own code-generation flags, device
-code only) and what it reports per kernel.  A plain module like plda_em_ref.py; the test files import it."""
+"""What the CPU checks of the compiled kernels and of the host-only headers share: one hipcc command line (the build's own
+code-generation flags, device code only), what it reports per kernel and the two assertions every resource test makes on that;
+the dump programs of tests/abi/ built with the host compiler; the integer constants of a public header.  A plain module like
+plda_em_ref.py; the test files import it."""
 import functools
 import os
 import re
@@ -52,19 +54,44 @@ def kernel_asm(src):
     return _hipcc("-S", src, "-o", "-").stdout
 
 
-def host_program(name, out_dir, *flags):
-    """tests/abi/`name`.cpp (a stand-alone program over a host-only header of csrc/) compiled with the host compiler into
-    `out_dir`; returns ask(request lines) -> the program's answer lines, one per request."""
+def kernel_instances(kernels, name):
+    """The mangled names among `kernels` that are kernel `name`: its length-prefixed name with no further identifier character
+    behind it, so the plain kernel and every instantiation of a template.  `name` may run on into the mangled template arguments
+    ("aug_mix_kernelILb0") to pick single instantiations."""
+    return [k for k in kernels if re.search(rf"\d{name}(?![a-z0-9_])", k)]
+
+
+def assert_no_scratch(r, what, waves=0):
+    """One kernel's report `r`: no scratch, no spilled register, at least `waves` waves per SIMD."""
+    assert r["scratch"] == 0 and r.get("spill", 0) == 0, (what, r)
+    assert r["occupancy"] >= waves, (what, r)
+
+
+def header_constants(header, prefix):
+    """{NAME: value} of the `#define <prefix>NAME <integer>` lines of include/`header`."""
+    text = open(os.path.join(ROOT, "include", header)).read()
+    return {m.group(1): int(m.group(2)) for m in re.finditer(rf"#define {prefix}(\w+) (\d+)", text)}
+
+
+def host_program(name, out_dir, *flags, include=()):
+    """tests/abi/`name`.cpp (a stand-alone program over a host-only header of csrc/, or of the directories `include`) compiled
+    with the host compiler into `out_dir`; returns ask(request lines) -> the program's answer lines, one per request.  For a
+    program that answers otherwise, ask.output(*argv, stdin=None, text=True) is the whole standard output of one run."""
     exe = os.path.join(str(out_dir), name)
     src = os.path.join(ROOT, "tests", "abi", name + ".cpp")
-    out = subprocess.run([HOST_CXX, "-std=c++17", "-O1", "-Wall", *flags, "-I", CSRC, src, "-o", exe], capture_output=True, text=True,
+    dirs = [arg for d in (CSRC, *include) for arg in ("-I", d)]
+    out = subprocess.run([HOST_CXX, "-std=c++17", "-O1", "-Wall", *flags, *dirs, src, "-o", exe], capture_output=True, text=True,
                          timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
 
-    def ask(requests):
-        res = subprocess.run([exe], input="\n".join(requests) + "\n", capture_output=True, text=True, timeout=120)
+    def output(*argv, stdin=None, text=True):
+        res = subprocess.run([exe, *argv], input=stdin, capture_output=True, text=text, timeout=300)
         assert res.returncode == 0, res.stderr[-500:]
-        lines = res.stdout.splitlines()
+        return res.stdout
+
+    def ask(requests):
+        lines = output(stdin="\n".join(requests) + "\n").splitlines()
         assert len(lines) == len(requests)
         return lines
+    ask.output = output
     return ask

@@ -10,16 +10,13 @@ and count as one; the sum and the quotient round once each): 3 (n - 1) 2^-53 max
 scipy evaluates the same expression per update, so the two sides agree far inside it: 4e-14 against 3e-11 at n = 513."""
 import ctypes
 import io
-import os
-import re
 
 import numpy as np
 import pytest
 
 import diar_ref
-from conftest import ROOT
 from scipy.cluster import hierarchy
-from hipcc_support import host_program, needs_host_cxx
+from hipcc_support import header_constants, host_program, needs_host_cxx
 
 P = 0x1000          # a pointer that is never followed: every call here fails its argument checks first
 INF, NAN = float("inf"), float("nan")
@@ -144,8 +141,7 @@ def test_module_restates_the_header_constants_and_refuses_the_cpu():
     import torch
     import xvector_amd
     from xvector_amd import diarize
-    hdr = open(os.path.join(ROOT, "include", "xvec_diar.h")).read()
-    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define XVEC_DIAR_(\w+) (\d+)", hdr)}
+    consts = header_constants("xvec_diar.h", "XVEC_DIAR_")
     assert consts == {"MAX_SEGMENTS": diarize.MAX_SEGMENTS, "THREADS_SMALL": diarize.THREADS_SMALL,
                       "THREADS_LARGE": diarize.THREADS_LARGE, "RESCAN_WIDTH": diarize.RESCAN_WIDTH}
     assert diarize.MAX_SEGMENTS >= 2048 and diarize.THREADS_SMALL == diarize.RESCAN_WIDTH == 64

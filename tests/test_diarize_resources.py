@@ -6,7 +6,7 @@ import os
 import re
 
 from conftest import ROOT
-from hipcc_support import kernel_resources, needs_hipcc
+from hipcc_support import assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc
 
 SMALL, LARGE, MAX_SEGMENTS = 64, 256, 2048          # tests/test_diarize.py ties the module's copies to the header
 ROW_BYTES = 8 + 4 + 4 + 4 + 4
@@ -25,12 +25,11 @@ def test_diar_kernels_use_no_scratch_and_the_lds_the_design_states():
     assert len(kernels) == sum(len(v) for v in KERNELS.values()), sorted(kernels)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for want, lds in KERNELS.items():
-        names = [k for k in kernels if re.search(rf"\d{want}(I|E)", k)]
+        names = kernel_instances(kernels, want)
         assert len(names) == len(lds), (want, sorted(kernels))
         for name in names:
             r = kernels[name]
-            assert r["scratch"] == 0 and r.get("spill", 0) == 0, (name, r)
-            assert r["occupancy"] >= 2, (name, r)
+            assert_no_scratch(r, name, waves=2)
         assert sorted(kernels[n]["lds"] for n in names) == sorted(lds), (want, [kernels[n] for n in names])
         for size in lds:
             if size:                            # DESIGN.md's table row: | `<kernel>` ... | <LDS bytes> |

@@ -2,14 +2,12 @@
 the package's mean_stat_per_model, the reference's fp64 open-set loop against its longdouble form (and the library's algorithm,
 restated in numpy, against both), the header's constants against the module's, and the C ABI's argument errors (each returns
 before the library touches a device)."""
-import os
-import re
 
 import numpy as np
 import pytest
 
 import ident_ref
-from conftest import ROOT
+from hipcc_support import header_constants
 
 P = 0x1000          # a pointer that is never followed: every call here fails its argument checks first
 
@@ -121,8 +119,7 @@ def test_reference_topk_orders_ties_zeros_and_nans():
 def test_module_restates_the_header_constants_and_refuses_the_cpu():
     import torch
     from xvector_amd import hip, identify
-    hdr = open(os.path.join(ROOT, "include", "xvec_ident.h")).read()
-    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define XVEC_IDENT_(\w+) (\d+)", hdr)}
+    consts = header_constants("xvec_ident.h", "XVEC_IDENT_")
     assert consts == {"X_F32": hip.IDENT_X_F32, "X_F64": hip.IDENT_X_F64, "COLS": identify.COLS,
                       "SLICE_ROWS": identify.SLICE_ROWS, "BLOCK_ROWS": identify.BLOCK_ROWS,
                       "TOPK_BLOCK_ROWS": identify.TOPK_BLOCK_ROWS, "APPLY_ROWS": identify.APPLY_ROWS,

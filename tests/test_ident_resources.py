@@ -6,7 +6,7 @@ import os
 import re
 
 from conftest import ROOT
-from hipcc_support import kernel_resources, needs_hipcc
+from hipcc_support import assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc
 
 WAVES, COLS = 4, 64                            # XVEC_IDENT_COLS (tests/test_ident.py ties the module's copy to the header)
 STATS_LDS = (WAVES - 1) * COLS * (8 + 8 + 4)   # m1, R, i1 of the waves 1 .. 3
@@ -28,12 +28,11 @@ def test_ident_kernels_use_no_scratch_and_the_lds_the_design_states():
     assert len(kernels) == sum(k[0] for k in KERNELS.values()), sorted(kernels)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for want, (count, lds) in KERNELS.items():
-        names = [k for k in kernels if re.search(rf"\d{want}(I|E)", k)]
+        names = kernel_instances(kernels, want)
         assert len(names) == count, (want, sorted(kernels))
         for name in names:
             r = kernels[name]
-            assert r["scratch"] == 0 and r.get("spill", 0) == 0, (name, r)
-            assert r["occupancy"] >= 2, (name, r)
+            assert_no_scratch(r, name, waves=2)
         assert sorted(kernels[n]["lds"] for n in names) == sorted(lds), (want, [kernels[n] for n in names])
         for size in lds:
             if size:                            # DESIGN.md's table row: | `<kernel>` ... | <LDS bytes> |

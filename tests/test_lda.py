@@ -11,6 +11,7 @@ import pytest
 
 import lda_ref as ref
 from conftest import ROOT
+from hipcc_support import header_constants
 
 # (N, D, C, rank, offset): tests/lda_ref.make_case, default_rng(1234)
 CASES = [(200, 24, 7, 6, 0.0), (400, 65, 12, 8, 0.0), (300, 130, 9, 8, 1e3), (97, 17, 5, 4, 0.0)]
@@ -32,8 +33,8 @@ def test_binding_constants_are_the_headers():
     from xvector_amd import hip
     from xvector_amd.lda import NORM_CLIP
     src = open(os.path.join(ROOT, "include", "xvec_lda.h")).read()
-    macro = lambda name: int(re.search(rf"#define {name} (\d+)", src).group(1))
-    assert (hip.EMBED_MAX_DIM, hip.EMBED_ROW_GROUP) == (macro("XVEC_EMBED_MAX_DIM"), macro("XVEC_EMBED_ROW_GROUP"))
+    embed = header_constants("xvec_lda.h", "XVEC_EMBED_")
+    assert (hip.EMBED_MAX_DIM, hip.EMBED_ROW_GROUP) == (embed["MAX_DIM"], embed["ROW_GROUP"])
     assert hip.EMBED_MAX_DIM >= 3000                          # the pooled statistics must fit
     assert re.search(r"XVEC_LDA_X_F32 = (\d), XVEC_LDA_X_F64 = (\d)", src).groups() == (str(hip.LDA_X_F32), str(hip.LDA_X_F64))
     assert NORM_CLIP == ref.NORM_CLIP == 1e-8

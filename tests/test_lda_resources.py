@@ -5,7 +5,7 @@ import os
 import re
 
 from conftest import ROOT
-from hipcc_support import kernel_resources, needs_hipcc
+from hipcc_support import assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc
 
 SCATTER_LDS = 2 * 2 * 16 * 80 * 8               # sA, sB: two buffers of 16 rows x 80 doubles each
 EMBED_LDS = 2 * 64 * 18 * 8 + 2 * 16 * 80 * 8   # sX: two buffers of 64 rows x 18 doubles; sW: two of 16 x 80
@@ -27,11 +27,11 @@ def test_lda_kernels_use_no_scratch_and_the_lds_the_design_states():
     assert len(kernels) == sum(k[0] for k in KERNELS.values()), sorted(kernels)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for want, (count, lds, occupancy) in KERNELS.items():
-        names = [k for k in kernels if re.search(rf"\d{want}(I|E)", k)]
+        names = kernel_instances(kernels, want)
         assert len(names) == count, (want, sorted(kernels))
         for name in names:
             r = kernels[name]
-            assert r["scratch"] == 0 and r.get("spill", 0) == 0, (name, r)
+            assert_no_scratch(r, name)
             assert r["lds"] == lds and r["occupancy"] == occupancy, (name, r)
         if lds > 4096:                          # DESIGN.md's table row: | <kernel> | <LDS bytes> | <blocks per CU> | <waves per SIMD> |
             assert 160 * 1024 // lds >= occupancy, (want, "the LDS image does not leave room for the blocks the occupancy counts")

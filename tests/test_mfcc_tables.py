@@ -3,17 +3,15 @@ per session with the host compiler, writes the blob and its offsets for a config
 oracle's formulas or against the layout rule the kernel reads it by (csrc/mfcc.hip).  No GPU, no HIP library."""
 import functools
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import mfcc_oracle as mo
 from conftest import ROOT
+from hipcc_support import host_program, needs_host_cxx
 
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-pytestmark = pytest.mark.skipif(CXX is None, reason="needs a C++ compiler")
+pytestmark = needs_host_cxx
 
 DEFAULTS = dict(samplerate=16000, winlen=0.025, winstep=0.01, numcep=24, nfilt=26, nfft=512, lowfreq=0.0, highfreq=0.0,
                 preemph=0.97, ceplifter=22, append_energy=1)
@@ -38,20 +36,13 @@ FAST = [k for k, (kw, _, _) in CASES.items() if {**DEFAULTS, **kw}["nfft"] == 51
 
 @pytest.fixture(scope="session")
 def dump_exe(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("mfcc_tables") / "mfcc_tables_dump")
-    src = os.path.join(ROOT, "tests", "abi", "mfcc_tables_dump.cpp")
-    out = subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-I", os.path.join(ROOT, "include"), src, "-o", exe],
-                         capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    return exe
+    return host_program("mfcc_tables_dump", tmp_path_factory.mktemp("mfcc_tables"), include=[os.path.join(ROOT, "include")]).output
 
 
 class Tables:
     def __init__(self, exe, kw, allow_banded):
         self.cfg = {**DEFAULTS, **kw}
-        out = subprocess.run([exe, *[str(v) for v in self.cfg.values()], str(int(allow_banded))], capture_output=True, timeout=60)
-        assert out.returncode == 0, out.stderr[-500:]
-        head, _, raw = out.stdout.partition(b"\n")
+        head, _, raw = exe(*[str(v) for v in self.cfg.values()], str(int(allow_banded)), text=False).partition(b"\n")
         self.rc = int(head.split()[0].split(b"=")[1])
         self.msg = head.decode().partition("msg=")[2]
         if self.rc:

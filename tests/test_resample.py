@@ -3,20 +3,13 @@ with the host compiler (tests/abi/resample_taps_dump.cpp) against the numpy rest
 the restatement's vectorised form against its literal double loop; the filter table against its formula; the restatement
 against an analytic sine (a check that does not come from the same formula); the C ABI's argument errors (each returns before the
 library touches a device) and its error channel; the Python module's constants and its refusal of the CPU."""
-import os
-import re
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import resample_ref as ref
-from conftest import ROOT
-
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-needs_cxx = pytest.mark.skipif(CXX is None, reason="needs a C++ compiler")
+from hipcc_support import header_constants, host_program, needs_host_cxx as needs_cxx
 
 RATIOS = [2.0, 1.0, 16000 / 48000, 16000 / 44100, 44100 / 16000, 16000 / 22050, 16000 / 11025, 1 / 0.9, 1 / 1.1]
 PRECISION = 9
@@ -36,18 +29,8 @@ def best():
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("resample_taps") / "dump")
-    src = os.path.join(ROOT, "tests", "abi", "resample_taps_dump.cpp")
-    inc = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-    out = subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-ffp-contract=off", "-I", inc, src, "-o", exe], capture_output=True,
-                         text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-
-    def ask(requests):
-        res = subprocess.run([exe], input="\n".join(requests) + "\n", capture_output=True, text=True, timeout=300)
-        assert res.returncode == 0, res.stderr[-500:]
-        return res.stdout.splitlines()
-    return ask
+    program = host_program("resample_taps_dump", tmp_path_factory.mktemp("resample_taps"), "-ffp-contract=off")
+    return lambda requests: program.output(stdin="\n".join(requests) + "\n").splitlines()      # (a request has many answer lines)
 
 
 def _check_taps(lines, jobs):
@@ -256,8 +239,7 @@ def test_module_restates_the_header_constants_and_refuses_the_cpu():
     import torch
     import xvector_amd as xa
     from xvector_amd import resample as rs
-    hdr = open(os.path.join(ROOT, "include", "xvec_resample.h")).read()
-    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define XVEC_RESAMPLE_(\w+) (\d+)", hdr)}
+    consts = header_constants("xvec_resample.h", "XVEC_RESAMPLE_")
     assert consts == {"X_F32": rs.X_F32, "X_I16": rs.X_I16, "OUT_F32": rs.OUT_F32, "OUT_F64": rs.OUT_F64, "ACC_F32": rs.ACC_F32,
                       "ACC_F64": rs.ACC_F64, "LEN_I64": rs.LEN_I64, "LEN_I32": rs.LEN_I32, "TILE": rs.TILE, "SPAN_MAX": rs.SPAN_MAX,
                       "PRECISION_MAX": rs.PRECISION_MAX}

@@ -2,37 +2,20 @@
 host compiler, walks tile_rc and tile_rc_sym over whole grids and answers the tile-size rule; the test checks that both walks
 visit every tile exactly once, that a supertile of the plain walk is what the L2 sharing rests on, and that the restatement of
 the rule the GPU tests plan their shapes with (tests/score_support.py) is the header's.  No GPU, no HIP library."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
 import score_support as ss
-from conftest import ROOT
+from hipcc_support import host_program, needs_host_cxx
 
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-pytestmark = pytest.mark.skipif(CXX is None, reason="needs a C++ compiler")
+pytestmark = needs_host_cxx
 
 THIN = [(1, 300), (300, 1), (9, 77), (77, 9), (8, 129), (129, 8), (17, 64)]
 
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("score_tiles") / "dump")
-    src = os.path.join(ROOT, "tests", "abi", "score_tiles_dump.cpp")
-    inc = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-    out = subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-I", inc, src, "-o", exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-
-    def ask(requests):
-        res = subprocess.run([exe], input="\n".join(requests) + "\n", capture_output=True, text=True, timeout=120)
-        assert res.returncode == 0, res.stderr[-500:]
-        lines = res.stdout.splitlines()
-        assert len(lines) == len(requests)
-        return lines
-    return ask
+    return host_program("score_tiles_dump", tmp_path_factory.mktemp("score_tiles"))
 
 
 def _pairs(line, head):

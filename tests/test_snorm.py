@@ -4,19 +4,13 @@ compiler (tests/abi/snorm_keys_dump.cpp), the C ABI's argument errors (each retu
 the independence of the snorm error channel from the score and eval channels."""
 import itertools
 import math
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import snorm_ref
-from conftest import ROOT
-
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-needs_cxx = pytest.mark.skipif(CXX is None, reason="needs a C++ compiler")
+from hipcc_support import header_constants, host_program, needs_host_cxx as needs_cxx
 NAN = float("nan")
 INF = float("inf")
 
@@ -89,19 +83,7 @@ def _bits(x):
 
 @pytest.fixture(scope="module")
 def dump(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("snorm_keys") / "dump")
-    src = os.path.join(ROOT, "tests", "abi", "snorm_keys_dump.cpp")
-    inc = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-    out = subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-I", inc, src, "-o", exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-
-    def ask(requests):
-        res = subprocess.run([exe], input="\n".join(requests) + "\n", capture_output=True, text=True, timeout=120)
-        assert res.returncode == 0, res.stderr[-500:]
-        lines = res.stdout.splitlines()
-        assert len(lines) == len(requests)
-        return lines
-    return ask
+    return host_program("snorm_keys_dump", tmp_path_factory.mktemp("snorm_keys"))
 
 
 def _ordered_doubles():
@@ -245,8 +227,7 @@ def test_module_restates_the_header_constants_and_refuses_the_cpu():
     import re
     import torch
     from xvector_amd import snorm
-    hdr = open(os.path.join(ROOT, "include", "xvec_snorm.h")).read()
-    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define XVEC_SNORM_(\w+) (\d+)", hdr)}
+    consts = header_constants("xvec_snorm.h", "XVEC_SNORM_")
     assert consts == {"THREADS": snorm.THREADS, "RESIDENT_SMALL": snorm.RESIDENT_SMALL, "RESIDENT_MAX": snorm.RESIDENT_MAX,
                       "APPLY_ROWS": snorm.APPLY_ROWS, "APPLY_COLS": snorm.APPLY_COLS}
     with pytest.raises(RuntimeError, match="HIP device only"):

@@ -5,7 +5,7 @@ import os
 import re
 
 from conftest import ROOT
-from hipcc_support import kernel_resources, needs_hipcc
+from hipcc_support import assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc
 
 SMALL, LARGE = 4096, 16384                     # XVEC_SNORM_RESIDENT_SMALL / _MAX (tests/test_snorm.py ties them to the header)
 SIDE = 8 * 8 + 256 * 4 + 4 * 4 + 2 * 4 + 2 * 4 + 8       # wave sums, histogram, scan totals, chosen digit, two counters, the minimum
@@ -24,10 +24,10 @@ def test_snorm_kernels_use_no_scratch_and_the_lds_the_design_states():
     assert len(kernels) == len(KERNELS), sorted(kernels)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for want, (lds, occupancy) in KERNELS.items():
-        name = [k for k in kernels if want in k]
+        name = kernel_instances(kernels, want)
         assert len(name) == 1, (want, sorted(kernels))
         r = kernels[name[0]]
-        assert r["scratch"] == 0 and r.get("spill", 0) == 0, (want, r)
+        assert_no_scratch(r, want)
         assert r["lds"] == lds and r["occupancy"] == occupancy, (want, r)
         blocks = 160 * 1024 // lds if lds else 8
         assert min(8, 2 * blocks) >= occupancy, (want, "the LDS image does not leave room for the blocks the occupancy counts")

@@ -10,7 +10,7 @@ import subprocess
 
 import pytest
 
-from hipcc_support import kernel_resources, needs_hipcc
+from hipcc_support import assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc
 
 GEMM_LDS = 2 * 2 * 16 * 132 * 4
 # OP 3: forward with dropout; OP 1, 2: the dW and dx products, unchanged by dropout.  (vec, ragged) in every combination.
@@ -28,15 +28,15 @@ def test_dropout_kernels_use_no_scratch():
     kernels = kernel_resources("tdnn_train_dropout.hip")
     assert len(kernels) == len(KERNELS) == 24, sorted(kernels)
     for want in KERNELS:
-        name = [k for k in kernels if want in k]
+        name = kernel_instances(kernels, want)
         assert len(name) == 1, (want, sorted(kernels))
         r = kernels[name[0]]
-        assert r["scratch"] == 0 and r.get("spill", 0) == 0, (want, r)
+        assert_no_scratch(r, want)
         assert r["lds"] <= 160 * 1024, (want, r)
     for want in DROPOUT_GEMMS + SHARED_GEMMS:
-        r = kernels[[k for k in kernels if want in k][0]]
+        r = kernels[kernel_instances(kernels, want)[0]]
         assert r["lds"] == GEMM_LDS and 4 * GEMM_LDS <= 160 * 1024, (want, r)
-        assert r["occupancy"] >= 2, (want, r)
+        assert_no_scratch(r, want, waves=2)
 
 
 @needs_hipcc

@@ -4,7 +4,6 @@ functions where it is installed; the host-only plan (csrc/tsne_plan.h) through i
 slices cover every (row, column) once, the workspace regions do not overlap; the C ABI's argument errors (each returns before
 the library touches a device) and its error channel; and the module's schedule on a fake stepper."""
 import os
-import re
 import threading
 
 import numpy as np
@@ -12,7 +11,7 @@ import pytest
 
 import tsne_ref
 from conftest import ROOT, load_golden
-from hipcc_support import host_program, needs_host_cxx
+from hipcc_support import header_constants, host_program, needs_host_cxx
 
 PTR = 0x1000          # a pointer that is never followed: every call here fails its argument checks first
 NAN, INF = float("nan"), float("inf")
@@ -151,8 +150,7 @@ def test_module_restates_the_header_and_refuses_the_cpu():
     import torch
     import xvector_amd
     from xvector_amd import hip, visualize
-    hdr = open(os.path.join(ROOT, "include", "xvec_tsne.h")).read()
-    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define XVEC_TSNE_(\w+) (\d+)", hdr)}
+    consts = header_constants("xvec_tsne.h", "XVEC_TSNE_")
     assert consts["MAX_POINTS"] == visualize.MAX_POINTS == 8192 and consts["SEARCH_STEPS"] == tsne_ref.SEARCH_STEPS
     assert (consts["X_F32"], consts["X_F64"]) == (hip.TSNE_X_F32, hip.TSNE_X_F64)
     exports = {"xvec_tsne_last_error", "xvec_tsne_workspace_bytes", "xvec_tsne_plan", "xvec_tsne_sqdist", "xvec_tsne_affinities",

@@ -6,7 +6,7 @@ import os
 import re
 
 from conftest import ROOT
-from hipcc_support import kernel_resources, needs_hipcc
+from hipcc_support import assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc
 
 WAVES, SLICE_MAX, TILE = 4, 2048, 32                  # tests/test_tsne.py ties the header's constants to the module
 # kernel -> (instantiations, static LDS bytes per block, waves per SIMD at least)
@@ -30,12 +30,11 @@ def test_tsne_kernels_use_no_scratch_and_the_lds_the_design_states():
     assert len(kernels) == sum(count for count, _, _ in KERNELS.values()), sorted(kernels)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for want, (count, lds, occupancy) in KERNELS.items():
-        names = [k for k in kernels if re.search(rf"\d{want}(E|I)", k)]
+        names = kernel_instances(kernels, want)
         assert len(names) == count, (want, sorted(kernels))
         for name in names:
             r = kernels[name]
-            assert r["scratch"] == 0 and r.get("spill", 0) == 0, (name, r)
-            assert r["occupancy"] >= occupancy, (name, r)
+            assert_no_scratch(r, name, waves=occupancy)
             assert r["lds"] == lds, (name, r)
         assert re.search(rf"\|\s*`{want}`[^|\n]*\|\s*{lds:,}\s*\|", design), f"DESIGN.md does not state {lds:,} bytes of LDS for {want}"
     assert KERNELS["tsne_pair_kernel"][1] <= 32 * 1024      # two blocks a CU beside each other with room to spare

@@ -12,7 +12,7 @@ import pytest
 
 import vad_ref
 from conftest import ROOT
-from hipcc_support import host_program, needs_host_cxx
+from hipcc_support import header_constants, host_program, needs_host_cxx
 
 P = 0x1000          # a pointer that is never followed: every call here fails its argument checks first
 NAN = float("nan")
@@ -154,7 +154,7 @@ def test_module_restates_the_header_constants_and_refuses_the_cpu():
     import xvector_amd
     from xvector_amd import hip, vad
     hdr = open(os.path.join(ROOT, "include", "xvec_vad.h")).read()
-    consts = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define XVEC_(\w+) (\d+)", hdr)}
+    consts = header_constants("xvec_vad.h", "XVEC_")
     assert consts == {"VAD_LANES": vad.LANES, "VAD_MAX_CHANNELS": vad.MAX_CHANNELS, "CMVN_MAX_WINDOW": vad.MAX_WINDOW,
                       "CMVN_TILE_MAX": vad.TILE_MAX, "CMVN_TILE_MIN": vad.TILE_MIN, "CMVN_GROUP_MIN": vad.GROUP_MIN,
                       "CMVN_LDS_BYTES": vad.LDS_BYTES}

@@ -7,7 +7,7 @@ import os
 import re
 
 from conftest import ROOT
-from hipcc_support import kernel_resources, needs_hipcc
+from hipcc_support import assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc
 
 LANES, TILE_MAX, LDS_BYTES = 256, 256, 61440          # tests/test_vad.py ties the module's copies to the header
 WAVES = LANES // 64
@@ -25,11 +25,10 @@ def test_vad_kernels_use_no_scratch_and_the_lds_the_design_states():
     assert len(kernels) == len(KERNELS), sorted(kernels)
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for want, lds in KERNELS.items():
-        names = [k for k in kernels if re.search(rf"\d{want}E", k)]
+        names = kernel_instances(kernels, want)
         assert len(names) == 1, (want, sorted(kernels))
         r = kernels[names[0]]
-        assert r["scratch"] == 0 and r.get("spill", 0) == 0, (want, r)
-        assert r["occupancy"] >= 4, (want, r)
+        assert_no_scratch(r, want, waves=4)
         assert r["lds"] == lds, (want, r)
         assert re.search(rf"\|\s*`{want}`[^|\n]*\|\s*{lds:,}\s*\|", design), f"DESIGN.md does not state {lds:,} bytes of LDS for {want}"
     total = KERNELS["cmvn_select_kernel"] + LDS_BYTES

@@ -4,16 +4,11 @@ them over both buffers and all twelve (product, plane) blocks as the kernel does
 and checks that the image is a bijection that hands every lane its MFMA operand, and that no store and no read instruction
 has two lanes of one service group on one bank (MI355X: ds_write_b64 is served in 4 groups of 16 consecutive lanes with 32
 banks of 4 bytes, ds_read_b128 in the 4 groups below with 64 banks).  No GPU, no HIP library."""
-import os
-import shutil
-import subprocess
-
 import pytest
 
-from conftest import ROOT
+from hipcc_support import host_program, needs_host_cxx
 
-CXX = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-pytestmark = pytest.mark.skipif(CXX is None, reason="needs a C++ compiler")
+pytestmark = needs_host_cxx
 
 # lanes served together by ds_read_b128
 READ_GROUPS = [[0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27],
@@ -24,15 +19,8 @@ WRITE_GROUPS = [list(range(16 * j, 16 * j + 16)) for j in range(16)]       # per
 
 @pytest.fixture(scope="module")
 def maps(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("wino_s3_lds_map") / "dump")
-    src = os.path.join(ROOT, "tests", "abi", "wino_s3_lds_map_dump.cpp")
-    inc = os.path.join(ROOT, "speaker-recognition-x-vectors_amd", "csrc")
-    out = subprocess.run([CXX, "-std=c++17", "-O1", "-Wall", "-I", inc, src, "-o", exe], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0, out.stderr[-2000:]
-    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert out.returncode == 0, out.stderr[-500:]
     m = {"st": {}, "rd": {}}
-    for line in out.stdout.splitlines():
+    for line in host_program("wino_s3_lds_map_dump", tmp_path_factory.mktemp("wino_s3_lds_map")).output().splitlines():
         f = line.split()
         if f[0] == "const":
             m["k"], m["pairs"], m["plane"], m["stage"] = map(int, f[1:])

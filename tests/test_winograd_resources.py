@@ -4,7 +4,7 @@ of (64 pairs + 128 channels) x 32 floats, the block's epilogue constants and two
 two blocks per CU."""
 import os
 
-from hipcc_support import CSRC, kernel_resources, needs_hipcc_and_make
+from hipcc_support import CSRC, assert_no_scratch, kernel_instances, kernel_resources, needs_hipcc_and_make
 
 PLANNED_LDS = (2 * (64 + 128) * 32 + 3 * 128 + 2 * 2 * 64) * 4 + 2 * 8
 
@@ -12,11 +12,10 @@ PLANNED_LDS = (2 * (64 + 128) * 32 + 3 * 128 + 2 * 2 * 64) * 4 + 2 * 8
 @needs_hipcc_and_make
 def test_winograd_kernel_resources():
     kernels = kernel_resources("tdnn_wino.hip")
-    assert len(kernels) == 1 and "tdnn_wino_kernel" in next(iter(kernels)), kernels
+    assert len(kernel_instances(kernels, "tdnn_wino_kernel")) == len(kernels) == 1, kernels
     r = next(iter(kernels.values()))
-    assert r["scratch"] == 0 and r.get("spill", 0) == 0, r
+    assert_no_scratch(r, "tdnn_wino_kernel", waves=2)
     assert r["vgprs"] + r.get("agprs", 0) <= 256, r
-    assert r["occupancy"] >= 2, r
     # dynamic LDS: the launch size the kernel file declares is the planned one, and two blocks fit a CU's 160 KiB
     src = open(os.path.join(CSRC, "tdnn_wino.hip")).read()
     assert "kLdsBytes = (2 * kStage + kConst + 2 * kTbl) * 4 + 2 * 8" in src
