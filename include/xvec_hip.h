@@ -253,6 +253,12 @@ enum {
     XVEC_KERNEL_FIRST = 3    /* xvec::first::tdnn_first_kernel / first3::tdnn_first3_kernel  layer 1 of the bf16 / bf16x3 path, streaming (csrc/tdnn_first.hip) */
 };
 int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n);
+/* Threads per block and blocks of the LAST launch of each frame-level layer: threads[0..4], blocks[0..4], *n = 5 (0, 0: not
+ * launched yet, or a kernel outside the 128x128 family: XVEC_KERNEL_PP / _FIRST).  Tells the two tilings of the Winograd
+ * bf16_split3 form apart: 256 threads = 64 pairs x 128 channels, two blocks per CU (csrc/tdnn_wino_s3.hip); 512 threads = 64
+ * pairs x 256 channels, one block per CU (csrc/tdnn_wino_s3w.hip: widths that are a multiple of 256, unless
+ * XVEC_BLOCKS_PER_CU=2 at xvec_create asks for the old grid).  Both give the same bits. */
+int xvec_get_tdnn_launch(const xvec_handle* h, int* threads, int* blocks, int* n);
 /* Which arithmetic form the LAST launch of each frame-level layer used: forms[0..4], *n = 5.  XVEC_FORM_WINOGRAD_F23: an fp32
  * layer with three equally spaced taps (layers 2 and 3 of the reference) as Winograd F(2,3) along time -- four products for
  * two output frames instead of six -- with either operand scheme: fp32 (csrc/tdnn_wino.hip) or bf16_split3 at large batches

@@ -144,10 +144,12 @@ __device__ __forceinline__ void first_utterance(const TdnnArgs& a, Ctx& cx) {
 // hipcc's instruction order inside the bf16_split3 K loop.  Part 1: logical block id -> channel column (returned: its first
 // channel n0) and range of 32-pair groups (cx.g_s, cx.g_end); the lane roles that do not depend on the kernel's LDS layout
 // (c = tid & c_mask: the 16-byte column set_rows addresses).
+// BN: channels of the block's tile (kBN; tdnn_wino_s3w.hip: 256 on eight waves).
+template <int BN = kBN>
 __device__ __forceinline__ int block_setup(const TdnnArgs& a, int c_mask, Ctx& cx, Lane& ln) {
     // the n_tiles columns of one range are consecutive ids on one XCD
     const int lid = xcd_remap(blockIdx.x, gridDim.x);
-    const int n0 = (lid % a.n_tiles) * kBN;
+    const int n0 = (lid % a.n_tiles) * BN;
     int64_t g_begin, g_end;
     group_range(a, lid / a.n_tiles, g_begin, g_end);
     const int tid = threadIdx.x;
@@ -167,12 +169,13 @@ __device__ __forceinline__ int block_setup(const TdnnArgs& a, int c_mask, Ctx& c
 // with that tile's rows set.  cx.drb is a constant of the launch and is set HERE, once: assigned again by every set_rows it was
 // a loop-carried value that hipcc kept in a vector register, and every input-row load of tdnn_wino_kernel's K loop that adds
 // it to its scalar offset was wrapped in a v_readfirstlane / v_cmp_eq / s_and_saveexec loop (34 of them, 4-6 % of the kernel).
+template <int BN = kBN>
 __device__ __forceinline__ void stream_start(const TdnnArgs& a, int n0, float* cst, int* tbl, int64_t* tblh, Ctx& cx, const Lane& ln) {
     const int tid = threadIdx.x;
-    if (tid < kBN) {
+    if (tid < BN) {
         cst[tid] = a.bias[n0 + tid];
-        cst[kBN + tid] = a.scale[n0 + tid];
-        cst[2 * kBN + tid] = a.shift[n0 + tid];
+        cst[BN + tid] = a.scale[n0 + tid];
+        cst[2 * BN + tid] = a.shift[n0 + tid];
     }
     cx.q0 = cx.g_s * 32;
     first_utterance(a, cx);
@@ -187,14 +190,14 @@ __device__ __forceinline__ void stream_start(const TdnnArgs& a, int n0, float* c
 // Epilogue of a tile of G pair groups (tp: its row-table parity; acc<k>_<i>: product k of group i): y(t) = M0 + M1 + M2,
 // y(t+d) = M1 - M2 - M3, then bias + ReLU + folded BatchNorm (tdnn_layer.py:30-39), stored to the rows set_rows tabled (-1:
 // none).  Accumulator element e of lane (r, h): pair = (e&3) + 8*(e>>2) + 4*h of the group, channel = r.
-template <int G>
+template <int G, int BN = kBN>
 __device__ __forceinline__ void epilogue(const TdnnArgs& a, const float* cst, const int* tbl, const int64_t* tblh, const Lane& ln,
                                          int n0, int tp, const f32x16& acc0_0, const f32x16& acc1_0, const f32x16& acc2_0,
                                          const f32x16& acc3_0, const f32x16& acc0_1, const f32x16& acc1_1, const f32x16& acc2_1,
                                          const f32x16& acc3_1) {
     const int h = ln.h, col = ln.col;
     cst += col - n0;
-    const float bi = cst[0], sc = cst[kBN], sh = cst[2 * kBN];
+    const float bi = cst[0], sc = cst[BN], sh = cst[2 * BN];
     // the tile's base row: the same in every lane (set_rows wrote it to LDS)
     const int64_t ob = (int64_t)uniform64((unsigned long long)tblh[tp]);
     const __amdgpu_buffer_rsrc_t yrsrc = make_rsrc(static_cast<float*>(a.Y) + ob * a.ldy);

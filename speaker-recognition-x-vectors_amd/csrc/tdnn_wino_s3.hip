@@ -16,6 +16,7 @@
 //   = 341 B per MFMA (the direct port of tdnn_wino.hip's tile: 427).
 #include "tdnn_wino_rows.h"
 #include "wino_s3_lds_map.h"
+#include "wino_s3_tile.h"
 
 namespace xvec {
 namespace wino {
@@ -24,114 +25,21 @@ static_assert(kS3Pairs == kPairs, "wino_s3_lds_map.h: kS3K, kS3Plane, kS3Stage a
 constexpr int kS3Const = kConst * 4;                      // bias | scale | shift of the tile's channels, bytes
 constexpr int kS3LdsBytes = 2 * kS3Stage + kS3Const + 2 * kTbl * 4 + 2 * 8;   // + row tables, per parity the base row
 
-// Step the load stream to the next chunk; after a tile's last chunk, to chunk 0 of the block's next tile.  Past the block's
-// last chunk it stays put (the look-ahead re-reads that chunk; the data is never used).
-__device__ __forceinline__ void s3_advance(const TdnnArgs& a, Ctx& cx, const Lane& ln, int* tbl, int64_t* tblh, int n_chunks) {
-    if (cx.kc + 1 < n_chunks) {
-        ++cx.kc;
-    } else {
-        const int64_t g_rem = cx.g_end - cx.g_s;
-        const int64_t g_next = cx.g_s + (g_rem < 2 ? g_rem : 2);
-        if (g_next < cx.g_end) {
-            cx.g_s = g_next;
-            cx.q0 = g_next * 32;
-            cx.lp ^= 1;
-            set_rows(a, cx, ln, tbl, tblh);
-            cx.kc = 0;
-        }
-    }
-}
-
-struct S3Stage {
-    float4 x0, x1, x2, x3;
-};
-
-// the four input rows of this thread's pair (group `grp`: 0 -> set_rows' pair q0 + r0, 1 -> q0 + r0 + 32) at the chunk cx
-// points at.  Rows x1, x2 are x0 + d, x0 + 2d: the scalar offset carries the shift; x3 has a lane offset of its own.
-__device__ __forceinline__ void s3_gld(const Ctx& cx, bool grp, S3Stage& s) {
-    const int xo0 = grp ? cx.x01 : cx.x00, xo3 = grp ? cx.x31 : cx.x30;
-    const int so = cx.kc * (kS3K * 4);
-    s.x0 = buf_load16(cx.xrsrc, xo0, so);
-    s.x1 = buf_load16(cx.xrsrc, xo0, so + cx.drb);
-    s.x2 = buf_load16(cx.xrsrc, xo0, so + 2 * cx.drb);
-    s.x3 = buf_load16(cx.xrsrc, xo3, so);
-}
-
-// V_k = x0-x2 | x1+x2 | x2-x1 | x1-x3 in fp32, each split into hi | mid | lo -> LDS buffer B (st: this thread's 8 bytes)
-__device__ __forceinline__ void s3_vstore(char* B, int st, const S3Stage& s) {
-    const float4 v[4] = {
-        make_float4(s.x0.x - s.x2.x, s.x0.y - s.x2.y, s.x0.z - s.x2.z, s.x0.w - s.x2.w),
-        make_float4(s.x1.x + s.x2.x, s.x1.y + s.x2.y, s.x1.z + s.x2.z, s.x1.w + s.x2.w),
-        make_float4(s.x2.x - s.x1.x, s.x2.y - s.x1.y, s.x2.z - s.x1.z, s.x2.w - s.x1.w),
-        make_float4(s.x1.x - s.x3.x, s.x1.y - s.x3.y, s.x1.z - s.x3.z, s.x1.w - s.x3.w)};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        u32x2 hi, mid, lo;
-        split3(v[k], hi, mid, lo);
-        *reinterpret_cast<u32x2*>(B + (3 * k + 0) * kS3Plane + st) = hi;
-        *reinterpret_cast<u32x2*>(B + (3 * k + 1) * kS3Plane + st) = mid;
-        *reinterpret_cast<u32x2*>(B + (3 * k + 2) * kS3Plane + st) = lo;
-    }
-}
-
-// The U-plane fragments (hi | mid | lo) of the four products of a chunk, this wave's column, and the A fragments of one product
-// (a: pair group 0, b: pair group 1).  Named members, not arrays: the K loop below is pinned with scheduling barriers.
-struct S3U {
-    float4 w00, w01, w02, w10, w11, w12, w20, w21, w22, w30, w31, w32;
-};
-struct S3Frag {
-    float4 a0, a1, a2, b0, b1, b2;
-};
-
-// one MFMA of s3_mfma6's six (tdnn_common.h: the same products in the same order into the same accumulator)
-#define WS3_MF(acc_, x_, w_) \
-    acc_ = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, x_), __builtin_bit_cast(bf16x8, w_), acc_, 0, 0, 0);
-// one A fragment of product kn_ of the chunk in buffer B_: plane pl_ of pair group g_ (0: ln.a_rd, 1: a_rd1)
-#define WS3_RD(dst_, B_, kn_, pl_, g_) \
-    dst_ = *reinterpret_cast<const float4*>((B_) + (3 * (kn_) + (pl_)) * kS3Plane + ((g_) ? a_rd1 : ln.a_rd));
-// the three U fragments of product K_ of chunk it + 1; the stream wraps to chunk 0 past the tile's last chunk (the next tile
-// of the block is in the same channel column)
-#define WS3_ULD(K_)                                                                   \
-    {                                                                                 \
-        int c_ = it + 1;                                                              \
-        if (c_ >= n_chunks) c_ -= n_chunks;                                           \
-        u.w##K_##0 = buf_load16(ursrc, ln.b_rd, ((4 * c_ + K_) * 3 + 0) * 1024);      \
-        u.w##K_##1 = buf_load16(ursrc, ln.b_rd, ((4 * c_ + K_) * 3 + 1) * 1024);      \
-        u.w##K_##2 = buf_load16(ursrc, ln.b_rd, ((4 * c_ + K_) * 3 + 2) * 1024);      \
-    }
-// Product K_ of a tile of two pair groups.  The two fragment sets roll: pair group 1's fragments of this product are read
-// from S behind the first MFMAs of pair group 0, pair group 0's of product kn_ (of the chunk in buffer NB_) behind the first
-// MFMAs of pair group 1 -- each into registers whose last MFMA has just issued, ONE ds_read_b128 per MFMA gap (MI355X: up to
-// two per gap are free), in the order the MFMAs take them (lo | mid | hi: the waits are counted), each five MFMAs ahead of
-// its use.  24 fragment registers, as without look-ahead.
-// BAR_: the chunk's barrier, between the two pair groups of product 3 (see the loop).
-#define WS3_PRODUCT2(K_, NB_, kn_, BAR_)                                                                   \
-    {                                                                                                      \
-        WS3_MF(acc##K_##_0, f.a2, u.w##K_##0) WS3_RD(f.b2, S, K_, 2, 1) SB();                              \
-        WS3_MF(acc##K_##_0, f.a1, u.w##K_##1) WS3_RD(f.b1, S, K_, 1, 1) SB();                              \
-        WS3_MF(acc##K_##_0, f.a0, u.w##K_##2) WS3_RD(f.b0, S, K_, 0, 1) SB();                              \
-        WS3_MF(acc##K_##_0, f.a1, u.w##K_##0) WS3_MF(acc##K_##_0, f.a0, u.w##K_##1) WS3_MF(acc##K_##_0, f.a0, u.w##K_##0) SB(); \
-        BAR_                                                                                               \
-        WS3_MF(acc##K_##_1, f.b2, u.w##K_##0) WS3_RD(f.a2, NB_, kn_, 2, 0) SB();                           \
-        WS3_MF(acc##K_##_1, f.b1, u.w##K_##1) WS3_RD(f.a1, NB_, kn_, 1, 0) SB();                           \
-        WS3_MF(acc##K_##_1, f.b0, u.w##K_##2) WS3_RD(f.a0, NB_, kn_, 0, 0) SB();                           \
-        WS3_MF(acc##K_##_1, f.b1, u.w##K_##0) WS3_MF(acc##K_##_1, f.b0, u.w##K_##1) WS3_MF(acc##K_##_1, f.b0, u.w##K_##0) SB(); \
-        WS3_ULD(K_)                                                                                        \
-        SB();                                                                                              \
-    }
-// Product K_ of a tile of one pair group (a block's odd last tile): the second set's registers are free, so the fragments of
-// product kn_ go to set N_ while this product runs on set C_ (a | b, alternating; product 0 runs on a).  BAR_ comes first:
-// product 3's own fragments were read a product ago, and the next chunk's must be read behind it.
-#define WS3_PRODUCT1(K_, C_, N_, NB_, kn_, BAR_)                                                           \
-    {                                                                                                      \
-        BAR_                                                                                               \
-        WS3_MF(acc##K_##_0, f.C_##2, u.w##K_##0) WS3_RD(f.N_##2, NB_, kn_, 2, 0) SB();                     \
-        WS3_MF(acc##K_##_0, f.C_##1, u.w##K_##1) WS3_RD(f.N_##1, NB_, kn_, 1, 0) SB();                     \
-        WS3_MF(acc##K_##_0, f.C_##0, u.w##K_##2) WS3_RD(f.N_##0, NB_, kn_, 0, 0) SB();                     \
-        WS3_MF(acc##K_##_0, f.C_##1, u.w##K_##0) WS3_MF(acc##K_##_0, f.C_##0, u.w##K_##1) WS3_MF(acc##K_##_0, f.C_##0, u.w##K_##0) SB(); \
-        WS3_ULD(K_)                                                                                        \
-        SB();                                                                                              \
-    }
+#ifdef XVEC_KNOCK
+// Timing-only knock-outs, compile time (-DXVEC_KNOCK=mask, the convention and the bit space of tdnn_pp16.hip; results are
+// garbage).  A knocked head does no input-row loads, no V formation, no split and no LDS stores; the products then run on what
+// the LDS buffers hold (the block prologue fills both with real V planes).  Everything else stays: the step of the load stream
+// (its row tables address the epilogue's stores), barriers, U loads, fragment reads, MFMAs, epilogue.  No address changes.
+//   bit 17: the blocks of ODD column tiles: every head knocked (half the head work per MFMA of the launch, but only in half
+//           the blocks: the launch ends with the unchanged ones)
+//   bit 18: EVERY block: the head of every odd chunk knocked (half the head work per MFMA in every block, with no cost of
+//           sharing it: the upper bound on a 256-channel tile, profiles/wino_s3_wide_bound.txt)
+//   bit 19: EVERY block: every head knocked (what the head costs altogether)
+#define WS3_KNOCK_HEAD ((XVEC_KNOCK & (131072 | 262144 | 524288)) != 0)
+#define WS3_KNOCK_MODE ((XVEC_KNOCK & 524288) ? 3 : (XVEC_KNOCK & 262144) ? 2 : 1)
+#else
+#define WS3_KNOCK_HEAD 0
+#endif
 
 // One tile of G pair groups x 128 channels; tp = its row-table parity.  On entry chunk 0 of the tile is in LDS buffer 0, its
 // U planes are in u (or on their way), pair group 0's A fragments of its product 0 in f.a*, and the staging registers hold
@@ -155,7 +63,8 @@ struct S3Frag {
 // so a U fragment has a whole chunk (48 MFMAs) to arrive and the queue is never drained.  The counts are hipcc's own (it sees
 // every load here); the block prologue requests in the same order, so the first chunk meets the same queue.  A tile's first
 // head may find the previous epilogue's stores behind the loads: its wait then covers a few entries more, never fewer.
-template <int G>
+// KN: the knock-out build's tiles (WS3_KNOCK_HEAD; 1: no head, 2: no head in odd chunks); the shipped build has KN = 0 only.
+template <int G, int KN = 0>
 __device__ __forceinline__ void s3_tile(const TdnnArgs& a, char* lds, int* tbl, int64_t* tblh, Ctx& cx, const Lane& ln,
                                         int a_rd1, S3Stage& st, S3U& u, S3Frag& f, __amdgpu_buffer_rsrc_t ursrc, int n0,
                                         int tp, int n_chunks) {
@@ -168,27 +77,12 @@ __device__ __forceinline__ void s3_tile(const TdnnArgs& a, char* lds, int* tbl, 
     }
     // ---- K chunks: chunk it in buffer it & 1 (n_chunks is even, so every tile starts in buffer 0)
     for (int it = 0; it < n_chunks; ++it) {
-        const char* S = lds + (it & 1) * kS3Stage;
-        char* Sn = lds + ((it & 1) ^ 1) * kS3Stage;
-        // chunk it + 1 -> the other buffer (free: every wave passed the barrier behind its last read of chunk it - 1),
-        // then the staging registers receive the chunk after it
-        s3_vstore(Sn, ln.st_off, st);
-        s3_advance(a, cx, ln, tbl, tblh, n_chunks);
-        s3_gld(cx, grp, st);
-        SB();
-        if constexpr (G > 1) {
-            WS3_PRODUCT2(0, S, 1, )
-            WS3_PRODUCT2(1, S, 2, )
-            WS3_PRODUCT2(2, S, 3, )
-            WS3_PRODUCT2(3, Sn, 0, __syncthreads(); SB();)
-        } else {
-            WS3_PRODUCT1(0, a, b, S, 1, )
-            WS3_PRODUCT1(1, b, a, S, 2, )
-            WS3_PRODUCT1(2, a, b, S, 3, )
-            WS3_PRODUCT1(3, b, a, Sn, 0, __syncthreads(); SB();)
+        WS3_CHUNK(KN != 1, 1)
+        if constexpr (KN == 2) {       // n_chunks is even
+            ++it;
+            WS3_CHUNK(false, 1)
         }
     }
-
     epilogue<G>(a, reinterpret_cast<const float*>(lds + 2 * kS3Stage), tbl, tblh, ln, n0, tp, acc0_0, acc1_0, acc2_0, acc3_0, acc0_1,
                 acc1_1, acc2_1, acc3_1);
     // With two chunks per tile the load stream reaches the tile after the next one at the head of the next tile's chunk 0:
@@ -197,8 +91,16 @@ __device__ __forceinline__ void s3_tile(const TdnnArgs& a, char* lds, int* tbl, 
     if (n_chunks == 2) __syncthreads();
 }
 
+#if WS3_KNOCK_HEAD
+// Knock-out build only: a block's whole run as a function, KN = without head work -- a code path of its own from the first
+// instruction on, so that the two forms share no registers (as two branches of one body hipcc spilled 197 of them).
+template <int KN>
+__device__ __forceinline__ void s3_block(const TdnnArgs& a, char* lds) {
+#else
 __global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const TdnnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    constexpr int KN = 0;
+#endif
     float* cst = reinterpret_cast<float*>(lds + 2 * kS3Stage);
     int* tbl = reinterpret_cast<int*>(cst + kConst);
     int64_t* tblh = reinterpret_cast<int64_t*>(tbl + 2 * kTbl);
@@ -239,14 +141,25 @@ __global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const TdnnArgs a) 
         WS3_ULD(0) WS3_ULD(1) WS3_ULD(2) WS3_ULD(3)
     }
     SB();
+    if constexpr (KN) s3_vstore(lds + kS3Stage, ln.st_off, st);      // chunk 1 -> buffer 1: the K loop will not write it
     __syncthreads();
     WS3_RD(f.a2, lds, 0, 2, 0) WS3_RD(f.a1, lds, 0, 1, 0) WS3_RD(f.a0, lds, 0, 0, 0)
 
     int64_t g = g_begin;
     int tp = 0;
-    for (; g + 2 <= g_end; g += 2, tp ^= 1) s3_tile<2>(a, lds, tbl, tblh, cx, ln, a_rd1, st, u, f, ursrc, n0, tp, n_chunks);
-    if (g < g_end) s3_tile<1>(a, lds, tbl, tblh, cx, ln, a_rd1, st, u, f, ursrc, n0, tp, n_chunks);
+    for (; g + 2 <= g_end; g += 2, tp ^= 1) s3_tile<2, KN>(a, lds, tbl, tblh, cx, ln, a_rd1, st, u, f, ursrc, n0, tp, n_chunks);
+    if (g < g_end) s3_tile<1, KN>(a, lds, tbl, tblh, cx, ln, a_rd1, st, u, f, ursrc, n0, tp, n_chunks);
 }
+
+#if WS3_KNOCK_HEAD
+__global__ __launch_bounds__(256, 2) void tdnn_wino_s3_kernel(const TdnnArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char lds[];
+    if constexpr (WS3_KNOCK_MODE > 1) s3_block<(WS3_KNOCK_MODE == 2 ? 2 : 1)>(a, lds);
+    else if ((xcd_remap(blockIdx.x, gridDim.x) % a.n_tiles) & 1) s3_block<1>(a, lds);      // block_setup: the block's column tile
+    else s3_block<0>(a, lds);
+}
+#endif
+#undef WS3_CHUNK
 #undef WS3_PRODUCT2
 #undef WS3_PRODUCT1
 #undef WS3_ULD

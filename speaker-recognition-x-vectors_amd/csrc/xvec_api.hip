@@ -128,6 +128,8 @@ struct xvec_handle {
     int num_cu;
     int split3_blocks_cu;              // blocks of tdnn_split3_kernel the device holds per CU, at most 3 (asked once, xvec_create)
     Policy pol;
+    bool wino_s3w_fits;                // the device holds one 512-thread block of tdnn_wino_s3w_kernel per CU (asked once, xvec_create)
+    int last_threads[XVEC_NUM_TDNN], last_blocks[XVEC_NUM_TDNN];   // block size and grid of that launch, where the planner sizes the grid (xvec_get_tdnn_launch)
     int last_kernel[XVEC_NUM_TDNN];    // XVEC_KERNEL_* the last launch of each frame-level layer went to (xvec_get_dispatch)
     int last_form[XVEC_NUM_TDNN];      // XVEC_FORM_* of that launch (xvec_get_tdnn_form)
     int last_operands[XVEC_NUM_TDNN];  // XVEC_OPERANDS_* of that launch (xvec_get_tdnn_operands)
@@ -295,7 +297,7 @@ struct LayerCall {
     int64_t rows_out;
 };
 
-enum class Launch { kDirect, kPp16, kFirst, kFirst3, kSplit3, kWino, kWinoS3 };
+enum class Launch { kDirect, kPp16, kFirst, kFirst3, kSplit3, kWino, kWinoS3, kWinoS3W };
 
 // What plan_layer chose for a call: the kernel, its complete arguments, and what the launch reports.
 struct LayerPlan {
@@ -400,6 +402,13 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
             lp.launch = Launch::kWinoS3;
             lp.operands = XVEC_OPERANDS_BF16_SPLIT3;
             a.Wf = h->Wu3[l];
+            // ... on tiles of 256 channels, eight waves, one block per CU (tdnn_wino_s3w.hip: half the staging work per MFMA,
+            // the same bits) where the width allows and the device holds the block; XVEC_BLOCKS_PER_CU=2 keeps the old grid
+            if (h->wino_s3w_fits && h->pol.blocks_per_cu <= 1 && tdnn_wino_s3w_applicable(g, c.ldx)) {
+                lp.launch = Launch::kWinoS3W;
+                a.n_tiles = g.n_pad / 256;
+                persistent_grid(h, 1, a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
+            }
         }
     }
     const bool rows32 = lp.mode.src == Src::kRows32;
@@ -435,8 +444,13 @@ int launch_layer(xvec_handle* h, const LayerPlan& lp, hipStream_t s) {
         case Launch::kSplit3: HIP_TRY(launch_tdnn_split3(lp.a, pool, s)); break;
         case Launch::kWino: HIP_TRY(launch_tdnn_wino(lp.a, s)); break;
         case Launch::kWinoS3: HIP_TRY(launch_tdnn_wino_s3(lp.a, s)); break;
+        case Launch::kWinoS3W: HIP_TRY(launch_tdnn_wino_s3w(lp.a, s)); break;
         case Launch::kDirect: HIP_TRY(launch_tdnn(lp.a, lp.mode, s)); break;
     }
+    // (the 128x128 family and its 256-channel Winograd tiling; the streaming and ping-pong kernels keep their own block shapes)
+    const bool sized = lp.launch != Launch::kFirst && lp.launch != Launch::kFirst3 && lp.launch != Launch::kPp16;
+    h->last_threads[lp.layer] = lp.launch == Launch::kWinoS3W ? 512 : sized ? 256 : 0;
+    h->last_blocks[lp.layer] = sized ? lp.a.blocks_per_col * lp.a.n_tiles : 0;
     h->last_kernel[lp.layer] = lp.kernel;
     h->last_form[lp.layer] = lp.form;
     h->last_operands[lp.layer] = lp.operands;
@@ -769,6 +783,13 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
         return g_err.fail(XVEC_ERR_HIP, "occupancy query of tdnn_split3_kernel failed: %s", hipGetErrorString(e));
     }
     h->split3_blocks_cu = std::max(1, std::min(3, s3_blocks));
+    // ... and the eight-wave Winograd split3 block only where one fits
+    int s3w_blocks = 0;
+    if (hipError_t e = tdnn_wino_s3w_max_blocks_per_cu(&s3w_blocks); e != hipSuccess) {
+        delete h;
+        return g_err.fail(XVEC_ERR_HIP, "occupancy query of tdnn_wino_s3w_kernel failed: %s", hipGetErrorString(e));
+    }
+    h->wino_s3w_fits = s3w_blocks >= 1;
     h->cin_pad = round_up(cfg->input_size, 4);
     fill_geometry(h, h->geo, 2 * kBK);
     fill_geometry(h, h->geo16, 4 * kBK);
@@ -1224,6 +1245,16 @@ int xvec_get_affine_dispatch(const xvec_handle* h, int* forms, int* ranges, int*
 int xvec_get_dispatch(const xvec_handle* h, int* kernels, int* n) {
     if (!h || !kernels || !n) return g_err.fail(XVEC_ERR_ARG, "null argument");
     for (int i = 0; i < XVEC_NUM_TDNN; ++i) kernels[i] = h->last_kernel[i];
+    *n = XVEC_NUM_TDNN;
+    return XVEC_OK;
+}
+
+int xvec_get_tdnn_launch(const xvec_handle* h, int* threads, int* blocks, int* n) {
+    if (!h || !threads || !blocks || !n) return g_err.fail(XVEC_ERR_ARG, "null argument");
+    for (int i = 0; i < XVEC_NUM_TDNN; ++i) {
+        threads[i] = h->last_threads[i];
+        blocks[i] = h->last_blocks[i];
+    }
     *n = XVEC_NUM_TDNN;
     return XVEC_OK;
 }

@@ -165,6 +165,12 @@ hipError_t launch_tdnn_wino(const TdnnArgs& a, hipStream_t s);
 // Wf = the same U_k as hi | mid | lo bf16 planes (launch_pack_wino_split3), W is not read
 bool tdnn_wino_s3_applicable(const TdnnGeom& g, int ldx);
 hipError_t launch_tdnn_wino_s3(const TdnnArgs& a, hipStream_t s);
+// ... the same on tiles of 64 pairs x 256 channels, eight waves, ONE block per CU (tdnn_wino_s3w.hip): the same arguments with
+// n_tiles = n_pad / 256 and the grid sized for one block per CU; needs n_pad % 256 == 0 and at least four 16-wide chunks per
+// product.  Every output is the same bits as launch_tdnn_wino_s3's.  _max_blocks_per_cu: what the device says it holds.
+bool tdnn_wino_s3w_applicable(const TdnnGeom& g, int ldx);
+hipError_t tdnn_wino_s3w_max_blocks_per_cu(int* blocks);
+hipError_t launch_tdnn_wino_s3w(const TdnnArgs& a, hipStream_t s);
 // U_0 = W_0, U_1 = (W_0+W_1+W_2)/2, U_2 = (W_0-W_1+W_2)/2, U_3 = W_2 of a 3-tap layer (fp64, rounded once) -> Wu [n_pad][4*kpt_pad]
 hipError_t launch_pack_wino(const float* W, const TdnnGeom& geo, float* Wu, hipStream_t s);
 // ... the same U_k (fp64, split into three bf16 pieces) for tdnn_wino_s3.hip: 1 KiB fragment-major blocks

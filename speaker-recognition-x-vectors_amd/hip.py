@@ -123,6 +123,7 @@ _SIGS = {
     "xvec_set_profiling": (C.c_int, [_vp, C.c_int]),
     "xvec_get_timings": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "xvec_get_dispatch": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "xvec_get_tdnn_launch": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_get_tdnn_form": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_get_tdnn_operands": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "xvec_get_affine_dispatch": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),

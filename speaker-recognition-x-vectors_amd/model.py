@@ -702,6 +702,16 @@ class XVectorModel(nn.Module):
         _hip.check(_hip.lib.xvec_get_dispatch(eng.h, buf, C.byref(n)))
         return [_hip.KERNEL_NAMES.get(int(buf[i])) for i in range(n.value)]
 
+    def last_launches(self, device=None) -> list:
+        """(threads per block, blocks) of the last launch of each frame-level layer; (0, 0) where the library does not size the
+        grid.  512 threads: the Winograd bf16_split3 form on 256-channel tiles (csrc/tdnn_wino_s3w.hip)."""
+        dev = torch.device(device) if device is not None else next(self.parameters()).device
+        eng = self._engine(dev)
+        thr, blk = (C.c_int * 8)(), (C.c_int * 8)()
+        n = C.c_int(0)
+        _hip.check(_hip.lib.xvec_get_tdnn_launch(eng.h, thr, blk, C.byref(n)))
+        return [(int(thr[i]), int(blk[i])) for i in range(n.value)]
+
     def last_forms(self, device=None) -> list:
         """Arithmetic form of the last launch of each frame-level layer: "direct" | "winograd_f23" (fp32 layers with three
         equally spaced taps, csrc/tdnn_wino.hip; XVEC_WINOGRAD=0 at engine creation forces "direct") | "bf16_split3" (fp32
