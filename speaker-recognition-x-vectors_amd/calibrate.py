@@ -26,7 +26,7 @@ import torch
 
 from . import hip as _hip
 from ._device import checker, score_matrix, sized_workspace, stream as _stream
-from .evaluate import TrialList, _class_ids, evaluate_trials
+from .evaluate import TrialList, _class_ids, evaluate_trials, score_vector_or_matrix as _scores, trial_args as _trial_args
 
 __all__ = ["Calibration", "FitResult", "CllrResult", "PavResult", "CalibrationReport", "ScoreCalibrator", "fit_calibration",
            "fit_calibration_all_pairs", "cllr", "cllr_all_pairs", "min_cllr", "pav_segments", "calibration_report", "THREADS",
@@ -121,26 +121,6 @@ def _read(struct, record: torch.Tensor):
 def _workspace(n: int, device, workspace=None) -> torch.Tensor:
     refusal = lambda: ValueError(f"{n} trials: the count must lie in 1 .. 2^31 - 1")
     return sized_workspace(_hip.lib.xvec_calib_workspace_bytes(n), refusal, device, workspace)
-
-
-def _trial_args(s: torch.Tensor, trials, what: str):
-    """(row, col, is_target, n) on the scores' device; `trials` a TrialList, or for a score VECTOR the target flags alone."""
-    if isinstance(trials, TrialList):
-        if len(trials) < 1:
-            raise ValueError(f"{what}: no trials")
-        row, col, tgt = trials.on(s.device)
-        return row, col, tgt, len(trials)
-    tgt = torch.as_tensor(trials).to(device=s.device).ne(0).to(torch.uint8).contiguous()
-    if s.shape[0] != 1 or tgt.dim() != 1 or tgt.numel() != s.shape[1] or tgt.numel() < 1:
-        raise ValueError(f"{what}: target flags alone go with a score vector of their length (a TrialList indexes a matrix)")
-    return None, None, tgt, tgt.numel()
-
-
-def _scores(scores, what: str) -> torch.Tensor:
-    """A device score matrix, or a device score vector as the [1, n] matrix the plain-vector form reads."""
-    if isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dim() == 1 and scores.dtype == torch.float64:
-        scores = scores.reshape(1, -1)
-    return score_matrix(scores, what)
 
 
 def _classes(s: torch.Tensor, row_labels, col_labels, what: str):

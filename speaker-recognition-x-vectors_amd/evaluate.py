@@ -117,6 +117,26 @@ def _workspace(n: int, device) -> torch.Tensor:
     return sized_workspace(_hip.lib.xvec_eval_workspace_bytes(n), refusal, device)
 
 
+def trial_args(s: torch.Tensor, trials, what: str):
+    """(row, col, is_target, n) on the scores' device; `trials` a TrialList, or for a score VECTOR the target flags alone."""
+    if isinstance(trials, TrialList):
+        if len(trials) < 1:
+            raise ValueError(f"{what}: no trials")
+        row, col, tgt = trials.on(s.device)
+        return row, col, tgt, len(trials)
+    tgt = torch.as_tensor(trials).to(device=s.device).ne(0).to(torch.uint8).contiguous()
+    if s.shape[0] != 1 or tgt.dim() != 1 or tgt.numel() != s.shape[1] or tgt.numel() < 1:
+        raise ValueError(f"{what}: target flags alone go with a score vector of their length (a TrialList indexes a matrix)")
+    return None, None, tgt, tgt.numel()
+
+
+def score_vector_or_matrix(scores, what: str) -> torch.Tensor:
+    """A device score matrix, or a device score vector as the [1, n] matrix the plain-vector form reads."""
+    if isinstance(scores, torch.Tensor) and scores.is_cuda and scores.dim() == 1 and scores.dtype == torch.float64:
+        scores = scores.reshape(1, -1)
+    return score_matrix(scores, what)
+
+
 def _read_result(out: torch.Tensor, what: str) -> TrialResult:
     r = _Result.from_buffer_copy(out.cpu().numpy().tobytes())          # the one copy to the host: 80 bytes
     if r.n_bad_index:
@@ -259,6 +279,7 @@ class plda_score_stat_object:
         self.positive_scores_mask = []
         self.negative_scores_mask = []
 
+        self._evaluated = False
         self.eer = 0
         self.eer_th = 0
         self.min_dcf = 0
@@ -317,6 +338,35 @@ class plda_score_stat_object:
         res = evaluate_trials(self._scoremat, self._trials, p_target=0.5)
         self.eer, self.eer_th = res.eer, res.eer_th
         self.min_dcf, self.min_dcf_th = res.min_dcf, res.min_dcf_th
+        self._evaluated = True
+
+    def _scored(self, what, thresholds=False):
+        if self._trials is None:
+            raise RuntimeError(f"{what}: call test_plda first")
+        if thresholds and not self._evaluated:
+            raise RuntimeError(f"{what}: call calc_eer_mindcf first")
+        return self._scoremat, self._trials
+
+    def score_images(self, dtype=torch.uint8):
+        """The six images of the reference's plot_images (plda_score_stat.py:132-192) at the object's own thresholds, on the
+        device, by the reference's names (report.score_images).  Call test_plda and calc_eer_mindcf first."""
+        from . import report
+        s, trials = self._scored("score_images", thresholds=True)
+        return report.score_images(s, trials, self.eer_th, self.min_dcf_th, dtype=dtype)
+
+    def det_curve(self, grid=0):
+        """The error-rate curve of the collected trials (report.det_curve): every distinct score, or thinned to `grid`."""
+        from . import report
+        s, trials = self._scored("det_curve")
+        return report.det_curve(s, trials, grid)
+
+    def write_images(self, writer, step=0):
+        """`writer.add_image(name, image, step)` for the six images in the reference's order: the image half of plot_images,
+        for a TensorBoard SummaryWriter or any object with `add_image`.  The images cross to the host as uint8."""
+        from . import report
+        images = self.score_images()
+        for name in report.IMAGE_NAMES:
+            writer.add_image(name, images[name].cpu(), step)
 
     def plot_images(self, writer):
         raise NotImplementedError("plot_images (TensorBoard images, LDA / PCA / t-SNE scatter plots) is out of scope")

@@ -97,6 +97,12 @@ class _wsb(C.c_size_t):
     tests/test_calibrate.py instead."""
 
 
+class _wsb_report(_wsb):
+    """size_t workspace_bytes of include/xvec_report.h: `_wsb` again, under one more name.  tests/test_calibrate.py lists every
+    (void*, _wsb) pair of the table below as the calibration unit's own; the report unit's answers are held by
+    tests/test_report.py."""
+
+
 _SIGS = {
     "xvec_create": (C.c_int, [C.POINTER(Cfg), C.POINTER(_vp)]),
     "xvec_destroy": (None, [_vp]),
@@ -225,6 +231,18 @@ _SIGS = {
                                             _wsb, _vp]),
     "xvec_calib_min_cllr": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _wsb,
                                       _vp]),
+    # include/xvec_report.h  (the workspace size is spelt _wsb_report: see the class above)
+    "xvec_report_last_error": (C.c_char_p, []),
+    "xvec_report_trial_map": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "xvec_report_range_workspace_bytes": (C.c_size_t, []),
+    "xvec_report_range": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _wsb_report, _vp]),
+    "xvec_report_images": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, C.c_double, C.c_double, C.c_uint32, _i32, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp]),
+    "xvec_report_det_workspace_bytes": (C.c_size_t, [_i64]),
+    "xvec_report_det": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _wsb_report,
+                                  _vp]),
+    "xvec_report_det_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
+                                            _wsb_report, _vp]),
     # include/xvec_train.h
     "xvec_train_last_error": (C.c_char_p, []),
     "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
