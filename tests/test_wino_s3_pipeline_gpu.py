@@ -29,7 +29,7 @@ import torch
 
 import xvector_oracle as oracle
 from conftest import assert_parity, float_params
-from tdnn_support import DEV, make_model, oracle_layer, worst_rel
+from tdnn_support import DEV, make_model, oracle_layer, workspace_rows, worst_rel
 
 pytestmark = pytest.mark.gpu
 WINO_LAYERS = (1, 2)          # time_context_layers.1 / .2: contexts [-2, 0, 2] and [-3, 0, 3]
@@ -152,17 +152,11 @@ def test_ragged_batch(synth, hid):
     off = np.concatenate([[0], np.cumsum([n - 14 for n in lens])])       # compact rows of layer 3's output
 
     def layer3_rows():
-        """Layer 3's rows of the ragged batch as the whole path left them in the workspace (it writes activation buffer A:
-        layer l goes to buffer l & 1; the pooled mode runs no segment layer, which would reuse it)."""
-        eng = m._engine(torch.device(DEV))
-        eng.ensure_workspace(sum(lens), len(lens))
-        eng.workspace.fill_(0xFF)                   # every byte NaN: a row that no layer wrote would be read as such
-        m.pooled(xg, lengths=lens)
-        torch.cuda.synchronize()
+        """Layer 3's rows of the ragged batch as the whole path left them in the workspace (tdnn_support.workspace_rows)."""
+        y = workspace_rows(m, xg, lens, "a")
         assert m.last_forms()[1:3] == ["winograd_f23"] * 2 and m.last_operands()[1:3] == ["bf16_split3"] * 2, m.last_operands()
-        lay = _layout(m, sum(lens), len(lens))
-        nh = lay.hidden_n_pad
-        return eng.workspace[lay.act_a: lay.act_a + int(off[-1]) * nh * 4].view(torch.float32).reshape(-1, nh)[:, :hid].clone()
+        assert y.shape[0] == int(off[-1])
+        return y
 
     y = layer3_rows()
     assert torch.isfinite(y).all(), "ragged: a layer-3 row was not written, or a row that no layer wrote was read"

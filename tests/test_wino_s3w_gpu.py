@@ -18,7 +18,7 @@ import torch
 
 import xvector_oracle as oracle
 from conftest import assert_parity, float_params
-from tdnn_support import DEV, make_model, oracle_layer, worst_rel
+from tdnn_support import DEV, make_model, oracle_layer, workspace_rows, worst_rel
 
 pytestmark = pytest.mark.gpu
 WINO_LAYERS = (1, 2)          # time_context_layers.1 / .2: contexts [-2, 0, 2] and [-3, 0, 3]
@@ -89,20 +89,6 @@ def test_fallback_to_four_waves(synth, hid):
     _compare(synth, hid, 3, 22, 256)
 
 
-def _layer3_rows(m, xg, hid):
-    import ctypes
-    from xvector_amd import hip
-    eng = m._engine(torch.device(DEV))
-    eng.ensure_workspace(sum(RAGGED), len(RAGGED))
-    eng.workspace.fill_(0xFF)                   # every byte NaN: a row that no layer wrote would be read as such
-    m.pooled(xg, lengths=RAGGED)
-    torch.cuda.synchronize()
-    lay = hip.WsLayout()
-    hip.check(hip.lib.xvec_workspace_layout(eng.h, sum(RAGGED), len(RAGGED), ctypes.byref(lay)))
-    n_rows, nh = sum(n - 14 for n in RAGGED), lay.hidden_n_pad
-    return eng.workspace[lay.act_a: lay.act_a + n_rows * nh * 4].view(torch.float32).reshape(-1, nh)[:, :hid].clone()
-
-
 @pytest.mark.parametrize("hid", (256, 512))
 def test_ragged_batch(synth, hid):
     wide, four, sd, _ = _handles(hid)
@@ -127,7 +113,7 @@ def test_ragged_batch(synth, hid):
     assert torch.equal(gw[fin], wide.extract_x_vec(xg, lengths=RAGGED)[fin]), f"width {hid}: ragged repeat run differs"
     # layer 3's compact rows as the whole path leaves them in the workspace (activation buffer A; the pooled mode runs no segment
     # layer, which would reuse it; layer 2's rows are overwritten by layer 4, and a wrong bit in them changes layer 3's)
-    rows = [_layer3_rows(m, xg, hid) for m in (wide, four)]
+    rows = [workspace_rows(m, xg, RAGGED, "a") for m in (wide, four)]
     assert torch.isfinite(rows[0]).all(), f"width {hid}: a layer-3 row was not written, or padding was read"
     assert torch.equal(rows[0], rows[1]), f"width {hid}: ragged layer-3 rows differ between the two tilings"
 
