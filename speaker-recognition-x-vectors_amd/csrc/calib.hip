@@ -1,5 +1,7 @@
 // Score calibration: prior-weighted linear logistic regression, the affine map, Cllr / actual DCF, and PAV minCllr.
 // C ABI, the definitions, the stopping rule and the summation order: include/xvec_calib.h.  Plan and checks: calib_plan.h.
+// The trial reader, the inverse of the score key and the block sums, counts and scans: trial_device.h, shared with eval.hip and
+// report.hip, so that the three units leave out the same trials.
 //   fit       gather (trial score and target bit into the workspace, block partials of the counts and of sum s)
 //             -> mean (one block) -> sum (s - mu)^2 (block partials) -> start (one block: sd, the weights, the first point)
 //             -> max_iter x [ pass (J, g_a, g_b, H_aa, H_ab, H_bb at the trial point: block partials)
@@ -20,6 +22,7 @@
 #include "../../include/xvec_hip.h"
 #include "calib_plan.h"
 #include "host_support.h"
+#include "trial_device.h"
 
 // Every operation rounds on its own: apply's result is numpy's a * S + b bit for bit, and the error bounds of
 // tests/test_calibrate_gpu.py count roundings.
@@ -29,102 +32,18 @@ namespace xvec {
 namespace {
 
 using namespace calib_plan;
+using namespace trial_device;      // the trial reader (as eval.hip gathers the trials), key_score, the block primitives
 
 constexpr int kWaves = kThreads / 64;
-constexpr uint8_t kBitVoid = 2;               // a trial left out
 constexpr double kLn2 = 0.693147180559945309417232121458;
 constexpr double kLog2e = 1.442695040888963407359924681002;
 constexpr double kAcceptSlack = 0x1p-40;
 constexpr double kStepCap = 8.0;
 
-// ---------------------------------------------------------------- block helpers (every thread of the block calls them)
-
-// Sum of one double per thread in the header's order: butterfly over the wave's lanes (every lane ends with the same bits),
-// then the waves' sums in wave order.  wsum: kWaves doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-    __syncthreads();                          // the previous call's readers are done with wsum
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = wsum[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) s += wsum[w];
-    return s;
-}
-
-__device__ __forceinline__ long long block_count(long long v, long long* wsum) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long s = wsum[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) s += wsum[w];
-    return s;
-}
-
-// Exclusive scan of one value per thread in thread order; *total receives the sum in every thread.  wtot: kWaves words.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    __syncthreads();
-    if (lane == 63) wtot[wave] = x;
-    __syncthreads();
-    uint32_t add = 0, t = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint32_t s = wtot[w];
-        if (w < wave) add += s;
-        t += s;
-    }
-    if (total) *total = t;
-    return add + x - v;
-}
-
 // softplus(x) / ln 2 with softplus(0) = ln 2 exactly (include/xvec_calib.h)
 __device__ __forceinline__ double softplus_bits(double x) {
     if (x == 0.0) return 1.0;
     return (fmax(x, 0.0) + log1p(exp(-fabs(x)))) * kLog2e;
-}
-
-// ---------------------------------------------------------------- the trial forms (as csrc/eval.hip gathers them)
-
-struct TrialArgs {
-    const double* scores;
-    int64_t ld, n_rows, n_cols, n;
-    const int32_t* a;          // row_idx | row_class
-    const int32_t* b;          // col_idx | col_class
-    const uint8_t* is_target;  // trial list only
-    int skip_diagonal;         // all pairs only
-};
-
-enum { kUse = 0, kNan = 1, kBad = 2, kSkip = 3 };
-
-// Trial t: its score and target bit; what became of it.  The cell of a bad index is never read.
-template <bool ALL_PAIRS>
-__device__ __forceinline__ int read_trial(const TrialArgs& g, int64_t t, double* s, bool* target) {
-    int64_t row, col;
-    if (ALL_PAIRS) {
-        row = (int64_t)((uint32_t)t / (uint32_t)g.n_cols);       // t < 2^31, n_cols < 2^31
-        col = t - row * g.n_cols;
-        *target = g.a[row] == g.b[col];
-        if (g.skip_diagonal && row == col) return kSkip;
-    } else {
-        row = g.a ? (int64_t)g.a[t] : 0;
-        col = g.b ? (int64_t)g.b[t] : t;
-        *target = g.is_target[t] != 0;
-        if (row < 0 || row >= g.n_rows || col < 0 || col >= g.n_cols) return kBad;
-    }
-    const double v = g.scores[row * g.ld + col];
-    *s = v;
-    return v != v ? kNan : kUse;
 }
 
 // ---------------------------------------------------------------- fit
@@ -158,20 +77,19 @@ __global__ __launch_bounds__(kThreads) void calib_gather_kernel(const TrialArgs 
         for (int k = 0; k < kItems; ++k) {
             const int64_t t = base + k * kThreads + threadIdx.x;
             if (t >= g.n) break;
+            const Trial tr = read_trial<ALL_PAIRS>(g, t);
             double s = 0.0;
-            bool target = false;
-            const int what = read_trial<ALL_PAIRS>(g, t, &s, &target);
             uint8_t bit = kBitVoid;
-            if (what == kUse) {
-                bit = target ? 1 : 0;
-                c_tar += target;
-                c_non += !target;
+            if (tr.what == kUse) {
+                s = tr.score;
+                bit = tr.target ? 1 : 0;
+                c_tar += tr.target;
+                c_non += !tr.target;
                 c_inf += isinf(s) ? 1 : 0;
                 sum += s;
             } else {
-                s = 0.0;
-                c_nan += what == kNan;
-                c_bad += what == kBad;
+                c_nan += tr.what == kNan;
+                c_bad += tr.what == kBad;
             }
             fs[t] = s;
             fb[t] = bit;
@@ -444,12 +362,11 @@ __global__ __launch_bounds__(kThreads) void calib_cllr_kernel(const TrialArgs g,
         for (int k = 0; k < kItems; ++k) {
             const int64_t t = base + k * kThreads + threadIdx.x;
             if (t >= g.n) break;
-            double l = 0.0;
-            bool target = false;
-            const int what = read_trial<ALL_PAIRS>(g, t, &l, &target);
-            if (what == kUse) {
+            const Trial tr = read_trial<ALL_PAIRS>(g, t);
+            const double l = tr.score;
+            if (tr.what == kUse) {
                 const bool rejected = l <= threshold;
-                if (target) {
+                if (tr.target) {
                     c[kLTar] += 1;
                     c[kLMiss] += rejected;
                     st += softplus_bits(-l);
@@ -459,8 +376,8 @@ __global__ __launch_bounds__(kThreads) void calib_cllr_kernel(const TrialArgs g,
                     sn += softplus_bits(l);
                 }
             } else {
-                c[kLNan] += what == kNan;
-                c[kLBad] += what == kBad;
+                c[kLNan] += tr.what == kNan;
+                c[kLBad] += tr.what == kBad;
             }
         }
     }
@@ -555,22 +472,11 @@ __global__ __launch_bounds__(kThreads) void calib_pav_counts_kernel(const uint8_
 // One block: counts[0] <- its exclusive scan (the targets in front of every block); the totals.
 __global__ __launch_bounds__(kThreads) void calib_pav_scan_kernel(uint32_t* __restrict__ counts, int64_t blocks, PavTotals* tot) {
     __shared__ uint32_t wtot[kWaves];
-    uint32_t carry = 0;
-    unsigned long long kept = 0;
-    for (int64_t c0 = 0; c0 < blocks; c0 += kThreads) {
-        const int64_t i = c0 + threadIdx.x;
-        const uint32_t v = i < blocks ? counts[i] : 0u;
-        uint32_t total;
-        const uint32_t e = block_excl_scan(v, wtot, &total);
-        if (i < blocks) counts[i] = carry + e;
-        carry += total;
-        uint32_t kt;
-        block_excl_scan(i < blocks ? counts[blocks + i] : 0u, wtot, &kt);
-        kept += kt;
-    }
+    const uint32_t targets = block_scan_array(counts, counts, blocks, wtot);
+    const uint32_t kept = block_scan_array(counts + blocks, nullptr, blocks, wtot);      // at most n < 2^31
     if (threadIdx.x == 0) {
         tot->m = (long long)kept;
-        tot->P = (long long)carry;
+        tot->P = (long long)targets;
     }
 }
 
@@ -650,11 +556,6 @@ struct PavOut {
     double* llr;
     int64_t capacity;
 };
-
-__device__ __forceinline__ float key_score(uint32_t k) {      // the inverse of eval.hip's score_key
-    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    return __uint_as_float(u);
-}
 
 // One block: the `groups` <= kFinal groups (each `span` slots wide) merged pairwise; the origin in front; the segments.
 __global__ __launch_bounds__(kThreads) void calib_hull_final_kernel(Pt* pts, const uint32_t* __restrict__ cnt_in, int groups,
@@ -749,21 +650,6 @@ Buffers carve(void* workspace, int64_t n) {
 
 int refused(const Refusal& why, bool too_large, const char* call) {
     return g_cerr.refused(too_large ? XVEC_ERR_TOO_LARGE : XVEC_ERR_ARG, why, call);
-}
-
-TrialArgs trial_args(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* a, const int32_t* b,
-                     const uint8_t* is_target, int64_t n, int skip_diagonal) {
-    TrialArgs g{};
-    g.scores = scores;
-    g.ld = ld;
-    g.n_rows = n_rows;
-    g.n_cols = n_cols;
-    g.n = n;
-    g.a = a;
-    g.b = b;
-    g.is_target = is_target;
-    g.skip_diagonal = skip_diagonal;
-    return g;
 }
 
 int fit(const TrialArgs& g, bool all_pairs, double p_target, int32_t max_iter, xvec_calib_fit_result* out, void* workspace,

@@ -8,6 +8,7 @@
 
 #include "../../include/xvec_calib.h"
 #include "plan_support.h"
+#include "trial_plan.h"
 
 namespace xvec {
 namespace calib_plan {
@@ -25,7 +26,11 @@ constexpr int kMaxIter = 1000;
 static_assert(kFinal <= kThreads, "the final block owns one group per thread");
 static_assert(kMaxBlocks % kThreads == 0, "the reducing block reads whole rounds of partials");
 
-inline bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffff; }
+// the trial forms and their checks are the family's (trial_plan.h)
+using trial_plan::check_all_pairs;
+using trial_plan::check_matrix;
+using trial_plan::check_trials;
+using trial_plan::count_ok;
 
 // Blocks of a multi-sum pass over n trials: a function of n alone (not of the device), so that the sums' order is too.
 inline int64_t pass_blocks(int64_t n) {
@@ -116,44 +121,6 @@ inline Layout make_layout(int64_t n, size_t eval_bytes) {
 
 // ---------------------------------------------------------------- argument checks: 0, or 1 with the reason in why
 
-inline int check_matrix(const void* scores, int64_t ld, int64_t n_rows, int64_t n_cols, Refusal& why) {
-    if (!scores) return why.refuse("null pointer: scores");
-    if (n_rows < 1 || n_cols < 1 || n_rows > 0x7fffffff || n_cols > 0x7fffffff)
-        return why.refuse("score matrix [%lld, %lld]: both sizes must be in 1 .. 2^31 - 1", (long long)n_rows, (long long)n_cols);
-    if (ld < n_cols) return why.refuse("ld = %lld is smaller than n_cols = %lld", (long long)ld, (long long)n_cols);
-    return 0;
-}
-
-// *too_large: the refusal is one of size (XVEC_ERR_TOO_LARGE), not of form
-inline int check_trials(const void* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const void* row_idx, const void* col_idx,
-                        const void* is_target, int64_t n_trials, Refusal& why, bool* too_large) {
-    *too_large = false;
-    if (n_trials < 1) return why.refuse("n_trials = %lld: need at least one trial", (long long)n_trials);
-    if (n_trials > 0x7fffffff) {
-        *too_large = true;
-        return why.refuse("n_trials = %lld exceeds 2^31 - 1", (long long)n_trials);
-    }
-    if (check_matrix(scores, ld, n_rows, n_cols, why)) return 1;
-    if (!is_target) return why.refuse("null pointer: is_target");
-    if ((row_idx == nullptr) != (col_idx == nullptr)) return why.refuse("row_idx and col_idx must both be given or both be null");
-    if (!row_idx && (n_rows != 1 || n_cols < n_trials))
-        return why.refuse("without index arrays the scores are a vector: n_rows = 1 and n_cols >= n_trials (got [%lld, %lld] for "
-                          "%lld trials)", (long long)n_rows, (long long)n_cols, (long long)n_trials);
-    return 0;
-}
-
-inline int check_all_pairs(const void* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const void* row_class,
-                           const void* col_class, Refusal& why, bool* too_large) {
-    *too_large = false;
-    if (check_matrix(scores, ld, n_rows, n_cols, why)) return 1;
-    if (!row_class || !col_class) return why.refuse("null pointer: row_class / col_class");
-    if (n_rows * n_cols > 0x7fffffff) {      // both < 2^31: no overflow
-        *too_large = true;
-        return why.refuse("%lld x %lld cells exceed 2^31 - 1 trials", (long long)n_rows, (long long)n_cols);
-    }
-    return 0;
-}
-
 inline int check_prior(double p_target, Refusal& why) {
     if (!(p_target > 0.0 && p_target < 1.0)) return why.refuse("p_target = %g must lie strictly between 0 and 1", p_target);
     return 0;
@@ -174,8 +141,7 @@ inline int check_costs(double c_miss, double c_fa, double p_target, Refusal& why
 inline int check_apply(const void* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const void* fit, const void* out,
                        int64_t ld_out, Refusal& why, bool* too_large) {
     *too_large = false;
-    if (n_rows < 1 || n_cols < 1 || n_rows > 0x7fffffff || n_cols > 0x7fffffff)
-        return why.refuse("score matrix [%lld, %lld]: both sizes must be in 1 .. 2^31 - 1", (long long)n_rows, (long long)n_cols);
+    if (trial_plan::check_shape(n_rows, n_cols, why)) return 1;
     if (ld < n_cols || ld_out < n_cols)
         return why.refuse("ld = %lld and ld_out = %lld must be at least n_cols = %lld", (long long)ld, (long long)ld_out,
                           (long long)n_cols);

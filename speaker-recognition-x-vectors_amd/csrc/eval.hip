@@ -1,6 +1,7 @@
 // Trial-list evaluation: EER and minDCF from scores that stay on the device.
 //   reference: plda_score_stat.py:36-97 -> speechbrain 0.5.12 utils.metric_stats EER / minDCF (float32 tensors)
-// C ABI and the algorithm: include/xvec_eval.h.  Stages, one kernel each:
+// C ABI and the algorithm: include/xvec_eval.h.  The score key, the trial reader and the block scan: trial_device.h; the argument
+// checks: trial_plan.h (both shared with calib.hip and report.hip).  Stages, one kernel each:
 //   gather + key   trial score -> fp32 (RNE) -> order-preserving 32-bit key, target bit next to it
 //   sort           stable LSD radix sort, 4 passes of 8 bits: per-tile digit histogram, scan of the histograms, scatter that
 //                  ranks inside the tile with wave ballots and reorders through LDS
@@ -17,68 +18,27 @@
 #include "../../include/xvec_eval.h"
 #include "../../include/xvec_hip.h"
 #include "host_support.h"
+#include "trial_device.h"
+#include "trial_plan.h"
 
 namespace xvec {
 namespace {
+
+using namespace trial_device;
 
 constexpr int kThreads = 256;
 constexpr int kItems = 16;
 constexpr int kTile = kThreads * kItems;      // elements a block owns in every stage
 constexpr int kWaves = kThreads / 64;
 constexpr int kRadix = 256;                   // 8-bit digits
-constexpr uint8_t kBitVoid = 2;               // a trial left out (NaN, bad index, skipped diagonal): key 0xffffffff, sorts last
-constexpr uint32_t kKeyVoid = 0xffffffffu;    // above the key of +inf (0xff800000); no finite score or infinity maps to it
 
 // counters in the workspace (uint64 each)
 enum { kCntNan = 0, kCntBad = 1, kCntSkipped = 2, kCntTargets = 3, kCounters = 4 };
 
-// ---------------------------------------------------------------- helpers
-
-// fp64 score -> fp32 (round to nearest even) -> key with key(a) < key(b) iff a < b; -0.0 and +0.0 share 0x80000000
-__device__ __forceinline__ uint32_t score_key(double s) {
-    uint32_t u = __float_as_uint(__double2float_rn(s));
-    if ((u << 1) == 0u) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ double key_score(uint32_t k) {
-    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    return (double)__uint_as_float(u);
-}
-
-// Exclusive scan of one value per thread over the block's 256 threads (thread order); *total (if given) receives the sum in
-// every thread.  wtot: kWaves words of LDS.  Every thread of the block must call it.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    if (lane == 63) wtot[wave] = x;
-    __syncthreads();
-    uint32_t add = 0, t = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint32_t s = wtot[w];
-        if (w < wave) add += s;
-        t += s;
-    }
-    if (total) *total = t;
-    __syncthreads();
-    return add + x - v;
-}
-
 // ---------------------------------------------------------------- stage 1: gather and key
 
 struct GatherArgs {
-    const double* scores;
-    int64_t ld, n_rows, n_cols, n;
-    const int32_t* a;          // row_idx | row_class
-    const int32_t* b;          // col_idx | col_class
-    const uint8_t* is_target;  // trial list only
-    int skip_diagonal;         // all pairs only
+    TrialArgs trials;
     uint32_t* keys;
     uint8_t* bits;
     unsigned long long* counters;
@@ -94,37 +54,17 @@ __global__ __launch_bounds__(kThreads) void eval_gather_kernel(const GatherArgs 
 #pragma unroll 4
     for (int k = 0; k < kItems; ++k) {
         const int64_t t = base + k * kThreads + threadIdx.x;
-        if (t >= g.n) break;
-        int64_t row, col;
-        bool target, use = true;
-        if (ALL_PAIRS) {
-            row = (int64_t)((uint32_t)t / (uint32_t)g.n_cols);       // t < 2^31, n_cols < 2^31
-            col = t - row * g.n_cols;
-            target = g.a[row] == g.b[col];
-            if (g.skip_diagonal && row == col) {
-                use = false;
-                ++n_skip;
-            }
-        } else {
-            row = g.a ? (int64_t)g.a[t] : 0;
-            col = g.b ? (int64_t)g.b[t] : t;
-            target = g.is_target[t] != 0;
-            if (row < 0 || row >= g.n_rows || col < 0 || col >= g.n_cols) {      // never dereferenced
-                use = false;
-                ++n_bad;
-            }
-        }
+        if (t >= g.trials.n) break;
+        const Trial tr = read_trial<ALL_PAIRS>(g.trials, t);
         uint32_t key = kKeyVoid;
         uint8_t bit = kBitVoid;
-        if (use) {
-            const double s = g.scores[row * g.ld + col];
-            if (s != s) {
-                ++n_nan;
-            } else {
-                key = score_key(s);
-                bit = target ? 1 : 0;
-            }
+        if (tr.what == kUse) {
+            key = score_key(tr.score);
+            bit = tr.target ? 1 : 0;
         }
+        n_nan += tr.what == kNan;
+        n_bad += tr.what == kBad;
+        n_skip += tr.what == kSkip;
         g.keys[t] = key;
         g.bits[t] = bit;
     }
@@ -175,16 +115,8 @@ __global__ __launch_bounds__(kThreads) void eval_scan_sums_kernel(const uint32_t
 __global__ __launch_bounds__(kThreads) void eval_scan_top_kernel(uint32_t* __restrict__ sums, int64_t n_sums,
                                                                  unsigned long long* __restrict__ total_out) {
     __shared__ uint32_t wtot[kWaves];
-    uint32_t carry = 0;
-    for (int64_t c0 = 0; c0 < n_sums; c0 += kThreads) {
-        const int64_t i = c0 + threadIdx.x;
-        const uint32_t v = i < n_sums ? sums[i] : 0u;
-        uint32_t total;
-        const uint32_t e = block_excl_scan(v, wtot, &total);
-        if (i < n_sums) sums[i] = carry + e;
-        carry += total;
-    }
-    if (total_out && threadIdx.x == 0) *total_out = carry;
+    const uint32_t total = block_scan_array(sums, sums, n_sums, wtot);
+    if (total_out && threadIdx.x == 0) *total_out = total;
 }
 
 __global__ __launch_bounds__(kThreads) void eval_scan_apply_kernel(uint32_t* __restrict__ v, int64_t len,
@@ -425,9 +357,9 @@ __global__ __launch_bounds__(kThreads) void eval_final_kernel(const SweepArgs g,
         r.far = (double)fa / (double)N;
         r.frr = (double)be.tp / (double)P;
         r.eer = (r.far + r.frr) / 2.0;
-        r.eer_threshold = key_score(g.keys[be.idx]);
+        r.eer_threshold = (double)key_score(g.keys[be.idx]);
         r.min_dcf = bd.val;
-        r.min_dcf_threshold = key_score(g.keys[bd.idx]);
+        r.min_dcf_threshold = (double)key_score(g.keys[bd.idx]);
     }
     *out = r;
 }
@@ -469,8 +401,6 @@ EvalPlan make_plan(void* workspace, int64_t n) {
     return p;
 }
 
-bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffff; }
-
 // v[0 .. len) <- its exclusive scan; *total_out (device, may be null) <- the sum
 int scan_in_place(uint32_t* v, int64_t len, uint32_t* sums, unsigned long long* total_out, hipStream_t s) {
     const int64_t nc = chunks(len);
@@ -484,7 +414,8 @@ int scan_in_place(uint32_t* v, int64_t len, uint32_t* sums, unsigned long long* 
 }
 
 // stages 1 and 2: afterwards keys[0] / bits[0] hold the sorted pairs
-int gather_and_sort(const GatherArgs& ga, bool all_pairs, const EvalPlan& p, hipStream_t s) {
+int gather_and_sort(const TrialArgs& trials, bool all_pairs, const EvalPlan& p, hipStream_t s) {
+    const GatherArgs ga{trials, p.keys[0], p.bits[0], p.counters};
     const hipError_t e = hipMemsetAsync(p.counters, 0, kCounters * sizeof(unsigned long long), s);
     if (e != hipSuccess) return g_eerr.fail(XVEC_ERR_HIP, "clearing the counters failed: %s", hipGetErrorString(e));
     const unsigned grid = (unsigned)p.tiles;
@@ -527,13 +458,8 @@ int sweep(const EvalPlan& p, double c_miss, double c_fa, double p_target, xvec_e
     return g_eerr.launch_ok("eval_final_kernel");
 }
 
-int check_matrix(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols) {
-    if (!scores) return g_eerr.fail(XVEC_ERR_ARG, "null pointer: scores");
-    if (n_rows < 1 || n_cols < 1 || n_rows > 0x7fffffff || n_cols > 0x7fffffff)
-        return g_eerr.fail(XVEC_ERR_ARG, "score matrix [%lld, %lld]: both sizes must be in 1 .. 2^31 - 1", (long long)n_rows,
-                           (long long)n_cols);
-    if (ld < n_cols) return g_eerr.fail(XVEC_ERR_ARG, "ld = %lld is smaller than n_cols = %lld", (long long)ld, (long long)n_cols);
-    return XVEC_OK;
+int refused(const Refusal& why, bool too_large = false) {
+    return g_eerr.refused(too_large ? XVEC_ERR_TOO_LARGE : XVEC_ERR_ARG, why);
 }
 
 int check_costs(double c_miss, double c_fa, double p_target) {
@@ -543,38 +469,21 @@ int check_costs(double c_miss, double c_fa, double p_target) {
     return XVEC_OK;
 }
 
+// trial_plan.h's check_trials in its pieces: this unit answers one unnamed "null pointer" for is_target and the workspace
+// (include/xvec_eval.h), where the other units name them apart.
 int check_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
                  const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, void* workspace, size_t workspace_bytes,
                  EvalPlan* plan) {
-    if (n_trials < 1) return g_eerr.fail(XVEC_ERR_ARG, "n_trials = %lld: need at least one trial", (long long)n_trials);
-    if (n_trials > 0x7fffffff) return g_eerr.fail(XVEC_ERR_TOO_LARGE, "n_trials = %lld exceeds 2^31 - 1", (long long)n_trials);
-    int rc;
-    if ((rc = check_matrix(scores, ld, n_rows, n_cols))) return rc;
+    Refusal why;
+    bool too_large;
+    if (trial_plan::check_trial_count(n_trials, why, &too_large) || trial_plan::check_matrix(scores, ld, n_rows, n_cols, why))
+        return refused(why, too_large);
     if (!is_target || !workspace) return g_eerr.fail(XVEC_ERR_ARG, "null pointer");
-    if ((row_idx == nullptr) != (col_idx == nullptr))
-        return g_eerr.fail(XVEC_ERR_ARG, "row_idx and col_idx must both be given or both be null");
-    if (!row_idx && (n_rows != 1 || n_cols < n_trials))
-        return g_eerr.fail(XVEC_ERR_ARG, "without index arrays the scores are a vector: n_rows = 1 and n_cols >= n_trials "
-                           "(got [%lld, %lld] for %lld trials)", (long long)n_rows, (long long)n_cols, (long long)n_trials);
+    if (trial_plan::check_index_pair(row_idx, col_idx, why) ||
+        trial_plan::check_vector_form(row_idx, n_rows, n_cols, n_trials, why))
+        return refused(why);
     *plan = make_plan(workspace, n_trials);
     return workspace_ok(workspace_bytes, plan->total, g_eerr);
-}
-
-GatherArgs trial_args(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
-                      const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, const EvalPlan& p) {
-    GatherArgs ga{};
-    ga.scores = scores;
-    ga.ld = ld;
-    ga.n_rows = n_rows;
-    ga.n_cols = n_cols;
-    ga.n = n_trials;
-    ga.a = row_idx;
-    ga.b = col_idx;
-    ga.is_target = is_target;
-    ga.keys = p.keys[0];
-    ga.bits = p.bits[0];
-    ga.counters = p.counters;
-    return ga;
 }
 
 }  // namespace
@@ -587,7 +496,7 @@ extern "C" {
 const char* xvec_eval_last_error(void) { return g_eerr.c_str(); }
 
 size_t xvec_eval_workspace_bytes(int64_t n_trials) {
-    if (!count_ok(n_trials)) return 0;
+    if (!trial_plan::count_ok(n_trials)) return 0;
     return make_plan(nullptr, n_trials).total;
 }
 
@@ -601,7 +510,7 @@ int xvec_eval_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n
     if (!out) return g_eerr.fail(XVEC_ERR_ARG, "null pointer: out");
     if ((rc = check_costs(c_miss, c_fa, p_target))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, p), false, p, s)))
+    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, false), false, p, s)))
         return rc;
     return sweep(p, c_miss, c_fa, p_target, out, s);
 }
@@ -609,19 +518,20 @@ int xvec_eval_trials(const double* scores, int64_t ld, int64_t n_rows, int64_t n
 int xvec_eval_all_pairs(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_class,
                         const int32_t* col_class, int32_t skip_diagonal, double c_miss, double c_fa, double p_target,
                         xvec_eval_result* out, void* workspace, size_t workspace_bytes, xvec_stream stream) {
-    int rc;
-    if ((rc = check_matrix(scores, ld, n_rows, n_cols))) return rc;
+    // trial_plan.h's check_all_pairs in its pieces, around this unit's one unnamed "null pointer"
+    Refusal why;
+    bool too_large;
+    if (trial_plan::check_matrix(scores, ld, n_rows, n_cols, why)) return refused(why);
     if (!row_class || !col_class || !out || !workspace) return g_eerr.fail(XVEC_ERR_ARG, "null pointer");
-    const int64_t n = n_rows * n_cols;      // both < 2^31: no overflow
-    if (n > 0x7fffffff)
-        return g_eerr.fail(XVEC_ERR_TOO_LARGE, "%lld x %lld cells exceed 2^31 - 1 trials", (long long)n_rows, (long long)n_cols);
+    if (trial_plan::check_cell_count(n_rows, n_cols, why, &too_large)) return refused(why, too_large);
+    int rc;
     if ((rc = check_costs(c_miss, c_fa, p_target))) return rc;
+    const int64_t n = n_rows * n_cols;
     const EvalPlan p = make_plan(workspace, n);
     if ((rc = workspace_ok(workspace_bytes, p.total, g_eerr))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    GatherArgs ga = trial_args(scores, ld, n_rows, n_cols, row_class, col_class, nullptr, n, p);
-    ga.skip_diagonal = skip_diagonal != 0;
-    if ((rc = gather_and_sort(ga, true, p, s))) return rc;
+    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_class, col_class, nullptr, n, skip_diagonal != 0), true, p, s)))
+        return rc;
     return sweep(p, c_miss, c_fa, p_target, out, s);
 }
 
@@ -634,7 +544,7 @@ int xvec_eval_sorted_keys(const double* scores, int64_t ld, int64_t n_rows, int6
         return rc;
     if (!keys_out || !bits_out) return g_eerr.fail(XVEC_ERR_ARG, "null pointer: keys_out / bits_out");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, p), false, p, s)))
+    if ((rc = gather_and_sort(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, false), false, p, s)))
         return rc;
     hipError_t e = hipMemcpyAsync(keys_out, p.keys[0], (size_t)n_trials * sizeof(uint32_t), hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess) e = hipMemcpyAsync(bits_out, p.bits[0], (size_t)n_trials, hipMemcpyDeviceToDevice, s);

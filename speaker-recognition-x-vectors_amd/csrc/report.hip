@@ -1,6 +1,8 @@
 // Trial report: the trial map, the range of the score matrix, the six TensorBoard images and the DET curve.
 //   reference: plda_score_stat.py:132-192 (the image half of plot_images)
 // C ABI, the definitions and the deviations: include/xvec_report.h.  Plan, checks and the shared host/device rules: report_plan.h.
+// The trial reader, the inverse of the score key and the block scans, counts and extremes: trial_device.h, shared with eval.hip and
+// calib.hip, so that the DET curve leaves out the trials the sort leaves out.
 //   trial_map  memset, then one thread per trial: a 32-bit OR atomic on the aligned word that holds the cell's byte
 //   range      tiles of one row x 1024 columns, block partials (min, max, count of non-finite cells) -> one block
 //   images     a block stages a tile of cells in LDS (the normalised value and six flag bits of every cell, consecutive lanes
@@ -20,6 +22,7 @@
 #include "../../include/xvec_report.h"
 #include "host_support.h"
 #include "report_plan.h"
+#include "trial_device.h"
 
 // Every operation rounds on its own: (S - mn) / (mx - mn) and K * S are numpy's results bit for bit.
 #pragma clang fp contract(off)
@@ -28,42 +31,14 @@ namespace xvec {
 namespace {
 
 using namespace report_plan;
+using namespace trial_device;      // the trial reader (as eval.hip gathers the trials), key_score, the block primitives
 
 constexpr int kWaves = kThreads / 64;
-constexpr uint8_t kBitVoid = 2;               // a trial left out (include/xvec_eval.h)
 
 // flag bits of a staged cell
 constexpr uint32_t kP = 1, kNg = 2, kGeE = 4, kLtE = 8, kGeM = 16, kLtM = 32;
 // what a plane holds
 enum { kModeZero = 0, kModeCount = 1, kModeValue = 2, kModeOne = 3 };
-
-// Exclusive scan of one value per thread in thread order; *total receives the sum in every thread.  wtot: kWaves words.
-__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wtot, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t y = __shfl_up(x, off);
-        if (lane >= off) x += y;
-    }
-    __syncthreads();                          // the previous call's readers are done with wtot
-    if (lane == 63) wtot[wave] = x;
-    __syncthreads();
-    uint32_t add = 0, t = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-        const uint32_t s = wtot[w];
-        if (w < wave) add += s;
-        t += s;
-    }
-    if (total) *total = t;
-    return add + x - v;
-}
-
-__device__ __forceinline__ float key_score(uint32_t k) {      // the inverse of include/xvec_eval.h's key
-    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-    return __uint_as_float(u);
-}
 
 // ---------------------------------------------------------------- trial map
 
@@ -91,35 +66,6 @@ __global__ __launch_bounds__(kThreads) void report_map_kernel(const int32_t* __r
 }
 
 // ---------------------------------------------------------------- range
-
-// Every thread of the block calls it; the result is in every thread.  MIN: minimum, else maximum.
-template <bool MIN>
-__device__ __forceinline__ double block_extreme(double v, double* wbuf) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const double o = __shfl_xor(v, off);
-        v = MIN ? fmin(v, o) : fmax(v, o);
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wbuf[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = wbuf[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) s = MIN ? fmin(s, wbuf[w]) : fmax(s, wbuf[w]);
-    return s;
-}
-
-__device__ __forceinline__ long long block_count(long long v, long long* wbuf) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) wbuf[threadIdx.x >> 6] = v;
-    __syncthreads();
-    long long s = wbuf[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) s += wbuf[w];
-    return s;
-}
 
 // part[3 b ..]: minimum, maximum, count (as int64 bits) of block b
 __global__ __launch_bounds__(kThreads) void report_range_kernel(const double* __restrict__ s, int64_t ld, int64_t n_cols,
@@ -344,11 +290,7 @@ struct DetState {              // in the state slot of the workspace
 static_assert(sizeof(DetState) <= 256, "the state's slot in the workspace");
 
 struct DetTrials {
-    const double* scores;
-    int64_t ld, n_rows, n_cols, n;
-    const int32_t* a;          // row_idx | row_class
-    const int32_t* b;          // col_idx | col_class
-    int skip_diagonal;         // all pairs only
+    TrialArgs trials;
     int32_t* row_out;          // all pairs only: the cells as a trial list
     int32_t* col_out;
     uint8_t* tgt_out;
@@ -362,28 +304,15 @@ __global__ __launch_bounds__(kThreads) void report_det_prepare_kernel(const DetT
     if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
     __syncthreads();
     const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (t < g.n) {
-        int64_t row, col;
-        bool use = true;
+    if (t < g.trials.n) {
+        const Trial tr = read_trial<ALL_PAIRS>(g.trials, t);
         if (ALL_PAIRS) {
-            row = (int64_t)((uint32_t)t / (uint32_t)g.n_cols);       // t < 2^31, n_cols < 2^31
-            col = t - row * g.n_cols;
-            if (g.skip_diagonal && row == col) use = false;
-            g.row_out[t] = use ? (int32_t)row : -1;
-            g.col_out[t] = (int32_t)col;
-            g.tgt_out[t] = g.a[row] == g.b[col] ? 1 : 0;
-        } else {
-            row = g.a ? (int64_t)g.a[t] : 0;
-            col = g.b ? (int64_t)g.b[t] : t;
-            if (row < 0 || row >= g.n_rows || col < 0 || col >= g.n_cols) {      // never dereferenced
-                use = false;
-                atomicAdd(&cnt[1], 1u);
-            }
+            g.row_out[t] = tr.what == kSkip ? -1 : (int32_t)tr.row;
+            g.col_out[t] = (int32_t)tr.col;
+            g.tgt_out[t] = tr.target ? 1 : 0;
         }
-        if (use) {
-            const double s = g.scores[row * g.ld + col];
-            if (s != s) atomicAdd(&cnt[0], 1u);
-        }
+        if (tr.what == kNan) atomicAdd(&cnt[0], 1u);
+        if (tr.what == kBad) atomicAdd(&cnt[1], 1u);
     }
     __syncthreads();
     if (threadIdx.x == 0 && cnt[0]) atomicAdd(&st->n_nan, (unsigned long long)cnt[0]);
@@ -439,28 +368,15 @@ __global__ __launch_bounds__(kThreads) void report_det_sums_kernel(const uint32_
 // One block, chunks of kThreads blocks in rising order: sums[0] and sums[2] <- their exclusive scans; the totals.
 __global__ __launch_bounds__(kThreads) void report_det_scan_kernel(uint32_t* __restrict__ sums, int64_t blocks, DetState* st) {
     __shared__ uint32_t wtot[kWaves];
-    uint32_t carry_t = 0, carry_e = 0;
-    unsigned long long kept = 0;
-    for (int64_t c0 = 0; c0 < blocks; c0 += kThreads) {
-        const int64_t i = c0 + threadIdx.x;
-        const bool in = i < blocks;
-        uint32_t tt, tk, te;
-        const uint32_t et = block_excl_scan(in ? sums[i] : 0u, wtot, &tt);
-        block_excl_scan(in ? sums[blocks + i] : 0u, wtot, &tk);
-        const uint32_t ee = block_excl_scan(in ? sums[2 * blocks + i] : 0u, wtot, &te);
-        if (in) {
-            sums[i] = carry_t + et;
-            sums[2 * blocks + i] = carry_e + ee;
-        }
-        carry_t += tt;
-        carry_e += te;
-        kept += tk;
-    }
+    uint32_t* ends = sums + 2 * blocks;
+    const uint32_t targets = block_scan_array(sums, sums, blocks, wtot);
+    const uint32_t kept = block_scan_array(sums + blocks, nullptr, blocks, wtot);      // at most n < 2^31
+    const uint32_t n_ends = block_scan_array(ends, ends, blocks, wtot);
     if (threadIdx.x == 0) {
-        st->P = (long long)carry_t;
+        st->P = (long long)targets;
         st->m = (long long)kept;
-        st->n_full = (long long)carry_e;
-        st->n_kept = (long long)carry_e;
+        st->n_full = (long long)n_ends;
+        st->n_kept = (long long)n_ends;
     }
 }
 
@@ -538,15 +454,8 @@ __global__ __launch_bounds__(kThreads) void report_det_keep_kernel(const DetOut 
 __global__ __launch_bounds__(kThreads) void report_det_keep_scan_kernel(uint32_t* __restrict__ keep_sums, int64_t blocks,
                                                                         DetState* st) {
     __shared__ uint32_t wtot[kWaves];
-    uint32_t carry = 0;
-    for (int64_t c0 = 0; c0 < blocks; c0 += kThreads) {
-        const int64_t i = c0 + threadIdx.x;
-        uint32_t total;
-        const uint32_t e = block_excl_scan(i < blocks ? keep_sums[i] : 0u, wtot, &total);
-        if (i < blocks) keep_sums[i] = carry + e;
-        carry += total;
-    }
-    if (threadIdx.x == 0) st->n_kept = (long long)carry;
+    const uint32_t total = block_scan_array(keep_sums, keep_sums, blocks, wtot);
+    if (threadIdx.x == 0) st->n_kept = (long long)total;
 }
 
 __global__ __launch_bounds__(kThreads) void report_det_compact_kernel(const DetOut o, const DetState* st, int64_t grid,
@@ -595,9 +504,8 @@ void add_plane(ImageArgs& g, uint64_t image, int es, int ch, int64_t width, int6
     p.mode = mode;
 }
 
-int det(const DetTrials& trials, bool all_pairs, const int32_t* row_idx, const int32_t* col_idx, const uint8_t* is_target,
-        int64_t grid, xvec_report_det_header* header, float* thr, int64_t* tp, int64_t* nn, int64_t capacity, void* workspace,
-        size_t workspace_bytes, xvec_stream stream, const char* call) {
+int det(const TrialArgs& trials, bool all_pairs, int64_t grid, xvec_report_det_header* header, float* thr, int64_t* tp,
+        int64_t* nn, int64_t capacity, void* workspace, size_t workspace_bytes, xvec_stream stream, const char* call) {
     Refusal why;
     if (check_curve(grid, header, thr, tp, nn, capacity, why)) return refused(why, false, call);
     const int64_t n = trials.n;
@@ -611,10 +519,8 @@ int det(const DetTrials& trials, bool all_pairs, const int32_t* row_idx, const i
     uint8_t* bits = reinterpret_cast<uint8_t*>(base + lay.bits);
     uint32_t* sums = reinterpret_cast<uint32_t*>(base + lay.sums);
     uint32_t* keep_sums = reinterpret_cast<uint32_t*>(base + lay.keep_sums);
-    DetTrials g = trials;
-    g.row_out = reinterpret_cast<int32_t*>(base + lay.row);
-    g.col_out = reinterpret_cast<int32_t*>(base + lay.col);
-    g.tgt_out = reinterpret_cast<uint8_t*>(base + lay.tgt);
+    const DetTrials g{trials, reinterpret_cast<int32_t*>(base + lay.row), reinterpret_cast<int32_t*>(base + lay.col),
+                      reinterpret_cast<uint8_t*>(base + lay.tgt)};
     hipStream_t s = static_cast<hipStream_t>(stream);
     const hipError_t e = hipMemsetAsync(st, 0, 256, s);
     if (e != hipSuccess) return g_rerr.fail(XVEC_ERR_HIP, "%s: clearing the counters failed: %s", call, hipGetErrorString(e));
@@ -622,13 +528,10 @@ int det(const DetTrials& trials, bool all_pairs, const int32_t* row_idx, const i
     if (all_pairs) report_det_prepare_kernel<true><<<per_trial, kThreads, 0, s>>>(g, st);
     else report_det_prepare_kernel<false><<<per_trial, kThreads, 0, s>>>(g, st);
     if ((rc = g_rerr.launch_ok("report_det_prepare_kernel"))) return rc;
-    if (all_pairs) {
-        row_idx = g.row_out;
-        col_idx = g.col_out;
-        is_target = g.tgt_out;
-    }
-    if ((rc = xvec_eval_sorted_keys(g.scores, g.ld, g.n_rows, g.n_cols, row_idx, col_idx, is_target, n, keys, bits, base + lay.eval,
-                                    eval_bytes, stream)))
+    // the sort takes a trial list: the one given, or the one the kernel has just written
+    if ((rc = xvec_eval_sorted_keys(trials.scores, trials.ld, trials.n_rows, trials.n_cols, all_pairs ? g.row_out : trials.a,
+                                    all_pairs ? g.col_out : trials.b, all_pairs ? g.tgt_out : trials.is_target, n, keys, bits,
+                                    base + lay.eval, eval_bytes, stream)))
         return g_rerr.fail(rc, "%s: xvec_eval_sorted_keys: %s", call, xvec_eval_last_error());
     const unsigned blocks = (unsigned)lay.blocks;
     report_det_sums_kernel<<<blocks, kThreads, 0, s>>>(keys, bits, n, sums, lay.blocks);
@@ -769,15 +672,8 @@ int xvec_report_det(const double* scores, int64_t ld, int64_t n_rows, int64_t n_
     bool too_large;
     if (check_trials(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, why, &too_large))
         return refused(why, too_large, call);
-    DetTrials g{};
-    g.scores = scores;
-    g.ld = ld;
-    g.n_rows = n_rows;
-    g.n_cols = n_cols;
-    g.n = n_trials;
-    g.a = row_idx;
-    g.b = col_idx;
-    return det(g, false, row_idx, col_idx, is_target, grid, header, thr, tp, nn, capacity, workspace, workspace_bytes, stream, call);
+    return det(trial_args(scores, ld, n_rows, n_cols, row_idx, col_idx, is_target, n_trials, false), false, grid, header, thr, tp, nn,
+               capacity, workspace, workspace_bytes, stream, call);
 }
 
 int xvec_report_det_all_pairs(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_class,
@@ -788,16 +684,8 @@ int xvec_report_det_all_pairs(const double* scores, int64_t ld, int64_t n_rows, 
     Refusal why;
     bool too_large;
     if (check_all_pairs(scores, ld, n_rows, n_cols, row_class, col_class, why, &too_large)) return refused(why, too_large, call);
-    DetTrials g{};
-    g.scores = scores;
-    g.ld = ld;
-    g.n_rows = n_rows;
-    g.n_cols = n_cols;
-    g.n = n_rows * n_cols;
-    g.a = row_class;
-    g.b = col_class;
-    g.skip_diagonal = skip_diagonal != 0;
-    return det(g, true, nullptr, nullptr, nullptr, grid, header, thr, tp, nn, capacity, workspace, workspace_bytes, stream, call);
+    return det(trial_args(scores, ld, n_rows, n_cols, row_class, col_class, nullptr, n_rows * n_cols, skip_diagonal != 0), true, grid,
+               header, thr, tp, nn, capacity, workspace, workspace_bytes, stream, call);
 }
 
 }  // extern "C"

@@ -4,15 +4,15 @@
 // header, like calib_plan.h), so that tests/test_report.py can ask it on the CPU (tests/abi/report_plan_dump.cpp).  The functions
 // marked XVEC_HD are the ones the kernels call too (wide_cols, split_piece, det_step, det_keep); everything else runs on the host.
 //
-// The key of a score is include/xvec_eval.h's (fp32, round to nearest even; -0.0 and +0.0 share 0x80000000; key(a) < key(b)
-// iff a < b): score bits u -> u >= 0 ? u | 0x80000000 : ~u.  report.hip only inverts it (the keys come from
-// xvec_eval_sorted_keys), so csrc/eval.hip is not touched and shares no header with this unit.
+// The checks of the trial forms are trial_plan.h's, re-exported here; the key of a score (include/xvec_eval.h) and its inverse
+// are trial_device.h's.  Both are shared with csrc/eval.hip and csrc/calib.hip.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 
 #include "../../include/xvec_report.h"
 #include "plan_support.h"
+#include "trial_plan.h"
 
 #ifdef __HIPCC__
 #define XVEC_HD __host__ __device__
@@ -35,7 +35,12 @@ constexpr int kMaxPlanes = 25;                         // 1 + 3 + 3 narrow plane
 static_assert(kDetTile == kThreads * kDetItems, "a thread scans kDetItems consecutive trials");
 static_assert(kTile % kThreads == 0 && kRangeBlocks % kThreads == 0, "whole rounds of the block");
 
-inline bool count_ok(int64_t n) { return n >= 1 && n <= 0x7fffffff; }
+// the trial forms and their checks are the family's (trial_plan.h)
+using trial_plan::check_all_pairs;
+using trial_plan::check_matrix;
+using trial_plan::check_shape;
+using trial_plan::check_trials;
+using trial_plan::count_ok;
 
 // ---------------------------------------------------------------- the image pass
 
@@ -148,19 +153,6 @@ inline int64_t range_blocks(int64_t n_rows, int64_t n_cols) {
 
 // ---------------------------------------------------------------- argument checks: 0, or 1 with the reason in why
 
-inline int check_shape(int64_t n_rows, int64_t n_cols, Refusal& why) {
-    if (n_rows < 1 || n_cols < 1 || n_rows > 0x7fffffff || n_cols > 0x7fffffff)
-        return why.refuse("score matrix [%lld, %lld]: both sizes must be in 1 .. 2^31 - 1", (long long)n_rows, (long long)n_cols);
-    return 0;
-}
-
-inline int check_matrix(const void* scores, int64_t ld, int64_t n_rows, int64_t n_cols, Refusal& why) {
-    if (!scores) return why.refuse("null pointer: scores");
-    if (check_shape(n_rows, n_cols, why)) return 1;
-    if (ld < n_cols) return why.refuse("ld = %lld is smaller than n_cols = %lld", (long long)ld, (long long)n_cols);
-    return 0;
-}
-
 inline int check_map(const void* map, int64_t ld_map, int64_t n_cols, Refusal& why) {
     if (!map) return why.refuse("null pointer: map");
     if (ld_map < n_cols) return why.refuse("ld_map = %lld is smaller than n_cols = %lld", (long long)ld_map, (long long)n_cols);
@@ -216,35 +208,6 @@ inline int check_curve(int64_t grid, const void* header, const void* thr, const 
     if (!header) return why.refuse("null pointer: header");
     if (capacity < 0) return why.refuse("capacity = %lld must not be negative", (long long)capacity);
     if (capacity > 0 && (!thr || !tp || !nn)) return why.refuse("null pointer: thr / tp / nn with capacity = %lld", (long long)capacity);
-    return 0;
-}
-
-inline int check_trials(const void* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const void* row_idx, const void* col_idx,
-                        const void* is_target, int64_t n_trials, Refusal& why, bool* too_large) {
-    *too_large = false;
-    if (n_trials < 1) return why.refuse("n_trials = %lld: need at least one trial", (long long)n_trials);
-    if (n_trials > 0x7fffffff) {
-        *too_large = true;
-        return why.refuse("n_trials = %lld exceeds 2^31 - 1", (long long)n_trials);
-    }
-    if (check_matrix(scores, ld, n_rows, n_cols, why)) return 1;
-    if (!is_target) return why.refuse("null pointer: is_target");
-    if ((row_idx == nullptr) != (col_idx == nullptr)) return why.refuse("row_idx and col_idx must both be given or both be null");
-    if (!row_idx && (n_rows != 1 || n_cols < n_trials))
-        return why.refuse("without index arrays the scores are a vector: n_rows = 1 and n_cols >= n_trials (got [%lld, %lld] for "
-                          "%lld trials)", (long long)n_rows, (long long)n_cols, (long long)n_trials);
-    return 0;
-}
-
-inline int check_all_pairs(const void* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const void* row_class,
-                           const void* col_class, Refusal& why, bool* too_large) {
-    *too_large = false;
-    if (check_matrix(scores, ld, n_rows, n_cols, why)) return 1;
-    if (!row_class || !col_class) return why.refuse("null pointer: row_class / col_class");
-    if (n_rows * n_cols > 0x7fffffff) {      // both < 2^31: no overflow
-        *too_large = true;
-        return why.refuse("%lld x %lld cells exceed 2^31 - 1 trials", (long long)n_rows, (long long)n_cols);
-    }
     return 0;
 }
 

@@ -19,6 +19,7 @@
 #include "../../include/xvec_snorm.h"
 #include "host_support.h"
 #include "snorm_keys.h"
+#include "trial_device.h"
 
 // Every operation rounds on its own: the error bounds of tests/test_snorm_gpu.py count roundings, and apply's symmetry
 // (include/xvec_snorm.h) does not survive a multiply-add fused on one side of the sum only.
@@ -28,6 +29,7 @@ namespace xvec {
 namespace {
 
 using namespace snorm_keys;
+using trial_device::block_sum;      // the sum order of the last line above, over the kWaves doubles handed to it
 
 constexpr int kThreads = XVEC_SNORM_THREADS;
 constexpr int kWaves = kThreads / 64;
@@ -49,22 +51,6 @@ struct RowStatsArgs {
     int32_t* n_used;
     xvec_snorm_select_record* rec;
 };
-
-// ---------------------------------------------------------------- block helpers (every thread of the block calls them)
-
-// Sum of one double per thread in a fixed order: butterfly over the wave's lanes (every lane ends with the same bits: the
-// partners of a step add the same two numbers), then the waves' sums in wave order.  wsum: kWaves doubles of LDS.
-__device__ __forceinline__ double block_sum(double v, double* wsum) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-    __syncthreads();                          // the previous call's readers are done with wsum
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double s = wsum[0];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) s += wsum[w];
-    return s;
-}
 
 // ---------------------------------------------------------------- row statistics
 
