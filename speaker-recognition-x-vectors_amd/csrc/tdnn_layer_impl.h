@@ -1,5 +1,6 @@
 // Device code of the 128x128 frame-level kernel family (tdnn_layer.hip: header comment there), shared by the translation
-// units that instantiate it: tdnn_layer.hip (tdnn_kernel, fp32 / bf16 / bf16x3) and tdnn_split3.hip (tdnn_split3_kernel).
+// units that instantiate it: tdnn_layer.hip (tdnn_kernel, fp32 / bf16 / bf16x3), tdnn_split3.hip (tdnn_split3_kernel) and
+// tdnn_split3w.hip (tdnn_split3w_kernel: the pooling S3 body on 384-channel tiles, template parameter WS = the wave set).
 #pragma once
 #include <cstdlib>
 
@@ -375,6 +376,9 @@ constexpr int kPlaneBytes = kBM * kBK * 2;   // one bf16 plane of a 128 x 32 chu
 // LDS of the split form: two buffers of three planes, then the constants table -- 50 688 B, three blocks per CU (the fp32 /
 // bf16 instantiations keep kLdsBytes, two 32 KiB buffers)
 constexpr int kS3BufBytes = 3 * kPlaneBytes;
+// channels of a block's tile: 128 on four waves; 384 on twelve for the wave sets WS = 0, 1, 2 of tdnn_split3w.hip
+template <int WS>
+constexpr int kTileBN = WS < 0 ? kBN : 3 * kBN;
 constexpr int kS3LdsBytes = 2 * kS3BufBytes + kConstFloats * 4;
 // first float of the constants table (bias | scale | shift) in a block's LDS
 template <bool S3>
@@ -427,10 +431,32 @@ __device__ __forceinline__ void s3_item(const Ctx& cx, const char* S, int rd3, f
     if constexpr (i == G - 1) s3_wld(cx, w, c_next, s, n_chunks);
 }
 
+#ifdef XVEC_KNOCK
+// Timing-only knock-outs, compile time (-DXVEC_KNOCK=mask, the convention and the bit space of tdnn_pp16.hip; results are
+// garbage), in the POOLING instantiation only, so that layer 4 still feeds layer 5 real data.  A knocked head does no s3_gld and
+// no s3_store (no row loads, no split, no LDS stores); the products then run on what the LDS buffers hold (in these builds the
+// block prologue puts the planes of chunk 0 into both).  The step of the load stream, the barrier, weight loads, fragment reads,
+// MFMAs and the epilogue stay.  No address changes.
+//   bit 20: EVERY block: the head knocked in two of every three chunks, counted through the block's tiles (a third of the
+//           head work per MFMA in every block, with no cost of sharing it: the upper bound on a 384-channel tile,
+//           profiles/split3_wide_bound.txt)
+//   bit 21: EVERY block: every head knocked (what the head costs altogether)
+#define XV_S3_KNOCK ((XVEC_KNOCK & ((1 << 20) | (1 << 21))) != 0)
+// (POOL_: the instantiation pools; G0_: the tile's first row group; NCH_: chunks per tile; IT_: the chunk)
+#define XV_S3_HEAD_LIVE(POOL_, G0_, NCH_, IT_) \
+    (!(POOL_) || !XV_S3_KNOCK || ((XVEC_KNOCK & (1 << 21)) == 0 && ((IT_) + (int)(((G0_) >> 2) % 3) * (NCH_)) % 3 == 0))
+#else
+#define XV_S3_KNOCK 0
+#define XV_S3_HEAD_LIVE(POOL_, G0_, NCH_, IT_) true
+#endif
+
 // One K-chunk: chunk `it` is in LDS buffer P, its weights in rg.w3; staging set N holds chunk it + 1, which goes to
 // buffer N (free: every wave passed the previous chunk's barrier after its last fragment read), then set N is refilled
 // with the chunk the stream points at next.  The order of the products into each accumulator is the chunk's k-steps in
 // turn, whatever the order of the row groups around them.
+// WS >= 0 (the 384-channel tile on twelve waves, tdnn_split3w.hip): only the wave set whose parity the chunk has (WS == P) does
+// this head, and its load stream steps TWO chunks, so its one staging set holds chunk it + 1 when the head of chunk it starts
+// and chunk it + 3 behind it; set 2 has no head in any chunk.  Everything behind the head is the same code for every wave.
 #define XV_S3_ITEM(i_, s_, IT_)                                                                           \
     if constexpr (G > i_) { s3_item<G, s_ * G + i_>(cx, S, ln.rd3, acc##i_, xf, rg.w3, (IT_) + 1, n_chunks); SB(); }
 #define XV_S3_CHUNK(P_, N_, IT_)                                                                          \
@@ -439,12 +465,18 @@ __device__ __forceinline__ void s3_item(const Ctx& cx, const char* S, int rd3, f
         char* Sn = reinterpret_cast<char*>(smem) + N_ * kS3BufBytes;                                      \
         float4 xf[2][3];                                                                                  \
         s3_frag(S, ln.rd3, 0, 0, xf[0]);                                                                  \
-        if constexpr (G > 0) s3_store(Sn, ln.st3, 0, rg.sA0_0);                                           \
-        if constexpr (G > 1) s3_store(Sn, ln.st3, 1, rg.sA1_0);                                           \
-        if constexpr (G > 2) s3_store(Sn, ln.st3, 2, rg.sA2_0);                                           \
-        if constexpr (G > 3) s3_store(Sn, ln.st3, 3, rg.sA3_0);                                           \
-        advance<GUARD, false>(a, cx, n_chunks);                                                           \
-        s3_gld<G>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);                                         \
+        if constexpr (WS < 0 || WS == P_) {  /* the wave sets of the 384-channel tile: head in the chunks of their parity */ \
+            const bool head_ = XV_S3_HEAD_LIVE(POOL, g0, n_chunks, IT_); /* true but in knock-out builds */                                              \
+            if (head_) {                                                                                  \
+                if constexpr (G > 0) s3_store(Sn, ln.st3, 0, rg.sA0_0);                                   \
+                if constexpr (G > 1) s3_store(Sn, ln.st3, 1, rg.sA1_0);                                   \
+                if constexpr (G > 2) s3_store(Sn, ln.st3, 2, rg.sA2_0);                                   \
+                if constexpr (G > 3) s3_store(Sn, ln.st3, 3, rg.sA3_0);                                   \
+            }                                                                                             \
+            advance<GUARD, false>(a, cx, n_chunks);                                                       \
+            if constexpr (WS >= 0) advance<GUARD, false>(a, cx, n_chunks);                                \
+            if (head_) s3_gld<G>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);                          \
+        }                                                                                                 \
         XV_S3_ITEM(0, 0, IT_) XV_S3_ITEM(1, 0, IT_) XV_S3_ITEM(2, 0, IT_) XV_S3_ITEM(3, 0, IT_)           \
         XV_S3_ITEM(0, 1, IT_) XV_S3_ITEM(1, 1, IT_) XV_S3_ITEM(2, 1, IT_) XV_S3_ITEM(3, 1, IT_)           \
         __syncthreads(); /* chunk it+1 complete in LDS; chunk it's buffer is free */                     \
@@ -452,12 +484,37 @@ __device__ __forceinline__ void s3_item(const Ctx& cx, const char* S, int rd3, f
 
 // Once per block: chunk 0 of the first tile -> LDS buffer 0, its first fragments -> set 0,
 // chunks 1 and 2 in flight in the two staging sets (bf16x3: chunk 1 in its single set).
-template <int GUARD, bool INBF, bool X3, bool S3>
+template <int GUARD, bool INBF, bool X3, bool S3, int WS = -1>
 __device__ __forceinline__ void block_prologue(const TdnnArgs& a, float* smem, Ctx& cx, Regs& rg, const Lane& ln,
                                                int n_chunks) {
     constexpr int G = 4;   // fetch all four row groups: rows past a short first tile are allocated
     constexpr int ES = INBF ? 2 : 4, BKE = 128 / ES;
     const int h = ln.h, sw = ln.sw, a_rd = ln.a_rd, b_rd = ln.b_rd, st_off = ln.st_off, c = ln.c;
+    if constexpr (S3 && WS >= 0) {
+        // the 384-channel tile (tdnn_split3w.hip).  Wave set 1 (head in the odd chunks) stages the even chunks: chunk 0 -> LDS
+        // buffer 0, chunk 2 in flight; set 0 stages the odd ones: chunk 1 in flight; set 2 never stages.  Weights of chunk 0.
+        if constexpr (WS == 1) {
+            s3_gld<4>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);
+            s3_wld(cx, rg.w3, 0, 0, n_chunks);
+            s3_wld(cx, rg.w3, 0, 1, n_chunks);
+            s3_store(reinterpret_cast<char*>(smem), ln.st3, 0, rg.sA0_0);
+            s3_store(reinterpret_cast<char*>(smem), ln.st3, 1, rg.sA1_0);
+            s3_store(reinterpret_cast<char*>(smem), ln.st3, 2, rg.sA2_0);
+            s3_store(reinterpret_cast<char*>(smem), ln.st3, 3, rg.sA3_0);
+            advance<GUARD, false>(a, cx, n_chunks);
+            advance<GUARD, false>(a, cx, n_chunks);
+            s3_gld<4>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);
+        } else {
+            if constexpr (WS == 0) {
+                advance<GUARD, false>(a, cx, n_chunks);
+                s3_gld<4>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);
+            }
+            s3_wld(cx, rg.w3, 0, 0, n_chunks);
+            s3_wld(cx, rg.w3, 0, 1, n_chunks);
+        }
+        __syncthreads();
+        return;
+    }
     if constexpr (S3) {      // chunk 0 -> LDS buffer 0 (split), chunk 1 in flight in the one staging set, weights of chunk 0
         char* B0 = reinterpret_cast<char*>(smem);
         s3_gld<4>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);
@@ -467,6 +524,12 @@ __device__ __forceinline__ void block_prologue(const TdnnArgs& a, float* smem, C
         s3_store(B0, ln.st3, 1, rg.sA1_0);
         s3_store(B0, ln.st3, 2, rg.sA2_0);
         s3_store(B0, ln.st3, 3, rg.sA3_0);
+        if constexpr (XV_S3_KNOCK) {      // knock-out builds: real planes in buffer 1 too (the first head overwrites them if it runs)
+            s3_store(B0 + kS3BufBytes, ln.st3, 0, rg.sA0_0);
+            s3_store(B0 + kS3BufBytes, ln.st3, 1, rg.sA1_0);
+            s3_store(B0 + kS3BufBytes, ln.st3, 2, rg.sA2_0);
+            s3_store(B0 + kS3BufBytes, ln.st3, 3, rg.sA3_0);
+        }
         advance<GUARD, false>(a, cx, n_chunks);
         s3_gld<4>(a, cx, rg.sA0_0, rg.sA1_0, rg.sA2_0, rg.sA3_0);
         __syncthreads();
@@ -500,10 +563,11 @@ __device__ __forceinline__ void block_prologue(const TdnnArgs& a, float* smem, C
 
 // One tile of G row groups (32 frames each) x 128 channels, starting at row group g0.  On entry
 // the pipeline is primed for this tile (block_prologue or the previous tile's last chunks).
-template <int G, int GUARD, bool POOL, bool STORE, bool INBF, bool OUTBF, bool X3, bool S3>
+template <int G, int GUARD, bool POOL, bool STORE, bool INBF, bool OUTBF, bool X3, bool S3, int WS = -1>
 __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx& cx, Regs& rg, const Lane& ln,
                                              int64_t g0, int n0, int n_chunks) {
     constexpr int ES = INBF ? 2 : 4, BKE = 128 / ES;
+    constexpr int BN = kTileBN<WS>;      // channels of the block's tile = stride of the constants table
     const int h = ln.h, sw = ln.sw, a_rd = ln.a_rd, b_rd = ln.b_rd, st_off = ln.st_off, c = ln.c;
     // bf16 in, bf16 out, one plane, stored: the transposed product (channels in the accumulator's registers), so
     // that a lane ends up with 8 consecutive channels of one frame = one 16-byte store.  With frames in the
@@ -524,7 +588,7 @@ __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx
         // accumulators start at bias - K, K = the block's pooling pivot of this lane's channel (at 0 in the block's
         // first tile, whose epilogue picks K and adds bias - K: a large bias must not sit in the accumulator while
         // the K loop adds small terms to it -- every MFMA would round at ulp(bias)): tdnn_common.h, pool_group_impl
-        const float b0 = smem[kCstFloat<S3> + kBN + (ln.col - n0)];
+        const float b0 = smem[kCstFloat<S3> + BN + (ln.col - n0)];
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc0[e] = b0;
         acc1 = acc0; acc2 = acc0; acc3 = acc0;
@@ -564,7 +628,7 @@ __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx
     // epilogue constants of this lane's channel: three LDS reads per tile instead of three registers held
     // across the K loop (the pooling and first-layer variants were 3-6 registers over the 256 budget)
     float* cst = smem + kCstFloat<S3> + (col - n0);
-    const float bi = cst[0], sc = cst[kBN], sh = cst[2 * kBN];
+    const float bi = cst[0], sc = cst[BN], sh = cst[2 * BN];
     // pooling variants: the three slots are bias | bias - K | -K (this wave's own channels: no barrier)
     float negk = sh;
     if constexpr (POOL) {
@@ -585,8 +649,8 @@ __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx
                 if constexpr (G > 2) acc2[e] += bmk;
                 if constexpr (G > 3) acc3[e] += bmk;
             }
-            cst[kBN] = bmk;
-            cst[2 * kBN] = negk;
+            cst[BN] = bmk;
+            cst[2 * BN] = negk;
             cx.pivot_set = true;
         }
     }
@@ -665,8 +729,9 @@ __device__ __forceinline__ void process_tile(const TdnnArgs& a, float* smem, Ctx
 #endif
 }
 
-template <int GUARD, bool POOL, bool STORE, bool INBF, bool OUTBF, bool X3, bool S3>
+template <int GUARD, bool POOL, bool STORE, bool INBF, bool OUTBF, bool X3, bool S3, int WS = -1>
 __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
+    constexpr int BN = kTileBN<WS>;
 #ifdef XVEC_DIAG
     const unsigned long long t_entry = __builtin_amdgcn_s_memtime(), r_entry = __builtin_amdgcn_s_memrealtime();
     if (threadIdx.x == 0 && blockIdx.x < 8192) { g_diag[blockIdx.x * 8 + 3] = 0; g_diag[blockIdx.x * 8 + 4] = 0; g_diag[blockIdx.x * 8 + 5] = 0; }
@@ -678,7 +743,7 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
     const int p = lid / a.n_tiles;
     int64_t g_begin, g_end;
     group_range(a, p, g_begin, g_end);
-    const int n0 = j * kBN;
+    const int n0 = j * BN;
     const int n_chunks = a.n_taps * a.cpt;
 
     const int tid = threadIdx.x;
@@ -688,7 +753,7 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
     const int r = lane & 31;
     // staging map: thread -> (row r0 + 32*j, 16-byte chunk c) of a 32-wide K chunk
     ln.c = tid & 7;
-    ln.r0 = tid >> 3;
+    ln.r0 = WS < 0 ? tid >> 3 : (tid & 255) >> 3;      // twelve waves: the 256-thread map within each wave set
     ln.st_off = ln.r0 * kBK + ((ln.c ^ ((ln.r0 >> 1) & 7)) << 2);
     // fragment read map: row (base + r), logical 16-B chunk 2q+h, swizzled by row
     ln.sw = (r >> 1) & 7;
@@ -698,10 +763,10 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
     // bf16_split3 planes: 64-byte rows, 16-byte piece q of row r stored at piece q ^ ((r >> 2) & 3)
     ln.st3 = ln.r0 * 64 + ((((ln.c >> 1) ^ ((ln.r0 >> 2) & 3)) * 16) | ((ln.c & 1) * 8));
     ln.rd3 = r * 64 + ((ln.h ^ ((r >> 2) & 3)) * 16);
-    if (tid < kBN) {
+    if (tid < BN) {
         smem[kCstFloat<S3> + tid] = a.bias[n0 + tid];
-        smem[kCstFloat<S3> + kBN + tid] = POOL ? 0.f : a.scale[n0 + tid];
-        smem[kCstFloat<S3> + 2 * kBN + tid] = POOL ? 0.f : a.shift[n0 + tid];
+        smem[kCstFloat<S3> + BN + tid] = POOL ? 0.f : a.scale[n0 + tid];
+        smem[kCstFloat<S3> + 2 * BN + tid] = POOL ? 0.f : a.shift[n0 + tid];
     }
 
     Ctx cx;
@@ -738,13 +803,13 @@ __device__ __forceinline__ void tdnn_body(const TdnnArgs& a, float* smem) {
     cx.itl = 0;
 
     Regs rg;
-    block_prologue<GUARD, INBF, X3, S3>(a, smem, cx, rg, ln, n_chunks);
+    block_prologue<GUARD, INBF, X3, S3, WS>(a, smem, cx, rg, ln, n_chunks);
     int64_t g = g_begin;
-    for (; g + 4 <= g_end; g += 4) process_tile<4, GUARD, POOL, STORE, INBF, OUTBF, X3, S3>(a, smem, cx, rg, ln, g, n0, n_chunks);
+    for (; g + 4 <= g_end; g += 4) process_tile<4, GUARD, POOL, STORE, INBF, OUTBF, X3, S3, WS>(a, smem, cx, rg, ln, g, n0, n_chunks);
     const int rem = (int)(g_end - g);
-    if (rem == 3) process_tile<3, GUARD, POOL, STORE, INBF, OUTBF, X3, S3>(a, smem, cx, rg, ln, g, n0, n_chunks);
-    else if (rem == 2) process_tile<2, GUARD, POOL, STORE, INBF, OUTBF, X3, S3>(a, smem, cx, rg, ln, g, n0, n_chunks);
-    else if (rem == 1) process_tile<1, GUARD, POOL, STORE, INBF, OUTBF, X3, S3>(a, smem, cx, rg, ln, g, n0, n_chunks);
+    if (rem == 3) process_tile<3, GUARD, POOL, STORE, INBF, OUTBF, X3, S3, WS>(a, smem, cx, rg, ln, g, n0, n_chunks);
+    else if (rem == 2) process_tile<2, GUARD, POOL, STORE, INBF, OUTBF, X3, S3, WS>(a, smem, cx, rg, ln, g, n0, n_chunks);
+    else if (rem == 1) process_tile<1, GUARD, POOL, STORE, INBF, OUTBF, X3, S3, WS>(a, smem, cx, rg, ln, g, n0, n_chunks);
 #ifdef XVEC_DIAG
     if (threadIdx.x == 0 && blockIdx.x < 8192) {
         __builtin_amdgcn_s_waitcnt(0);

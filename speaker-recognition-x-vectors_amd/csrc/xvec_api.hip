@@ -54,6 +54,10 @@ struct Policy {
     int split3_min_rows;    // XVEC_SPLIT3_MIN_ROWS: ... which take bf16_split3 from this many output rows per CU on
     bool wino_split3;       // XVEC_WINO_SPLIT3=0 forces the fp32 operands of the Winograd form (tdnn_wino.hip)
     int wino_s3_min_rows;   // XVEC_WINO_SPLIT3_MIN_ROWS: ... which takes bf16_split3 operands from this many output rows per CU on
+    // (the next two: tdnn_split3w_knobs, tdnn_split3w.hip)
+    bool split3_wide;       // XVEC_SPLIT3_WIDE=0 keeps the pooling bf16_split3 layer on the four-wave kernel (the A/B switch)
+    int split3w_min_rows;   // XVEC_SPLIT3_WIDE_MIN_ROWS: ... which takes the 384-channel tile from this many output rows per CU on
+                            // (a knob of its own: XVEC_SPLIT3_MIN_ROWS does not move it)
 };
 
 int env_int(const char* name, int unset) {
@@ -64,10 +68,13 @@ int env_int(const char* name, int unset) {
 Policy read_policy() {
     const int tenths = env_int("XVEC_PP_MIN_TENTHS", 18), s3_rows = env_int("XVEC_SPLIT3_MIN_ROWS", kSplit3MinRowsPerCu);
     const int ws3_rows = env_int("XVEC_WINO_SPLIT3_MIN_ROWS", kWinoS3MinRowsPerCu);
+    bool s3w_on = true;       // the 384-channel tile's two knobs and its default threshold live with the kernel (tdnn_split3w.hip)
+    int s3w_rows = 0;
+    tdnn_split3w_knobs(&s3w_on, &s3w_rows);
     return {std::max(0, env_int("XVEC_BLOCKS_PER_CU", 0)), env_int("XVEC_PP", 1) != 0, tenths > 0 ? tenths : 18,
             env_int("XVEC_PP_CU_PCT", 0), env_int("XVEC_WINOGRAD", 1) != 0, env_int("XVEC_SPLIT3", 1) != 0,
             s3_rows >= 0 ? s3_rows : kSplit3MinRowsPerCu, env_int("XVEC_WINO_SPLIT3", 1) != 0,
-            ws3_rows >= 0 ? ws3_rows : kWinoS3MinRowsPerCu};
+            ws3_rows >= 0 ? ws3_rows : kWinoS3MinRowsPerCu, s3w_on, s3w_rows};
 }
 
 // RAII: the calling thread's current device is whatever it was before the call
@@ -129,6 +136,7 @@ struct xvec_handle {
     int split3_blocks_cu;              // blocks of tdnn_split3_kernel the device holds per CU, at most 3 (asked once, xvec_create)
     Policy pol;
     bool wino_s3w_fits;                // the device holds one 512-thread block of tdnn_wino_s3w_kernel per CU (asked once, xvec_create)
+    bool split3w_fits;                 // ... and one 768-thread block of tdnn_split3w_kernel
     int last_threads[XVEC_NUM_TDNN], last_blocks[XVEC_NUM_TDNN];   // block size and grid of that launch, where the planner sizes the grid (xvec_get_tdnn_launch)
     int last_kernel[XVEC_NUM_TDNN];    // XVEC_KERNEL_* the last launch of each frame-level layer went to (xvec_get_dispatch)
     int last_form[XVEC_NUM_TDNN];      // XVEC_FORM_* of that launch (xvec_get_tdnn_form)
@@ -297,7 +305,7 @@ struct LayerCall {
     int64_t rows_out;
 };
 
-enum class Launch { kDirect, kPp16, kFirst, kFirst3, kSplit3, kWino, kWinoS3, kWinoS3W };
+enum class Launch { kDirect, kPp16, kFirst, kFirst3, kSplit3, kSplit3W, kWino, kWinoS3, kWinoS3W };
 
 // What plan_layer chose for a call: the kernel, its complete arguments, and what the launch reports.
 struct LayerPlan {
@@ -383,6 +391,16 @@ int plan_layer(const xvec_handle* h, const LayerCall& c, LayerPlan& lp) {
         a.Wf = h->Wp3[l];
         // three blocks per CU (50 688 B of LDS, 168 registers): a third instruction stream per SIMD for the matrix pipe
         persistent_grid(h, blocks_per_cu(h, true), a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
+        // ... the pooling layer on tiles of 384 channels, twelve waves, one block per CU (tdnn_split3w.hip: a third of the staging
+        // work per MFMA; CUs / 4 blocks per column = 3 CUs / 12, the same row ranges, so the same bits) where the width allows,
+        // the device holds the block and the batch is large; XVEC_BLOCKS_PER_CU keeps the four-wave grid.  Layer 4 (N = 512)
+        // stays on the four-wave kernel.
+        if (pool && h->split3w_fits && h->pol.split3_wide && h->pol.blocks_per_cu == 0 && tdnn_split3w_applicable(g) &&
+            c.rows_out >= (int64_t)h->pol.split3w_min_rows * h->num_cu) {
+            lp.launch = Launch::kSplit3W;
+            a.n_tiles = g.n_pad / 384;
+            persistent_grid(h, 1, a.n_tiles, a.groups_total, &a.blocks_per_col, &a.pair_period);
+        }
     } else if (!bf && from_act && !pool && h->pol.wino && h->Wu[l] && tdnn_wino_applicable(g, c.ldx)) {
         // fp32, three equally spaced taps: Winograd F(2,3) along time (tdnn_wino.hip), 2/3 of the direct form's products; the
         // same kernel family (persistent fp32, 128 x 128 output tiles)
@@ -442,6 +460,7 @@ int launch_layer(xvec_handle* h, const LayerPlan& lp, hipStream_t s) {
         case Launch::kFirst: HIP_TRY(launch_tdnn_first(lp.a, h->num_cu, s)); break;
         case Launch::kFirst3: HIP_TRY(launch_tdnn_first3(lp.a, h->num_cu, s)); break;
         case Launch::kSplit3: HIP_TRY(launch_tdnn_split3(lp.a, pool, s)); break;
+        case Launch::kSplit3W: HIP_TRY(launch_tdnn_split3w(lp.a, s)); break;
         case Launch::kWino: HIP_TRY(launch_tdnn_wino(lp.a, s)); break;
         case Launch::kWinoS3: HIP_TRY(launch_tdnn_wino_s3(lp.a, s)); break;
         case Launch::kWinoS3W: HIP_TRY(launch_tdnn_wino_s3w(lp.a, s)); break;
@@ -449,7 +468,7 @@ int launch_layer(xvec_handle* h, const LayerPlan& lp, hipStream_t s) {
     }
     // (the 128x128 family and its 256-channel Winograd tiling; the streaming and ping-pong kernels keep their own block shapes)
     const bool sized = lp.launch != Launch::kFirst && lp.launch != Launch::kFirst3 && lp.launch != Launch::kPp16;
-    h->last_threads[lp.layer] = lp.launch == Launch::kWinoS3W ? 512 : sized ? 256 : 0;
+    h->last_threads[lp.layer] = lp.launch == Launch::kSplit3W ? 768 : lp.launch == Launch::kWinoS3W ? 512 : sized ? 256 : 0;
     h->last_blocks[lp.layer] = sized ? lp.a.blocks_per_col * lp.a.n_tiles : 0;
     h->last_kernel[lp.layer] = lp.kernel;
     h->last_form[lp.layer] = lp.form;
@@ -790,6 +809,13 @@ int xvec_create(const xvec_cfg* cfg, xvec_handle** out) {
         return g_err.fail(XVEC_ERR_HIP, "occupancy query of tdnn_wino_s3w_kernel failed: %s", hipGetErrorString(e));
     }
     h->wino_s3w_fits = s3w_blocks >= 1;
+    // ... and the twelve-wave split3 pooling block
+    int s3wide_blocks = 0;
+    if (hipError_t e = tdnn_split3w_max_blocks_per_cu(&s3wide_blocks); e != hipSuccess) {
+        delete h;
+        return g_err.fail(XVEC_ERR_HIP, "occupancy query of tdnn_split3w_kernel failed: %s", hipGetErrorString(e));
+    }
+    h->split3w_fits = s3wide_blocks >= 1;
     h->cin_pad = round_up(cfg->input_size, 4);
     fill_geometry(h, h->geo, 2 * kBK);
     fill_geometry(h, h->geo16, 4 * kBK);

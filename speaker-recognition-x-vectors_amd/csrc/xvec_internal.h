@@ -128,6 +128,14 @@ hipError_t launch_tdnn(const TdnnArgs& a, TdnnMode m, hipStream_t s);
 hipError_t launch_tdnn_split3(const TdnnArgs& a, bool pool, hipStream_t s);
 // blocks of it (the fewer of its two variants) the current device keeps resident per CU, at its block and LDS size
 hipError_t tdnn_split3_max_blocks_per_cu(int* blocks);
+// ... its pooling variant on tiles of 128 rows x 384 channels, twelve waves, ONE block per CU (tdnn_split3w.hip): the same
+// arguments with n_tiles = n_pad / 384 (n_pad % 384 == 0: tdnn_split3w_applicable); the same bits
+bool tdnn_split3w_applicable(const TdnnGeom& g);
+// its dispatch knobs, read from the environment (once per handle, read_policy): XVEC_SPLIT3_WIDE=0 switches the tile off,
+// XVEC_SPLIT3_WIDE_MIN_ROWS = the output rows per CU from which the pooling layer takes it (unset or negative: the default)
+void tdnn_split3w_knobs(bool* enabled, int* min_rows_per_cu);
+hipError_t tdnn_split3w_max_blocks_per_cu(int* blocks);
+hipError_t launch_tdnn_split3w(const TdnnArgs& a, hipStream_t s);
 // Large-batch bf16 mapping (tdnn_pp16.hip, v_mfma_f32_16x16x32_bf16): 256-channel columns, 64-frame units.  Reads TdnnArgs with
 //   W = K-tile major bf16 [n_pad/256][k_pad/64][256][64] (K order as the fp32 packing, 64-element chunks), n_tiles = n_pad / 256,
 //   groups_total = ceil(rows / 64) units, blocks_per_col ranges per column (>= 1.8 units each: the measured crossover with the 128x128 kernel).

@@ -704,7 +704,7 @@ class XVectorModel(nn.Module):
 
     def last_launches(self, device=None) -> list:
         """(threads per block, blocks) of the last launch of each frame-level layer; (0, 0) where the library does not size the
-        grid.  512 threads: the Winograd bf16_split3 form on 256-channel tiles (csrc/tdnn_wino_s3w.hip)."""
+        grid.  512 threads: the Winograd bf16_split3 form on 256-channel tiles (csrc/tdnn_wino_s3w.hip); 768: fp32 layer 5 as bf16_split3 on 384-channel tiles (csrc/tdnn_split3w.hip)."""
         dev = torch.device(device) if device is not None else next(self.parameters()).device
         eng = self._engine(dev)
         thr, blk = (C.c_int * 8)(), (C.c_int * 8)()
