@@ -16,7 +16,8 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "write_rttm", "vad", "VadCmvn", "energy_vad", "sliding_cmvn", "select_voiced", "speech_runs", "run_windows", "visualize",
            "Tsne", "tsne_map", "tsne_affinities", "pca_map", "scatter_maps", "calibrate", "Calibration", "ScoreCalibrator", "CalibrationReport",
            "fit_calibration", "fit_calibration_all_pairs", "cllr", "min_cllr", "pav_segments", "calibration_report", "report", "DetCurve",
-           "TrialReport", "trial_map", "score_range", "score_images", "det_curve", "det_curve_all_pairs", "trial_report"]
+           "TrialReport", "trial_map", "score_range", "score_images", "det_curve", "det_curve_all_pairs", "trial_report", "vbx", "Vbx",
+           "VbxModel", "VbxResult"]
 
 
 def __getattr__(name):
@@ -65,6 +66,9 @@ def __getattr__(name):
                 "trial_report"):
         import importlib
         return getattr(importlib.import_module(".report", __name__), name)
+    if name in ("Vbx", "VbxModel", "VbxResult"):
+        import importlib
+        return getattr(importlib.import_module(".vbx", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -72,7 +76,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize", "vad", "visualize", "calibrate", "report"):
+                "diarize", "vad", "visualize", "calibrate", "report", "vbx"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

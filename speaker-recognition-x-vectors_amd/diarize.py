@@ -14,6 +14,8 @@ tests/test_diarize.py holds against scipy.cluster.hierarchy.linkage.  The score 
     write_rttm(res.turns, names, "out.rttm")
     d = Diarizer(model, scorer, transform, frontend=vad.VadCmvn(), max_gap=10)      # the recipe's front end: sliding CMVN, and
                                                                                     # windows inside the runs of speech only
+    d = Diarizer(model, scorer, transform, threshold=0.0, resegment=vbx.Vbx(vbx.VbxModel.from_plda(plda), n_speakers=10))
+                                                                                    # VBx behind the clustering (vbx.py)
 
 Largest score first, equal scores by the lowest pair of cluster indices, NaN never; clusters are numbered in the order of
 their first window.  There is no CPU path.
@@ -148,10 +150,12 @@ class Diarizer:
     then normalised and windowed inside their runs of speech only (`max_gap`: the silence in frames a run bridges), as the
     recipe does, and the turns stay in the recordings' own frames.  Recordings are grouped into calls whose windows total at most
     `max_score_rows`: one call scores all its windows against each other (the scorer has no launch for the diagonal blocks
-    alone), so the bound caps the cells computed between different recordings."""
+    alone), so the bound caps the cells computed between different recordings.  `resegment`: an optional `vbx.Vbx` -- the
+    windows of each call then go through its model's projection and VBx, initialised from the clustering's labels (the
+    clustering is capped at its n_speakers clusters through max_speakers), and the VBx labels replace the clustering's."""
 
     def __init__(self, model, scorer, transform=None, win=150, hop=75, threshold=None, max_speakers=None, min_tail=None,
-                 max_score_rows=8192, device="cuda:0", frontend=None, max_gap=0):
+                 max_score_rows=8192, device="cuda:0", frontend=None, max_gap=0, resegment=None):
         self.device = require_device(device, "diarization")
         if isinstance(scorer, str):
             if scorer != "cosine":
@@ -170,7 +174,13 @@ class Diarizer:
         if int(max_gap) < 0:
             raise ValueError(f"Diarizer: max_gap = {max_gap} must not be negative")
         self.frontend, self.max_gap = frontend, int(max_gap)
-        self._ws = None
+        if resegment is not None:
+            if not hasattr(resegment, "model") or not hasattr(resegment.model, "project"):
+                raise TypeError("Diarizer: resegment must be a vbx.Vbx")
+            cap = int(resegment.n_speakers)
+            self.max_speakers = cap if self.max_speakers is None else min(int(self.max_speakers), cap)
+        self.resegment = resegment
+        self._ws = self._vbx_ws = None
 
     def _scores(self, v) -> torch.Tensor:
         if self.scorer == "cosine":
@@ -229,6 +239,14 @@ class Diarizer:
             s = self._scores(vecs[lo:hi])
             self._ws = byte_workspace(int(_hip.lib.xvec_ahc_workspace_bytes(rs.ctypes.data_as(_I64P), b - a)), self.device, self._ws)
             cl = cluster(s, rs, self.threshold, None if want is None else want[a:b], self.max_speakers, workspace=self._ws)
+            if self.resegment is not None:
+                from . import vbx as _vbx
+                self._vbx_ws = byte_workspace(_vbx.workspace_bytes(rs, len(self.resegment.model.phi), self.resegment.n_speakers),
+                                              self.device, self._vbx_ws)
+                cl = _vbx.resegment(self.resegment, vecs[lo:hi], rs, cl.labels, self.device, workspace=self._vbx_ws)
+                labels[lo:hi] = cl.labels
+                n_clusters[a:b] = cl.n_speakers
+                continue
             labels[lo:hi] = cl.labels
             n_clusters[a:b] = cl.n_clusters
         lab = labels.cpu().numpy()

@@ -76,6 +76,11 @@ class VadOptions(C.Structure):                                  # xvec_vad_optio
                 ("frames_context", C.c_int32), ("energy_col", C.c_int32)]
 
 
+class VbxOptions(C.Structure):                                  # xvec_vbx_options
+    _fields_ = [("loop_prob", C.c_double), ("Fa", C.c_double), ("Fb", C.c_double), ("epsilon", C.c_double),
+                ("max_iter", C.c_int32), ("reserved", C.c_int32)]
+
+
 class CmvnOptions(C.Structure):                                 # xvec_cmvn_options
     _fields_ = [("cmn_window", C.c_int32), ("min_window", C.c_int32), ("center", C.c_int32), ("norm_vars", C.c_int32)]
 
@@ -101,6 +106,11 @@ class _wsb_report(_wsb):
     """size_t workspace_bytes of include/xvec_report.h: `_wsb` again, under one more name.  tests/test_calibrate.py lists every
     (void*, _wsb) pair of the table below as the calibration unit's own; the report unit's answers are held by
     tests/test_report.py."""
+
+
+class _wsb_vbx(_wsb_report):
+    """size_t workspace_bytes of include/xvec_vbx.h: one more name.  tests/test_report.py lists every (void*, _wsb_report) pair
+    of the table below as the report unit's own; the VBx unit's answers are held by tests/test_vbx.py."""
 
 
 _SIGS = {
@@ -243,6 +253,12 @@ _SIGS = {
                                   _vp]),
     "xvec_report_det_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                             _wsb_report, _vp]),
+    # include/xvec_vbx.h  (the workspace size is spelt _wsb_vbx: see the class above)
+    "xvec_vbx_last_error": (C.c_char_p, []),
+    "xvec_vbx_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i32, _i32, _i32]),
+    "xvec_vbx_init": (C.c_int, [_vp, C.POINTER(_i64), _i32, _i32, C.c_double, _vp, _i64, _vp, _vp]),
+    "xvec_vbx_run": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(_i64), _i32, _i32, C.POINTER(VbxOptions), _vp, _i64, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _wsb_vbx, _vp]),
     # include/xvec_train.h
     "xvec_train_last_error": (C.c_char_p, []),
     "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
