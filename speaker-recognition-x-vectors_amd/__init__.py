@@ -17,7 +17,7 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "Tsne", "tsne_map", "tsne_affinities", "pca_map", "scatter_maps", "calibrate", "Calibration", "ScoreCalibrator", "CalibrationReport",
            "fit_calibration", "fit_calibration_all_pairs", "cllr", "min_cllr", "pav_segments", "calibration_report", "report", "DetCurve",
            "TrialReport", "trial_map", "score_range", "score_images", "det_curve", "det_curve_all_pairs", "trial_report", "vbx", "Vbx",
-           "VbxModel", "VbxResult"]
+           "VbxModel", "VbxResult", "der", "DerResult", "read_rttm"]
 
 
 def __getattr__(name):
@@ -69,6 +69,9 @@ def __getattr__(name):
     if name in ("Vbx", "VbxModel", "VbxResult"):
         import importlib
         return getattr(importlib.import_module(".vbx", __name__), name)
+    if name in ("DerResult", "read_rttm"):
+        import importlib
+        return getattr(importlib.import_module(".der", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -76,7 +79,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize", "vad", "visualize", "calibrate", "report", "vbx"):
+                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

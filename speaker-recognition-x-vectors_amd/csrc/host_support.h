@@ -1,5 +1,5 @@
 // Host-side plumbing of every C-ABI translation unit (xvec_api, mfcc, score, plda_train, eval, snorm, ident, diar, lda,
-// augment, resample, vad, tsne, calib, report, vbx, tdnn_train*, train_tail*): the error text behind a *_last_error() export, the workspace check,
+// augment, resample, vad, tsne, calib, report, vbx, der, tdnn_train*, train_tail*): the error text behind a *_last_error() export, the workspace check,
 // the CU count, and through plan_support.h the alignment, the workspace carver and a plan header's refusal (eval, calib and
 // report share theirs: trial_plan.h).  Host code only: nothing here is called from a kernel.
 #pragma once

@@ -1,4 +1,4 @@
-// What the host-only plan headers (diar_plan.h, vad_plan.h, tsne_plan.h, calib_plan.h, report_plan.h, vbx_plan.h, trial_plan.h) and the C-ABI translation units (through
+// What the host-only plan headers (diar_plan.h, vad_plan.h, tsne_plan.h, calib_plan.h, report_plan.h, vbx_plan.h, der_plan.h, trial_plan.h) and the C-ABI translation units (through
 // host_support.h) both need: the 256-byte alignment, the workspace carver, the reason of a refused argument check.  No HIP
 // header, so that the plan headers stay compilable by the host compiler alone (tests/abi/*_dump.cpp).
 #pragma once

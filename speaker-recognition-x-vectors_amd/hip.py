@@ -113,6 +113,11 @@ class _wsb_vbx(_wsb_report):
     of the table below as the report unit's own; the VBx unit's answers are held by tests/test_vbx.py."""
 
 
+class _wsb_der(_wsb_vbx):
+    """size_t workspace_bytes of include/xvec_der.h: one more name.  tests/test_vbx.py lists every (void*, _wsb_vbx) pair of the
+    table below as the VBx unit's own; the DER unit's answers are held by tests/test_der.py."""
+
+
 _SIGS = {
     "xvec_create": (C.c_int, [C.POINTER(Cfg), C.POINTER(_vp)]),
     "xvec_destroy": (None, [_vp]),
@@ -259,6 +264,13 @@ _SIGS = {
     "xvec_vbx_init": (C.c_int, [_vp, C.POINTER(_i64), _i32, _i32, C.c_double, _vp, _i64, _vp, _vp]),
     "xvec_vbx_run": (C.c_int, [_vp, _i64, _i32, _vp, C.POINTER(_i64), _i32, _i32, C.POINTER(VbxOptions), _vp, _i64, _vp, _vp, _vp,
                                _vp, _vp, _vp, _wsb_vbx, _vp]),
+    # include/xvec_der.h  (the workspace size is spelt _wsb_der: see the class above)
+    "xvec_der_last_error": (C.c_char_p, []),
+    "xvec_der_workspace_bytes": (C.c_size_t, [C.POINTER(_i64), _i32, _i64, _i64]),
+    "xvec_der_cooccurrence": (C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _wsb_der, _vp]),
+    "xvec_der_assign": (C.c_int, [_vp, _i32, _vp, _vp, _vp]),
+    "xvec_der_score": (C.c_int, [_vp, _i64, _vp, _i64, C.POINTER(_i64), _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _wsb_der,
+                                 _vp]),
     # include/xvec_train.h
     "xvec_train_last_error": (C.c_char_p, []),
     "xvec_tdnn_train_workspace_bytes": (C.c_size_t, [_i32, _i32, _i32, _i32, C.POINTER(_i32), _i32]),
