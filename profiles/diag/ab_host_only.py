@@ -40,14 +40,44 @@ def workspace_table(lib_path):
         "xvec_plda_em_workspace_bytes": ([i32, i32], [(10, 4), (1211, 150), (1, 1), (7000, 512), (33, 31), (0, 4)]),
         "xvec_eval_workspace_bytes": ([i64], [(1000,), (2**31 - 1,), (1,), (2048,), (2049,), (37720,), (4874 * 4874,), (0,),
                                               (2**31,)]),
+        "xvec_calib_workspace_bytes": ([i64], [(1,), (1000,), (37720,), (4874 * 4874,), (2**31 - 1,), (0,), (2**31,)]),
+        "xvec_report_det_workspace_bytes": ([i64], [(1,), (1000,), (37720,), (4874 * 4874,), (2**31 - 1,), (0,), (2**31,)]),
+        # rec_start: a tuple of the recordings' counts (passed as their running sum from 0), or None for a null pointer
+        "xvec_ahc_workspace_bytes": ([rec, i32], [((1,), 1), ((3, 4, 5), 3), ((64, 65, 1), 3), ((2048,), 1), ((2048,) * 64, 64),
+                                                  ((2049,), 1), ((3, 0, 2), 3), ((), 0), (None, 1)]),
+        "xvec_vbx_workspace_bytes": ([rec, i32, i32, i32], [((1,), 1, 1, 1), ((40, 50), 2, 128, 8), ((16384,), 1, 512, 64),
+                                                           ((16384,) * 16, 16, 512, 64), ((16385,), 1, 128, 8),
+                                                           ((40, 0), 2, 128, 8), ((40,), 1, 513, 8), ((40,), 1, 128, 65),
+                                                           ((40,), 1, 128, 0), ((), 0, 128, 8), (None, 1, 128, 8)]),
+        "xvec_der_workspace_bytes": ([rec, i32, i64, i64], [((1,), 1, 0, 0), ((100, 4097), 2, 3, 4), ((2**31 - 1,), 1, 5, 5),
+                                                           ((2**30, 2**30 - 1), 2, 2**31 - 1, 2**31 - 1), ((2**30, 2**30), 2, 1, 1),
+                                                           ((5, 0), 2, 1, 1), ((5,), 1, -1, 1), ((5,), 1, 1, 2**31), ((), 0, 1, 1),
+                                                           (None, 1, 1, 1)]),
     }
     out = {}
     for name, (argtypes, rows) in calls.items():
         fn = getattr(lib, name)
-        fn.restype, fn.argtypes = C.c_size_t, argtypes
+        fn.restype, fn.argtypes = C.c_size_t, [C.POINTER(i64) if t is rec else t for t in argtypes]
         for row in rows:
-            out[(name,) + row] = fn(*row)
+            out[(name,) + row] = fn(*(rec(a) if t is rec else a for t, a in zip(argtypes, row)))
     return out
+
+
+def show(arg):
+    """An argument of a row as the table prints it: a long run of one count as `(n,) * k`."""
+    if isinstance(arg, tuple) and len(arg) > 4 and len(set(arg)) == 1:
+        return f"({arg[0]},) * {len(arg)}"
+    return repr(arg)
+
+
+def rec(counts):
+    """rec_start of the recordings' `counts`, as the library reads it on the host."""
+    if counts is None:
+        return None
+    starts = [0]
+    for n in counts:
+        starts.append(starts[-1] + n)
+    return (C.c_int64 * len(starts))(*starts)
 
 
 def main():
@@ -65,7 +95,7 @@ def main():
     for key in a:
         same = a[key] == b[key]
         bad += not same
-        print(f"{key[0]}{key[1:]} = {a[key]}" + ("" if same else f"  DIFFERS: the other tree returns {b[key]}"))
+        print(f"{key[0]}({', '.join(map(show, key[1:]))}) = {a[key]}" + ("" if same else f"  DIFFERS: the other tree returns {b[key]}"))
     print(f"{len(mine)} translation units, {len(a)} workspace sizes: " + ("all equal" if not bad else f"{bad} differ"))
     return 1 if bad else 0
 

@@ -1,7 +1,10 @@
 """Host plumbing shared by every module that calls the library (model, frontend, scoring, plda, evaluate, snorm, identify,
 diarize, vbx, der, lda, augment, resample, vad, visualize, calibrate, report, train): error checks, the raw stream pointer, the pointer of an optional
-tensor, the device-only guard, host data onto the device, the check of a device score matrix, byte workspaces."""
+tensor, the device-only guard, host data onto the device, the check of a device score matrix, the check of a host rec_start,
+the pointer of a host int64 array, byte workspaces."""
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -58,6 +61,20 @@ def score_matrix(scores, what, shape="[n_rows, n_cols]", square=False) -> torch.
     if scores.shape[0] < 1 or scores.shape[1] < 1:
         raise ValueError(f"{what}: empty score matrix")
     return scores if scores.stride(1) == 1 and scores.stride(0) >= scores.shape[1] else scores.contiguous()
+
+
+def rec_start(rec_start, n, what, rows, unit) -> np.ndarray:
+    """`rec_start` as the library reads it on the host: contiguous int64 [n_rec + 1] rising from 0 to `n`, no recording empty.
+    `rows` says what the n are, `unit` what a recording is made of."""
+    rs = np.ascontiguousarray(np.asarray(rec_start), dtype=np.int64)
+    if rs.ndim != 1 or rs.shape[0] < 2 or rs[0] != 0 or rs[-1] != n or (np.diff(rs) < 1).any():
+        raise ValueError(f"{what}: rec_start must rise from 0 to the {n} {rows}, a {unit} or more per recording")
+    return rs
+
+
+def i64_ptr(a: np.ndarray):
+    """The `const int64_t*` of a contiguous host int64 array (rec_start, class_start); `a` must outlive the call."""
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))
 
 
 def byte_workspace(need, device, cached=None) -> torch.Tensor:

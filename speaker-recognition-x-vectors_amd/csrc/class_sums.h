@@ -58,6 +58,5 @@ inline int first_short_class(const int64_t* cs, int n_classes, int64_t min_rows)
 }
 
 inline int upload_class_start(int64_t* dev, const int64_t* host, int n_classes, hipStream_t s, ErrorChannel& err) {
-    const hipError_t e = hipMemcpyAsync(dev, host, (size_t)(n_classes + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    return e == hipSuccess ? XVEC_OK : err.fail(XVEC_ERR_HIP, "class_start copy failed: %s", hipGetErrorString(e));
+    return upload(dev, host, (size_t)(n_classes + 1), "class_start", s, err);
 }

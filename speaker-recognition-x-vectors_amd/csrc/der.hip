@@ -371,10 +371,9 @@ int front(const int32_t* ref_turns, int64_t m_ref, const int32_t* hyp_turns, int
     l = der_plan::make_layout(rec_start_host, n_rec);
     int rc;
     if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_derr))) return rc;
-    char* ws = static_cast<char*>(workspace);
-    hipError_t e = hipMemcpyAsync(ws + l.rec_start, rec_start_host, ((size_t)n_rec + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return g_derr.fail(XVEC_ERR_HIP, "rec_start copy failed: %s", hipGetErrorString(e));
-    e = hipMemsetAsync(ws + l.zero_from, 0, l.total - l.zero_from, s);
+    if ((rc = upload(part<int64_t>(workspace, l.rec_start), rec_start_host, (size_t)n_rec + 1, "rec_start", s, g_derr)))
+        return rc;
+    const hipError_t e = hipMemsetAsync(part<char>(workspace, l.zero_from), 0, l.total - l.zero_from, s);
     if (e != hipSuccess) return g_derr.fail(XVEC_ERR_HIP, "zeroing the workspace failed: %s", hipGetErrorString(e));
 
     RasterArgs ra{};
@@ -382,14 +381,14 @@ int front(const int32_t* ref_turns, int64_t m_ref, const int32_t* hyp_turns, int
     ra.m_ref = m_ref;
     ra.hyp = hyp_turns;
     ra.m_hyp = m_hyp;
-    ra.rec_start = reinterpret_cast<const i64*>(ws + l.rec_start);
+    ra.rec_start = part<const i64>(workspace, l.rec_start);
     ra.n_rec = n_rec;
     ra.collar = collar;
-    ra.ref_mask = reinterpret_cast<u64*>(ws + l.ref_mask);
-    ra.hyp_mask = reinterpret_cast<u64*>(ws + l.hyp_mask);
-    ra.noscore = reinterpret_cast<unsigned*>(ws + l.noscore);
-    ra.ignored = reinterpret_cast<u64*>(ws + l.ignored);
-    ra.blk_start = reinterpret_cast<int*>(ws + l.blk_start);
+    ra.ref_mask = part<u64>(workspace, l.ref_mask);
+    ra.hyp_mask = part<u64>(workspace, l.hyp_mask);
+    ra.noscore = part<unsigned>(workspace, l.noscore);
+    ra.ignored = part<u64>(workspace, l.ignored);
+    ra.blk_start = part<int>(workspace, l.blk_start);
     const der_plan::Launch rl = der_plan::raster_launch(m_ref, m_hyp);
     der_raster_kernel<<<(unsigned)rl.blocks, rl.threads, 0, s>>>(ra);
     if ((rc = g_derr.launch_ok("der_raster_kernel"))) return rc;
@@ -402,8 +401,8 @@ int front(const int32_t* ref_turns, int64_t m_ref, const int32_t* hyp_turns, int
     pa.ref_mask = ra.ref_mask;
     pa.hyp_mask = ra.hyp_mask;
     pa.noscore = ra.noscore;
-    pa.acc = reinterpret_cast<u64*>(ws + l.acc);
-    pa.cooc = reinterpret_cast<u64*>(ws + l.cooc);
+    pa.acc = part<u64>(workspace, l.acc);
+    pa.cooc = part<u64>(workspace, l.cooc);
     const der_plan::Launch pl = der_plan::pass_launch(rec_start_host, n_rec);
     der_pass_kernel<<<(unsigned)pl.blocks, pl.threads, 0, s>>>(pa);
     return g_derr.launch_ok("der_pass_kernel");
@@ -433,12 +432,11 @@ int xvec_der_cooccurrence(const int32_t* ref_turns, int64_t m_ref, const int32_t
     if ((rc = front(ref_turns, m_ref, hyp_turns, m_hyp, rec_start_host, n_rec, collar, skip_overlap, counts && cooc && ignored,
                     "counts / cooc / ignored", workspace, workspace_bytes, s, l)))
         return rc;
-    char* ws = static_cast<char*>(workspace);
     AssignArgs g{};
-    g.cooc_in = reinterpret_cast<const i64*>(ws + l.cooc);
+    g.cooc_in = part<const i64>(workspace, l.cooc);
     g.cooc_out = reinterpret_cast<i64*>(cooc);
-    g.acc = reinterpret_cast<const i64*>(ws + l.acc);
-    g.ign = reinterpret_cast<const i64*>(ws + l.ignored);
+    g.acc = part<const i64>(workspace, l.acc);
+    g.ign = part<const i64>(workspace, l.ignored);
     g.counts = reinterpret_cast<i64*>(counts);
     g.ignored_out = reinterpret_cast<i64*>(ignored);
     const der_plan::Launch al = der_plan::assign_launch(n_rec);
@@ -468,12 +466,11 @@ int xvec_der_score(const int32_t* ref_turns, int64_t m_ref, const int32_t* hyp_t
     if ((rc = front(ref_turns, m_ref, hyp_turns, m_hyp, rec_start_host, n_rec, collar, skip_overlap, counts && map && der && ignored,
                     "counts / map / der / ignored", workspace, workspace_bytes, s, l)))
         return rc;
-    char* ws = static_cast<char*>(workspace);
     AssignArgs g{};
-    g.cooc_in = reinterpret_cast<const i64*>(ws + l.cooc);
+    g.cooc_in = part<const i64>(workspace, l.cooc);
     g.cooc_out = reinterpret_cast<i64*>(cooc);
-    g.acc = reinterpret_cast<const i64*>(ws + l.acc);
-    g.ign = reinterpret_cast<const i64*>(ws + l.ignored);
+    g.acc = part<const i64>(workspace, l.acc);
+    g.ign = part<const i64>(workspace, l.ignored);
     g.counts = reinterpret_cast<i64*>(counts);
     g.map = map;
     g.der = der;

@@ -6,7 +6,7 @@
 #include <cstdint>
 
 #include "../../include/xvec_der.h"
-#include "plan_support.h"
+#include "rec_plan.h"
 
 namespace xvec {
 namespace der_plan {
@@ -20,15 +20,7 @@ static_assert(XVEC_DER_CHUNK_TICKS == XVEC_DER_THREADS * XVEC_DER_WAVE_ROWS, "th
 // rec_start [n_rec + 1]: from 0, every recording with a tick or more, fewer than 2^31 ticks in all.
 // 0, or 1 with the reason in why.
 inline int check_rec_start(const int64_t* rs, int32_t n_rec, Refusal& why) {
-    if (n_rec < 1) return why.refuse("n_rec = %d: need at least one recording", n_rec);
-    if (!rs) return why.refuse("null pointer: rec_start");
-    if (rs[0] != 0) return why.refuse("rec_start must begin at 0 (got %lld)", (long long)rs[0]);
-    for (int32_t r = 0; r < n_rec; ++r) {
-        if (rs[r + 1] - rs[r] < 1) return why.refuse("recording %d is empty or rec_start decreases: every recording needs a tick", r);
-        if (rs[r + 1] > 0x7fffffff)
-            return why.refuse("%lld ticks up to recording %d: the total must stay below 2^31", (long long)rs[r + 1], r);
-    }
-    return 0;
+    return rec_plan::check_rec_start(rs, n_rec, {"tick", 0, ""}, why);
 }
 
 // The turn counts of the two sides (a wave of the rasteriser each: their sum must leave the grid below 2^31 blocks).
@@ -115,10 +107,7 @@ inline Chunk block_chunk(const int64_t* rs, int32_t n_rec, int64_t block) {
     return Chunk{-1, -1, -1, 0};
 }
 
-struct Launch {
-    int64_t blocks;
-    int32_t threads;
-};
+using rec_plan::Launch;
 
 // The rasteriser: a wave per turn of either side, and one block more that lays out blk_start.
 inline Launch raster_launch(int64_t m_ref, int64_t m_hyp) {

@@ -354,18 +354,17 @@ int xvec_ahc_cluster(const double* S, int64_t ld, const int64_t* rec_start_host,
     int rc;
     if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_derr))) return rc;
 
-    char* ws = static_cast<char*>(workspace);
     AhcArgs g{};
     g.S = S;
     g.ld = ld;
     g.N = N;
     g.n_rec = n_rec;
-    g.rec_start = reinterpret_cast<const int64_t*>(ws + l.rec_start);
-    g.want = want_host ? reinterpret_cast<const int*>(ws + l.want) : nullptr;
-    g.mat_off = reinterpret_cast<int64_t*>(ws + l.mat_off);
-    g.best_v = reinterpret_cast<double*>(ws + l.best_v);
-    g.best_i = reinterpret_cast<int*>(ws + l.best_i);
-    g.mats = reinterpret_cast<double*>(ws + l.mats);
+    g.rec_start = part<const int64_t>(workspace, l.rec_start);
+    g.want = want_host ? part<const int>(workspace, l.want) : nullptr;
+    g.mat_off = part<int64_t>(workspace, l.mat_off);
+    g.best_v = part<double>(workspace, l.best_v);
+    g.best_i = part<int>(workspace, l.best_i);
+    g.mats = part<double>(workspace, l.mats);
     g.threshold = threshold;
     g.max_clusters = max_clusters;
     g.labels = labels;
@@ -375,10 +374,9 @@ int xvec_ahc_cluster(const double* S, int64_t ld, const int64_t* rec_start_host,
     g.merge_score = merge_score;
 
     hipStream_t s = static_cast<hipStream_t>(stream);
-    hipError_t e = hipMemcpyAsync(ws + l.rec_start, rec_start_host, ((size_t)n_rec + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && want_host)
-        e = hipMemcpyAsync(ws + l.want, want_host, (size_t)n_rec * sizeof(int32_t), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return g_derr.fail(XVEC_ERR_HIP, "rec_start / want copy failed: %s", hipGetErrorString(e));
+    const char* copied = "rec_start / want";
+    if ((rc = upload(part<int64_t>(workspace, l.rec_start), rec_start_host, (size_t)n_rec + 1, copied, s, g_derr))) return rc;
+    if (want_host && (rc = upload(part<int32_t>(workspace, l.want), want_host, (size_t)n_rec, copied, s, g_derr))) return rc;
     ahc_layout_kernel<<<1, 256, 0, s>>>(g.rec_start, n_rec, g.mat_off);
     if ((rc = g_derr.launch_ok("ahc_layout_kernel"))) return rc;
     constexpr int rows = kInitThreads / 64;

@@ -7,7 +7,7 @@
 #include <cstdint>
 
 #include "../../include/xvec_diar.h"
-#include "plan_support.h"
+#include "rec_plan.h"
 
 #if defined(__HIPCC__)
 #define XVEC_DIAR_FN __host__ __device__ __forceinline__
@@ -25,20 +25,7 @@ XVEC_DIAR_FN int64_t mat_elems(int64_t n) { return (n * n + 31) & ~(int64_t)31; 
 // rec_start [n_rec + 1]: from 0, every recording with 1 .. XVEC_DIAR_MAX_SEGMENTS segments, fewer than 2^31 in all.
 // 0, or 1 with the reason in why.
 inline int check_rec_start(const int64_t* rs, int32_t n_rec, Refusal& why) {
-    if (n_rec < 1) return why.refuse("n_rec = %d: need at least one recording", n_rec);
-    if (!rs) return why.refuse("null pointer: rec_start");
-    if (rs[0] != 0) return why.refuse("rec_start must begin at 0 (got %lld)", (long long)rs[0]);
-    for (int32_t r = 0; r < n_rec; ++r) {
-        const int64_t n = rs[r + 1] - rs[r];
-        if (n < 1)
-            return why.refuse("recording %d is empty or rec_start decreases: every recording needs a segment", r);
-        if (n > XVEC_DIAR_MAX_SEGMENTS)
-            return why.refuse("recording %d has %lld segments, more than XVEC_DIAR_MAX_SEGMENTS = %d", r, (long long)n,
-                              XVEC_DIAR_MAX_SEGMENTS);
-        if (rs[r + 1] > 0x7fffffff)
-            return why.refuse("%lld segments up to recording %d: the total must stay below 2^31", (long long)rs[r + 1], r);
-    }
-    return 0;
+    return rec_plan::check_rec_start(rs, n_rec, {"segment", XVEC_DIAR_MAX_SEGMENTS, "XVEC_DIAR_MAX_SEGMENTS"}, why);
 }
 
 // want [n_rec] (may be null: no recording asks for a count): no negative entry.

@@ -1,7 +1,8 @@
 // Host-side plumbing of every C-ABI translation unit (xvec_api, mfcc, score, plda_train, eval, snorm, ident, diar, lda,
 // augment, resample, vad, tsne, calib, report, vbx, der, tdnn_train*, train_tail*): the error text behind a *_last_error() export, the workspace check,
-// the CU count, and through plan_support.h the alignment, the workspace carver and a plan header's refusal (eval, calib and
-// report share theirs: trial_plan.h).  Host code only: nothing here is called from a kernel.
+// the upload of a small host array, the CU count, and through plan_support.h the alignment, the workspace carver, the typed
+// pointer of a workspace part and a plan header's refusal (eval, calib and report share theirs: trial_plan.h; diar, vbx and der
+// theirs: rec_plan.h).  Host code only: nothing here is called from a kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
@@ -60,6 +61,14 @@ inline int workspace_arg_ok(const void* ws, size_t have, size_t need, ErrorChann
     if (align && reinterpret_cast<uintptr_t>(ws) % align != 0)
         return err.fail(XVEC_ERR_ARG, "%s%sworkspace is not %zu-byte aligned", call, sep, align);
     return have >= need ? XVEC_OK : err.fail(small_code, "workspace too small: %zu < %zu bytes", have, need);
+}
+
+// `count` elements of a small host array (rec_start, class_start, want) into device memory, in stream order.  XVEC_OK, or
+// XVEC_ERR_HIP "<name> copy failed: <hip error>".
+template <typename T>
+inline int upload(T* dev, const T* host, size_t count, const char* name, hipStream_t s, ErrorChannel& err) {
+    const hipError_t e = hipMemcpyAsync(dev, host, count * sizeof(T), hipMemcpyHostToDevice, s);
+    return e == hipSuccess ? XVEC_OK : err.fail(XVEC_ERR_HIP, "%s copy failed: %s", name, hipGetErrorString(e));
 }
 
 // Compute units of the current device (256 where the query fails), asked once per device.

@@ -1,6 +1,7 @@
-// What the host-only plan headers (diar_plan.h, vad_plan.h, tsne_plan.h, calib_plan.h, report_plan.h, vbx_plan.h, der_plan.h, trial_plan.h) and the C-ABI translation units (through
-// host_support.h) both need: the 256-byte alignment, the workspace carver, the reason of a refused argument check.  No HIP
-// header, so that the plan headers stay compilable by the host compiler alone (tests/abi/*_dump.cpp).
+// What the host-only plan headers (diar_plan.h, vad_plan.h, tsne_plan.h, calib_plan.h, report_plan.h, vbx_plan.h, der_plan.h,
+// trial_plan.h, rec_plan.h) and the C-ABI translation units (through host_support.h) both need: the 256-byte alignment, the
+// workspace carver, the typed pointer of a recorded byte offset, the reason of a refused argument check.  No HIP header, so
+// that the plan headers stay compilable by the host compiler alone (tests/abi/*_dump.cpp).
 #pragma once
 #include <cstdarg>
 #include <cstddef>
@@ -29,6 +30,12 @@ struct Carver {
     }
     size_t total() const { return off; }
 };
+
+// The part of workspace `ws` that a plan header's Layout records at byte offset `off`, as a T*.
+template <typename T>
+inline T* part(void* ws, size_t off) {
+    return reinterpret_cast<T*>(static_cast<char*>(ws) + off);
+}
 
 // Why a plan header's check refused its arguments.  A check returns 0, or `why.refuse(...)` = 1 with the reason in why.text;
 // the translation unit forwards it with ErrorChannel::refused (host_support.h).

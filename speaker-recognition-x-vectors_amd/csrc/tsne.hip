@@ -393,11 +393,6 @@ __global__ __launch_bounds__(kThreads) void tsne_finish_kernel(const StepArgs g,
 
 thread_local ErrorChannel g_terr;
 
-template <typename T>
-T* part(void* ws, size_t off) {
-    return reinterpret_cast<T*>(static_cast<char*>(ws) + off);
-}
-
 }  // namespace
 }  // namespace xvec
 

@@ -413,15 +413,14 @@ int xvec_cmvn_sliding(const float* x, int32_t B, int32_t T, int32_t C, int64_t r
     if (!new_lengths) return g_verr.fail(XVEC_ERR_ARG, "null pointer: new_lengths (optional only without a mask)");
     const vad_plan::Layout l = vad_plan::make_layout(B, T);
     if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_verr))) return rc;
-    char* ws = static_cast<char*>(workspace);
     VadArgs g{};
     g.B = B;
     g.T = T;
     g.lengths = lengths;
     g.mask_in = mask;
     g.ms = mask_stride;
-    g.prefix = reinterpret_cast<int*>(ws + l.prefix);
-    g.count_ws = reinterpret_cast<int*>(ws + l.count);
+    g.prefix = part<int>(workspace, l.prefix);
+    g.count_ws = part<int>(workspace, l.count);
     vad_count_kernel<<<(unsigned)B, kLanes, 0, st>>>(g);
     if ((rc = g_verr.launch_ok("vad_count_kernel"))) return rc;
     return launch_cmvn(s, cmvn, tile, mask, mask_stride, g.prefix, g.count_ws, y, y_row_stride, y_utt_stride, new_lengths, st);
@@ -438,11 +437,10 @@ int xvec_vad_cmvn(const float* x, int32_t B, int32_t T, int32_t C, int64_t row_s
     if ((rc = check_normalise(s, cmvn, y, y_row_stride, y_utt_stride, &tile))) return rc;
     const vad_plan::Layout l = vad_plan::make_layout(B, T);
     if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_verr))) return rc;
-    char* ws = static_cast<char*>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
     VadArgs g = decide_args(s, *vad, mask, mask_stride, counts, thr);
-    g.prefix = reinterpret_cast<int*>(ws + l.prefix);
-    g.count_ws = reinterpret_cast<int*>(ws + l.count);
+    g.prefix = part<int>(workspace, l.prefix);
+    g.count_ws = part<int>(workspace, l.count);
     vad_decide_kernel<<<(unsigned)B, kLanes, 0, st>>>(g);
     if ((rc = g_verr.launch_ok("vad_decide_kernel"))) return rc;
     if (!select) return launch_cmvn(s, cmvn, tile, nullptr, 0, nullptr, nullptr, y, y_row_stride, y_utt_stride, new_lengths, st);

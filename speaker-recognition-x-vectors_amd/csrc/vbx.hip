@@ -469,13 +469,12 @@ int xvec_vbx_run(const double* X, int64_t ldx, int32_t dim, const double* phi, c
     int rc;
     if ((rc = workspace_arg_ok(workspace, workspace_bytes, l.total, g_verr))) return rc;
 
-    char* ws = static_cast<char*>(workspace);
     VbxArgs g{};
     g.X = X;
     g.ldx = ldx;
     g.dim = dim;
     g.phi = phi;
-    g.rec_start = reinterpret_cast<const int64_t*>(ws + l.rec_start);
+    g.rec_start = part<const int64_t>(workspace, l.rec_start);
     g.n_spk = n_spk;
     g.loop_prob = options->loop_prob;
     g.Fa = options->Fa;
@@ -489,18 +488,18 @@ int xvec_vbx_run(const double* X, int64_t ldx, int32_t dim, const double* phi, c
     g.iters = iters;
     g.labels = labels;
     g.n_speakers = n_speakers;
-    g.rho = reinterpret_cast<double*>(ws + l.rho);
-    g.g = reinterpret_cast<double*>(ws + l.g);
-    g.em = reinterpret_cast<double*>(ws + l.em);
-    g.fw = reinterpret_cast<double*>(ws + l.fw);
-    g.c = reinterpret_cast<double*>(ws + l.c);
-    g.mx = reinterpret_cast<double*>(ws + l.mx);
-    g.raw = reinterpret_cast<int*>(ws + l.raw);
-    g.model = reinterpret_cast<double*>(ws + l.model);
+    g.rho = part<double>(workspace, l.rho);
+    g.g = part<double>(workspace, l.g);
+    g.em = part<double>(workspace, l.em);
+    g.fw = part<double>(workspace, l.fw);
+    g.c = part<double>(workspace, l.c);
+    g.mx = part<double>(workspace, l.mx);
+    g.raw = part<int>(workspace, l.raw);
+    g.model = part<double>(workspace, l.model);
 
     hipStream_t s = static_cast<hipStream_t>(stream);
-    const hipError_t e = hipMemcpyAsync(ws + l.rec_start, rec_start_host, ((size_t)n_rec + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) return g_verr.fail(XVEC_ERR_HIP, "rec_start copy failed: %s", hipGetErrorString(e));
+    if ((rc = upload(part<int64_t>(workspace, l.rec_start), rec_start_host, (size_t)n_rec + 1, "rec_start", s, g_verr)))
+        return rc;
     const vbx_plan::Launch run = vbx_plan::run_launch(n_rec);
     vbx_run_kernel<<<(unsigned)run.blocks, run.threads, 0, s>>>(g);
     return g_verr.launch_ok("vbx_run_kernel");

@@ -6,7 +6,7 @@
 #include <cstdint>
 
 #include "../../include/xvec_vbx.h"
-#include "plan_support.h"
+#include "rec_plan.h"
 
 namespace xvec {
 namespace vbx_plan {
@@ -18,19 +18,7 @@ inline int64_t rho_cols(int32_t dim) { return (int64_t)dim + 1; }
 // rec_start [n_rec + 1]: from 0, every recording with 1 .. XVEC_VBX_MAX_FRAMES frames, fewer than 2^31 in all.
 // 0, or 1 with the reason in why.
 inline int check_rec_start(const int64_t* rs, int32_t n_rec, Refusal& why) {
-    if (n_rec < 1) return why.refuse("n_rec = %d: need at least one recording", n_rec);
-    if (!rs) return why.refuse("null pointer: rec_start");
-    if (rs[0] != 0) return why.refuse("rec_start must begin at 0 (got %lld)", (long long)rs[0]);
-    for (int32_t r = 0; r < n_rec; ++r) {
-        const int64_t n = rs[r + 1] - rs[r];
-        if (n < 1) return why.refuse("recording %d is empty or rec_start decreases: every recording needs a frame", r);
-        if (n > XVEC_VBX_MAX_FRAMES)
-            return why.refuse("recording %d has %lld frames, more than XVEC_VBX_MAX_FRAMES = %d", r, (long long)n,
-                              XVEC_VBX_MAX_FRAMES);
-        if (rs[r + 1] > 0x7fffffff)
-            return why.refuse("%lld frames up to recording %d: the total must stay below 2^31", (long long)rs[r + 1], r);
-    }
-    return 0;
+    return rec_plan::check_rec_start(rs, n_rec, {"frame", XVEC_VBX_MAX_FRAMES, "XVEC_VBX_MAX_FRAMES"}, why);
 }
 
 inline int check_shape(int32_t dim, int32_t n_spk, Refusal& why) {
@@ -85,10 +73,7 @@ inline Layout make_layout(const int64_t* rs, int32_t n_rec, int32_t dim, int32_t
 
 // The launch of xvec_vbx_run: one block per recording, whatever max_iter is; of xvec_vbx_init: a thread per row of gamma and
 // per row of pi.
-struct Launch {
-    int64_t blocks;
-    int32_t threads;
-};
+using rec_plan::Launch;
 
 inline Launch run_launch(int32_t n_rec) { return Launch{n_rec, XVEC_VBX_THREADS}; }
 

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, ptr, require_device, stream as _stream
+from ._device import checker, i64_ptr, ptr, require_device, sized_workspace, stream as _stream
 
 __all__ = ["der", "assign", "read_rttm", "workspace_bytes", "DerResult", "MAX_SPEAKERS", "CHUNK_TICKS", "WAVE_ROWS", "THREADS"]
 
@@ -29,7 +29,6 @@ __all__ = ["der", "assign", "read_rttm", "workspace_bytes", "DerResult", "MAX_SP
 MAX_SPEAKERS, CHUNK_TICKS, WAVE_ROWS, THREADS = 64, 4096, 16, 256
 
 _check = checker(_hip.lib.xvec_der_last_error)
-_I64P = _hip.C.POINTER(_hip.C.c_int64)
 _I32_MIN, _I32_MAX = -2 ** 31, 2 ** 31 - 1
 
 
@@ -112,7 +111,7 @@ def _rec_start(rec_len) -> np.ndarray:
 def workspace_bytes(rec_len, m_ref=0, m_hyp=0) -> int:
     """Bytes of workspace `der` needs for recordings of these lengths (0: the arguments are refused)."""
     rs = _rec_start(rec_len)
-    return int(_hip.lib.xvec_der_workspace_bytes(rs.ctypes.data_as(_I64P), rs.shape[0] - 1, int(m_ref), int(m_hyp)))
+    return int(_hip.lib.xvec_der_workspace_bytes(i64_ptr(rs), rs.shape[0] - 1, int(m_ref), int(m_hyp)))
 
 
 def der(ref_turns, hyp_turns, rec_len, collar=0, skip_overlap=False, strict=True, return_cooccurrence=False, workspace=None,
@@ -131,10 +130,9 @@ def der(ref_turns, hyp_turns, rec_len, collar=0, skip_overlap=False, strict=True
     rs = _rec_start(rec_len)
     n_rec = rs.shape[0] - 1
     m_ref, m_hyp = (0 if ref is None else int(ref.shape[0])), (0 if hyp is None else int(hyp.shape[0]))
-    rs_p = rs.ctypes.data_as(_I64P)
-    need = int(_hip.lib.xvec_der_workspace_bytes(rs_p, n_rec, m_ref, m_hyp))
-    if need == 0:
-        raise ValueError(f"der: {int(rs[-1])} ticks in {n_rec} recordings: the total must stay below 2^31")
+    rs_p = i64_ptr(rs)
+    refusal = lambda: ValueError(f"der: {int(rs[-1])} ticks in {n_rec} recordings: the total must stay below 2^31")
+    ws = sized_workspace(_hip.lib.xvec_der_workspace_bytes(rs_p, n_rec, m_ref, m_hyp), refusal, dev, workspace)
     if int(collar) < 0:
         raise ValueError(f"der: collar = {collar} must not be negative")
     counts = torch.empty((n_rec, 5), dtype=torch.int64, device=dev)
@@ -142,7 +140,6 @@ def der(ref_turns, hyp_turns, rec_len, collar=0, skip_overlap=False, strict=True
     rate = torch.empty(n_rec + 1, dtype=torch.float64, device=dev)
     ign = torch.empty(2, dtype=torch.int64, device=dev)
     cooc = torch.empty((n_rec, MAX_SPEAKERS, MAX_SPEAKERS), dtype=torch.int64, device=dev) if return_cooccurrence else None
-    ws = byte_workspace(need, dev, workspace)
     with torch.cuda.device(dev):
         _check(_hip.lib.xvec_der_score(ptr(ref), m_ref, ptr(hyp), m_hyp, rs_p, n_rec, int(collar), 1 if skip_overlap else 0,
                                        counts.data_ptr(), mapping.data_ptr(), rate.data_ptr(), ign.data_ptr(), ptr(cooc),

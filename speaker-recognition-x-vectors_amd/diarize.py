@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, score_matrix, stream as _stream
+from ._device import (byte_workspace, checker, dev_f64, i64_ptr, rec_start as _dev_rec_start, require_device, score_matrix,
+                      stream as _stream)
 
 __all__ = ["cluster", "Clustering", "turns", "write_rttm", "Diarizer", "Diarization", "MAX_SEGMENTS", "THREADS_SMALL",
            "THREADS_LARGE", "RESCAN_WIDTH"]
@@ -38,7 +39,7 @@ __all__ = ["cluster", "Clustering", "turns", "write_rttm", "Diarizer", "Diarizat
 MAX_SEGMENTS, THREADS_SMALL, THREADS_LARGE, RESCAN_WIDTH = 2048, 64, 256, 64
 
 _check = checker(_hip.lib.xvec_diar_last_error)
-_I64P, _I32P = _hip.C.POINTER(_hip.C.c_int64), _hip.C.POINTER(_hip.C.c_int32)
+_I32P = _hip.C.POINTER(_hip.C.c_int32)
 
 
 class Clustering(NamedTuple):
@@ -52,10 +53,7 @@ def _matrix(scores, what) -> torch.Tensor:
 
 
 def _rec_start(rec_start, n, what) -> np.ndarray:
-    rs = np.ascontiguousarray(np.asarray(rec_start), dtype=np.int64)
-    if rs.ndim != 1 or rs.shape[0] < 2 or rs[0] != 0 or rs[-1] != n or (np.diff(rs) < 1).any():
-        raise ValueError(f"{what}: rec_start must rise from 0 to the {n} rows of the score matrix, a segment or more per recording")
-    return rs
+    return _dev_rec_start(rec_start, n, what, "rows of the score matrix", "segment")
 
 
 def cluster(S, rec_start, threshold=None, n_speakers=None, max_speakers=None, return_merges=False, workspace=None) -> Clustering:
@@ -88,7 +86,7 @@ def cluster(S, rec_start, threshold=None, n_speakers=None, max_speakers=None, re
     if return_merges:
         merges = (torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
                   torch.empty(n, dtype=torch.float64, device=dev))
-    rs_p = rs.ctypes.data_as(_I64P)
+    rs_p = i64_ptr(rs)
     ws = byte_workspace(int(_hip.lib.xvec_ahc_workspace_bytes(rs_p, n_rec)), dev, workspace)
     with torch.cuda.device(dev):
         _check(_hip.lib.xvec_ahc_cluster(s.data_ptr(), s.stride(0), rs_p, n_rec, thr, max_clusters,
@@ -237,7 +235,7 @@ class Diarizer:
             lo, hi = int(rec_start[a]), int(rec_start[b])
             rs = rec_start[a:b + 1] - lo
             s = self._scores(vecs[lo:hi])
-            self._ws = byte_workspace(int(_hip.lib.xvec_ahc_workspace_bytes(rs.ctypes.data_as(_I64P), b - a)), self.device, self._ws)
+            self._ws = byte_workspace(int(_hip.lib.xvec_ahc_workspace_bytes(i64_ptr(rs), b - a)), self.device, self._ws)
             cl = cluster(s, rs, self.threshold, None if want is None else want[a:b], self.max_speakers, workspace=self._ws)
             if self.resegment is not None:
                 from . import vbx as _vbx

@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, score_matrix, stream as _stream
+from ._device import byte_workspace, checker, dev_f64, i64_ptr, require_device, score_matrix, stream as _stream
 
 __all__ = ["group_models", "SpeakerModels", "enroll", "open_set_scores", "identify", "Identification", "SpeakerIdentifier",
            "identification_rate", "COLS", "SLICE_ROWS", "BLOCK_ROWS", "TOPK_BLOCK_ROWS", "APPLY_ROWS", "APPLY_COLS", "MAX_K"]
@@ -78,9 +78,8 @@ def enroll(xvecs, names, device="cuda:0") -> SpeakerModels:
     ws = byte_workspace(_hip.lib.xvec_model_mean_workspace_bytes(m), device)
     xd = _hip.IDENT_X_F32 if x.dtype == torch.float32 else _hip.IDENT_X_F64
     with torch.cuda.device(device):
-        _check(_hip.lib.xvec_model_mean(x.data_ptr(), xd, n, dim, x.stride(0), order_d.data_ptr(),
-                                        start.ctypes.data_as(_hip.C.POINTER(_hip.C.c_int64)), m, out.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), _stream(device)))
+        _check(_hip.lib.xvec_model_mean(x.data_ptr(), xd, n, dim, x.stride(0), order_d.data_ptr(), i64_ptr(start), m,
+                                        out.data_ptr(), ws.data_ptr(), ws.numel(), _stream(device)))
     return SpeakerModels(unique, out, np.diff(start))
 
 

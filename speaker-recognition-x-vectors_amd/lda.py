@@ -30,7 +30,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import byte_workspace, checker, dev_f64, i64_ptr, require_device, stream as _stream
 from .plda import _labels
 
 __all__ = ["lda_matrix_from_scatter", "embed_transform", "LdaStats", "LDA", "lda", "EmbeddingTransform", "NORM_CLIP"]
@@ -115,10 +115,8 @@ class LdaStats:
         ws = byte_workspace(_hip.lib.xvec_lda_stats_workspace_bytes(n, dim, C), dev)
         xd = _hip.LDA_X_F32 if t.dtype == torch.float32 else _hip.LDA_X_F64
         with torch.cuda.device(dev):
-            _check(_hip.lib.xvec_lda_stats(t.data_ptr(), xd, n, dim, order_d.data_ptr(),
-                                           start.ctypes.data_as(_hip.C.POINTER(_hip.C.c_int64)), C, mean.data_ptr(),
-                                           cm.data_ptr(), sw.data_ptr(), sb.data_ptr(), ws.data_ptr(), ws.numel(),
-                                           _stream(dev)))
+            _check(_hip.lib.xvec_lda_stats(t.data_ptr(), xd, n, dim, order_d.data_ptr(), i64_ptr(start), C, mean.data_ptr(),
+                                           cm.data_ptr(), sw.data_ptr(), sb.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
         self.mean = mean.cpu().numpy()
         self.class_means = cm.cpu().numpy()
         self.s_within = sw.cpu().numpy()

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import byte_workspace, checker, dev_f64, i64_ptr, require_device, stream as _stream
 
 _check = checker(_hip.lib.xvec_plda_last_error)
 
@@ -99,8 +99,7 @@ class PldaStats:
         ws = byte_workspace(_hip.lib.xvec_plda_stats_workspace_bytes(n, dim, C), dev)
         xd = _hip.PLDA_X_F32 if t.dtype == torch.float32 else _hip.PLDA_X_F64
         with torch.cuda.device(dev):
-            _check(_hip.lib.xvec_plda_stats(t.data_ptr(), xd, n, dim, order_d.data_ptr(),
-                                            start.ctypes.data_as(_hip.C.POINTER(_hip.C.c_int64)), C, self.scaling_factor,
+            _check(_hip.lib.xvec_plda_stats(t.data_ptr(), xd, n, dim, order_d.data_ptr(), i64_ptr(start), C, self.scaling_factor,
                                             mean.data_ptr(), counts.data_ptr(), self._cls.data_ptr(), self._cls_t.data_ptr(),
                                             sigma.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)))
         self._counts = counts

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import hip as _hip
-from ._device import byte_workspace, checker, dev_f64, require_device, stream as _stream
+from ._device import byte_workspace, checker, dev_f64, i64_ptr, rec_start as _dev_rec_start, require_device, stream as _stream
 
 __all__ = ["vbx", "vbx_init", "Vbx", "VbxModel", "VbxResult", "MAX_SPEAKERS", "MAX_DIM", "MAX_FRAMES", "THREADS", "PREFETCH"]
 
@@ -32,7 +32,6 @@ __all__ = ["vbx", "vbx_init", "Vbx", "VbxModel", "VbxResult", "MAX_SPEAKERS", "M
 MAX_SPEAKERS, MAX_DIM, MAX_FRAMES, THREADS, PREFETCH = 64, 512, 16384, 256, 8
 
 _check = checker(_hip.lib.xvec_vbx_last_error)
-_I64P = _hip.C.POINTER(_hip.C.c_int64)
 
 
 class VbxResult(NamedTuple):
@@ -104,10 +103,7 @@ def _frames(x, what) -> torch.Tensor:
 
 
 def _rec_start(rec_start, n, what) -> np.ndarray:
-    rs = np.ascontiguousarray(np.asarray(rec_start), dtype=np.int64)
-    if rs.ndim != 1 or rs.shape[0] < 2 or rs[0] != 0 or rs[-1] != n or (np.diff(rs) < 1).any():
-        raise ValueError(f"{what}: rec_start must rise from 0 to the {n} frames, a frame or more per recording")
-    return rs
+    return _dev_rec_start(rec_start, n, what, "frames", "frame")
 
 
 def vbx_init(labels, rec_start, n_speakers, smoothing=5.0):
@@ -121,7 +117,7 @@ def vbx_init(labels, rec_start, n_speakers, smoothing=5.0):
     gamma = torch.empty((lab.shape[0], max(S, 1)), dtype=torch.float64, device=dev)
     pi = torch.empty((n_rec, max(S, 1)), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        _check(_hip.lib.xvec_vbx_init(lab.data_ptr(), rs.ctypes.data_as(_I64P), n_rec, S, float(smoothing), gamma.data_ptr(),
+        _check(_hip.lib.xvec_vbx_init(lab.data_ptr(), i64_ptr(rs), n_rec, S, float(smoothing), gamma.data_ptr(),
                                       gamma.stride(0), pi.data_ptr(), _stream(dev)))
     return gamma, pi
 
@@ -159,7 +155,7 @@ def vbx(x, rec_start, phi, init_labels=None, gamma=None, pi=None, n_speakers=Non
             raise ValueError(f"vbx: pi of shape {tuple(p.shape)} for {n_rec} recordings of {S} speakers")
     S = int(g.shape[1])
     opts = _hip.VbxOptions(float(loop_prob), float(Fa), float(Fb), float(epsilon), int(max_iter), 0)
-    rs_p = rs.ctypes.data_as(_I64P)
+    rs_p = i64_ptr(rs)
     elbo = torch.empty((n_rec, max(int(max_iter), 1)), dtype=torch.float64, device=dev)
     iters = torch.empty(n_rec, dtype=torch.int32, device=dev)
     labels = torch.empty(n, dtype=torch.int32, device=dev)
@@ -175,7 +171,7 @@ def vbx(x, rec_start, phi, init_labels=None, gamma=None, pi=None, n_speakers=Non
 def workspace_bytes(rec_start, dim, n_speakers) -> int:
     """Bytes of workspace `vbx` needs for these recordings (0: the arguments are refused)."""
     rs = np.ascontiguousarray(np.asarray(rec_start), dtype=np.int64)
-    return int(_hip.lib.xvec_vbx_workspace_bytes(rs.ctypes.data_as(_I64P), rs.shape[0] - 1, int(dim), int(n_speakers)))
+    return int(_hip.lib.xvec_vbx_workspace_bytes(i64_ptr(rs), rs.shape[0] - 1, int(dim), int(n_speakers)))
 
 
 def resegment(opts: Vbx, vecs, rec_start, labels, device, workspace=None) -> VbxResult:

@@ -10,14 +10,10 @@
 //   costs <c_miss> <c_fa> <p_target>       -> ok | refused <message>
 //   apply <ld> <rows> <cols> <ld_out> <in place 0|1> -> ok | refused <message> | toolarge <message>
 //   segments <capacity> <arrays 0|1>       -> ok | refused <message>
-#include <cstdio>
-#include <cstdlib>
 #include <iostream>
-#include <sstream>
-#include <string>
-#include <vector>
 
 #include "calib_plan.h"
+#include "plan_dump.h"
 
 int main() {
     using namespace xvec::calib_plan;
@@ -25,48 +21,40 @@ int main() {
     void* const P = reinterpret_cast<void*>(0x1000);      // never followed
     void* const Q = reinterpret_cast<void*>(0x2000);
     while (std::getline(std::cin, line)) {
-        std::istringstream in(line);
-        std::string what;
-        if (!(in >> what)) return 2;
-        std::vector<std::string> a;
-        for (std::string x; in >> x;) a.push_back(x);
-        auto I = [&](size_t k) { return std::strtoll(a.at(k).c_str(), nullptr, 10); };
-        auto D = [&](size_t k) { return std::strtod(a.at(k).c_str(), nullptr); };
+        const plan_dump::Request q(line);
         xvec::Refusal why;
         bool too_large = false;
-        auto verdict = [&](int bad) {
-            if (bad) std::printf("%s %s\n", too_large ? "toolarge" : "refused", why.text); else std::printf("ok\n");
-        };
-        if (what == "const" && a.empty()) {
+        auto verdict = [&](int bad) { plan_dump::answer(bad, why, too_large); };
+        if (q.what == "const" && q.a.empty()) {
             std::printf("const %d %d %d %d %d %d %d\n", kThreads, kItems, kMaxBlocks, kChunk, kFinal, kHullTile, kPartialWords);
-        } else if (what == "blocks" && a.size() == 1) {
-            std::printf("blocks %lld %lld\n", (long long)pass_blocks(I(0)), (long long)sum_depth(I(0)));
-        } else if (what == "hull" && a.size() == 1) {
+        } else if (q.what == "blocks" && q.a.size() == 1) {
+            std::printf("blocks %lld %lld\n", (long long)pass_blocks(q.I(0)), (long long)sum_depth(q.I(0)));
+        } else if (q.what == "hull" && q.a.size() == 1) {
             HullPlan h;
-            if (plan_hull(I(0), &h)) {
+            if (plan_hull(q.I(0), &h)) {
                 std::printf("refused\n");
             } else {
                 std::printf("hull %d", h.levels);
                 for (int l = 1; l <= h.levels; ++l) std::printf(" %lld %lld", (long long)h.groups[l], (long long)h.span[l]);
                 std::printf("\n");
             }
-        } else if (what == "layout" && a.size() == 2) {
-            const Layout l = make_layout(I(0), (size_t)I(1));
+        } else if (q.what == "layout" && q.a.size() == 2) {
+            const Layout l = make_layout(q.I(0), (size_t)q.I(1));
             std::printf("layout %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu %lld\n", l.state, l.partials, l.fit_scores, l.fit_bits,
                         l.eval, l.keys, l.bits, l.points, l.block_counts, l.group_counts, l.total, (long long)l.hull_blocks);
-        } else if (what == "trials" && a.size() == 5) {
-            verdict(check_trials(P, I(0), I(1), I(2), I(3) ? P : nullptr, I(3) ? P : nullptr, P, I(4), why, &too_large));
-        } else if (what == "pairs" && a.size() == 3) {
-            verdict(check_all_pairs(P, I(0), I(1), I(2), P, P, why, &too_large));
-        } else if (what == "fit" && a.size() == 2) {
-            verdict(check_fit(D(0), (int32_t)I(1), why));
-        } else if (what == "costs" && a.size() == 3) {
-            verdict(check_costs(D(0), D(1), D(2), why));
-        } else if (what == "apply" && a.size() == 5) {
-            verdict(check_apply(P, I(0), I(1), I(2), P, I(4) ? P : Q, I(3), why, &too_large));
-        } else if (what == "segments" && a.size() == 2) {
-            void* arr = I(1) ? P : nullptr;
-            verdict(check_segments(arr, arr, arr, arr, I(0), why));
+        } else if (q.what == "trials" && q.a.size() == 5) {
+            verdict(check_trials(P, q.I(0), q.I(1), q.I(2), q.I(3) ? P : nullptr, q.I(3) ? P : nullptr, P, q.I(4), why, &too_large));
+        } else if (q.what == "pairs" && q.a.size() == 3) {
+            verdict(check_all_pairs(P, q.I(0), q.I(1), q.I(2), P, P, why, &too_large));
+        } else if (q.what == "fit" && q.a.size() == 2) {
+            verdict(check_fit(q.D(0), (int32_t)q.I(1), why));
+        } else if (q.what == "costs" && q.a.size() == 3) {
+            verdict(check_costs(q.D(0), q.D(1), q.D(2), why));
+        } else if (q.what == "apply" && q.a.size() == 5) {
+            verdict(check_apply(P, q.I(0), q.I(1), q.I(2), P, q.I(4) ? P : Q, q.I(3), why, &too_large));
+        } else if (q.what == "segments" && q.a.size() == 2) {
+            void* arr = q.I(1) ? P : nullptr;
+            verdict(check_segments(arr, arr, arr, arr, q.I(0), why));
         } else {
             return 2;
         }

@@ -8,53 +8,36 @@
 //   turns <0 | 1> <m> <ref | hyp>   -> ok | refused <message>       check_turns of a null (0) or a given (1) pointer
 //   blocks <n_0> <n_1> ...          -> blocks <pass blocks> then per block " <rec>:<chunk>:<first tick>:<ticks>"
 //   launch <m_ref> <m_hyp> <n_0> .. -> launch <raster blocks> <threads> <pass blocks> <threads> <assign blocks> <threads> <pool blocks> <threads>
-#include <cstdio>
 #include <iostream>
-#include <sstream>
-#include <string>
-#include <vector>
 
 #include "der_plan.h"
+#include "plan_dump.h"
 
 int main() {
     using namespace xvec::der_plan;
     std::string line;
     while (std::getline(std::cin, line)) {
-        std::istringstream in(line);
-        std::string what;
-        if (!(in >> what)) return 2;
+        const plan_dump::Request q(line);
+        const std::string& what = q.what;
         xvec::Refusal why;
-        auto answer = [&](int bad) { if (bad) std::printf("refused %s\n", why.text); else std::printf("ok\n"); };
+        auto answer = [&](int bad) { plan_dump::answer(bad, why); };
         if (what == "turns") {
-            int given;
-            long long m;
-            std::string side;
-            if (!(in >> given >> m >> side)) return 2;
+            if (q.a.size() != 3) return 2;
             static const int32_t row[4] = {0, 0, 1, 0};
-            answer(check_turns(given ? row : nullptr, m, side.c_str(), why));
-            continue;
-        }
-        std::vector<long long> v;
-        for (long long x; in >> x;) v.push_back(x);
-        if (what == "nullstart") {
-            if (v.size() != 1) return 2;
-            answer(check_rec_start(nullptr, (int32_t)v[0], why));
+            answer(check_turns(q.I(0) ? row : nullptr, q.I(1), q.a[2].c_str(), why));
+        } else if (what == "nullstart") {
+            if (q.a.size() != 1) return 2;
+            answer(check_rec_start(nullptr, (int32_t)q.I(0), why));
         } else if (what == "counts") {
-            if (v.size() != 2) return 2;
-            answer(check_turn_counts(v[0], v[1], why));
+            if (q.a.size() != 2) return 2;
+            answer(check_turn_counts(q.I(0), q.I(1), why));
         } else if (what == "collar") {
-            if (v.size() != 1) return 2;
-            answer(check_collar((int32_t)v[0], why));
+            if (q.a.size() != 1) return 2;
+            answer(check_collar((int32_t)q.I(0), why));
         } else if (what == "start" || what == "check" || what == "layout" || what == "blocks" || what == "launch") {
-            const size_t skip = what == "launch" ? 2 : 0;
-            if (v.size() < skip) return 2;
-            std::vector<int64_t> rs;
-            if (what == "start") {
-                rs.assign(v.begin(), v.end());
-            } else {
-                rs.push_back(0);
-                for (size_t i = skip; i < v.size(); ++i) rs.push_back(rs.back() + v[i]);
-            }
+            const size_t lead = what == "launch" ? 2 : 0;
+            if (q.a.size() < lead) return 2;
+            const std::vector<int64_t> rs = q.rec_start(lead);
             const int32_t n_rec = (int32_t)rs.size() - 1;
             const int bad = check_rec_start(rs.data(), n_rec, why);
             if (what == "start" || what == "check") {
@@ -74,7 +57,7 @@ int main() {
                 }
                 std::printf("\n");
             } else {
-                const Launch r = raster_launch(v[0], v[1]), p = pass_launch(rs.data(), n_rec), a = assign_launch(n_rec), q = pool_launch();
+                const Launch r = raster_launch(q.I(0), q.I(1)), p = pass_launch(rs.data(), n_rec), a = assign_launch(n_rec), q = pool_launch();
                 std::printf("launch %lld %d %lld %d %lld %d %lld %d\n", (long long)r.blocks, r.threads, (long long)p.blocks, p.threads,
                             (long long)a.blocks, a.threads, (long long)q.blocks, q.threads);
             }

@@ -4,40 +4,29 @@
 //   layout <n_0> ...    -> layout <rec_start> <want> <mat_off> <best_v> <best_i> <mats> <total> <matrix 0> <matrix 1> ...   byte offsets
 //   check <n_0> ...     -> ok | refused <message>                                       check_rec_start
 //   start <s_0> ...     -> ok | refused <message>                                       check_rec_start of n_rec = count - 1 offsets
+//   nullstart <n_rec>   -> ok | refused <message>                                       check_rec_start of a null pointer
 //   want <w_0> ...      -> ok | refused <message>                                       check_want
 //   groups <n_0> ...    -> groups <first> <count> <threads> ...                         plan_groups
 //   threads <n>         -> threads <block size>                                         block_threads
-#include <cstdio>
-#include <cstring>
-#include <sstream>
-#include <string>
-#include <vector>
 #include <iostream>
 
 #include "diar_plan.h"
+#include "plan_dump.h"
 
 int main() {
     using namespace xvec::diar_plan;
+    using plan_dump::answer;
     std::string line;
     while (std::getline(std::cin, line)) {
-        std::istringstream in(line);
-        std::string what;
-        if (!(in >> what)) return 2;
-        std::vector<long long> v;
-        for (long long x; in >> x;) v.push_back(x);
+        const plan_dump::Request q(line);
+        const std::string& what = q.what;
         xvec::Refusal why;
         if (what == "start" || what == "check" || what == "layout" || what == "groups") {
-            std::vector<int64_t> rs;
-            if (what == "start") {
-                rs.assign(v.begin(), v.end());
-            } else {
-                rs.push_back(0);
-                for (long long n : v) rs.push_back(rs.back() + n);
-            }
+            const std::vector<int64_t> rs = q.rec_start();
             const int32_t n_rec = (int32_t)rs.size() - 1;
             const int bad = check_rec_start(rs.data(), n_rec, why);
             if (what == "start" || what == "check") {
-                if (bad) std::printf("refused %s\n", why.text); else std::printf("ok\n");
+                answer(bad, why);
             } else if (bad) {
                 return 3;
             } else if (what == "layout") {
@@ -49,15 +38,19 @@ int main() {
                 Group g[2];
                 const int n = plan_groups(rs.data(), n_rec, g);
                 std::printf("groups");
-                for (int q = 0; q < n; ++q) std::printf(" %d %d %d", g[q].first, g[q].count, g[q].threads);
+                for (int k = 0; k < n; ++k) std::printf(" %d %d %d", g[k].first, g[k].count, g[k].threads);
                 std::printf("\n");
             }
+        } else if (what == "nullstart") {
+            if (q.a.size() != 1) return 2;
+            answer(check_rec_start(nullptr, (int32_t)q.I(0), why), why);
         } else if (what == "want") {
-            std::vector<int32_t> w(v.begin(), v.end());
-            if (check_want(w.data(), (int32_t)w.size(), why)) std::printf("refused %s\n", why.text); else std::printf("ok\n");
+            std::vector<int32_t> w;
+            for (size_t k = 0; k < q.a.size(); ++k) w.push_back((int32_t)q.I(k));
+            answer(check_want(w.data(), (int32_t)w.size(), why), why);
         } else if (what == "threads") {
-            if (v.size() != 1) return 2;
-            std::printf("threads %d\n", block_threads(v[0]));
+            if (q.a.size() != 1) return 2;
+            std::printf("threads %d\n", block_threads(q.I(0)));
         } else {
             return 2;
         }
