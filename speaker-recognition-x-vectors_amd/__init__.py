@@ -17,7 +17,8 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "Tsne", "tsne_map", "tsne_affinities", "pca_map", "scatter_maps", "calibrate", "Calibration", "ScoreCalibrator", "CalibrationReport",
            "fit_calibration", "fit_calibration_all_pairs", "cllr", "min_cllr", "pav_segments", "calibration_report", "report", "DetCurve",
            "TrialReport", "trial_map", "score_range", "score_images", "det_curve", "det_curve_all_pairs", "trial_report", "vbx", "Vbx",
-           "VbxModel", "VbxResult", "der", "DerResult", "read_rttm"]
+           "VbxModel", "VbxResult", "der", "DerResult", "read_rttm", "fuse", "Term", "Fusion", "FusionResult", "ScoreFuser", "fit_fusion",
+           "fit_fusion_all_pairs", "log_duration_terms", "row_quality", "col_quality"]
 
 
 def __getattr__(name):
@@ -72,6 +73,10 @@ def __getattr__(name):
     if name in ("DerResult", "read_rttm"):
         import importlib
         return getattr(importlib.import_module(".der", __name__), name)
+    if name in ("Term", "Fusion", "FusionResult", "ScoreFuser", "fit_fusion", "fit_fusion_all_pairs", "log_duration_terms",
+                "row_quality", "col_quality"):
+        import importlib
+        return getattr(importlib.import_module(".fuse", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -79,7 +84,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der"):
+                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der", "fuse"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

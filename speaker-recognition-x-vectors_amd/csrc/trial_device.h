@@ -90,6 +90,26 @@ __device__ __forceinline__ Trial read_trial(const TrialArgs& g, int64_t t) {
     return r;
 }
 
+// The index half of read_trial for a unit that reads several arrays per trial (fuse.hip): row, col, target and what (kUse, kBad
+// or kSkip by the same tests); g.scores is not touched and score stays 0.  The caller reads its cells for kUse only.
+template <bool ALL_PAIRS>
+__device__ __forceinline__ Trial locate_trial(const TrialArgs& g, int64_t t) {
+    Trial r;
+    r.score = 0.0;
+    if (ALL_PAIRS) {
+        r.row = (int64_t)((uint32_t)t / (uint32_t)g.n_cols);
+        r.col = t - r.row * g.n_cols;
+        r.target = g.a[r.row] == g.b[r.col];
+        r.what = g.skip_diagonal && r.row == r.col ? kSkip : kUse;
+    } else {
+        r.row = g.a ? (int64_t)g.a[t] : 0;
+        r.col = g.b ? (int64_t)g.b[t] : t;
+        r.target = g.is_target[t] != 0;
+        r.what = r.row < 0 || r.row >= g.n_rows || r.col < 0 || r.col >= g.n_cols ? kBad : kUse;
+    }
+    return r;
+}
+
 // ---------------------------------------------------------------- block primitives
 
 // Exclusive scan of one value per thread in thread order; *total (if given) receives the sum.

@@ -118,6 +118,11 @@ class _wsb_der(_wsb_vbx):
     table below as the VBx unit's own; the DER unit's answers are held by tests/test_der.py."""
 
 
+class _wsb_fuse(_wsb_der):
+    """size_t workspace_bytes of include/xvec_fuse.h: one more name.  tests/test_der.py lists every (void*, _wsb_der) pair of the
+    table below as the DER unit's own; the fusion unit's answers are held by tests/test_fuse.py."""
+
+
 _SIGS = {
     "xvec_create": (C.c_int, [C.POINTER(Cfg), C.POINTER(_vp)]),
     "xvec_destroy": (None, [_vp]),
@@ -246,6 +251,13 @@ _SIGS = {
                                             _wsb, _vp]),
     "xvec_calib_min_cllr": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _wsb,
                                       _vp]),
+    # include/xvec_fuse.h  (the workspace size is spelt _wsb_fuse: see the class above; `terms` is a HOST array of xvec_fuse_term)
+    "xvec_fuse_last_error": (C.c_char_p, []),
+    "xvec_fuse_workspace_bytes": (C.c_size_t, [_i64, _i32]),
+    "xvec_fuse_fit": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, C.c_double, C.c_double, _i32, _vp, _vp, _wsb_fuse, _vp]),
+    "xvec_fuse_fit_all_pairs": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _wsb_fuse,
+                                          _vp]),
+    "xvec_fuse_apply": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp, _i64, _vp]),
     # include/xvec_report.h  (the workspace size is spelt _wsb_report: see the class above)
     "xvec_report_last_error": (C.c_char_p, []),
     "xvec_report_trial_map": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp]),
