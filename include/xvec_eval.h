@@ -85,6 +85,24 @@ int xvec_eval_sorted_keys(const double* scores, int64_t ld, int64_t n_rows, int6
                           int64_t n_trials, uint32_t* keys_out, uint8_t* bits_out, void* workspace,
                           size_t workspace_bytes, xvec_stream stream);
 
+/* The same two stages with the trial's place instead of its bit: the sorted keys [n_trials] and, next to each key, the 32-bit
+ * index t of its trial (the position in the trial list; for all pairs t = row * n_cols + col).  Trials that are left out
+ * carry the key 0xffffffff and sort last, their indices with them.  The sort is STABLE: trials with equal keys (equal fp32
+ * scores; every trial left out) keep the order of their indices.  The bootstrap (xvec_boot.h) resamples over this order: a
+ * replicate changes the weight of a trial, not its place.  One sort serves both payloads (one byte there, four here); the
+ * workspace is xvec_eval_sorted_order_workspace_bytes(n_trials), 0 for a count that is refused. */
+size_t xvec_eval_sorted_order_workspace_bytes(int64_t n_trials);
+
+int xvec_eval_sorted_order(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols, const int32_t* row_idx,
+                           const int32_t* col_idx, const uint8_t* is_target, int64_t n_trials, uint32_t* keys_out,
+                           uint32_t* order_out, void* workspace, size_t workspace_bytes, xvec_stream stream);
+
+/* Arguments as xvec_eval_all_pairs; keys_out / order_out [n_rows * n_cols]. */
+int xvec_eval_sorted_order_all_pairs(const double* scores, int64_t ld, int64_t n_rows, int64_t n_cols,
+                                     const int32_t* row_class, const int32_t* col_class, int32_t skip_diagonal,
+                                     uint32_t* keys_out, uint32_t* order_out, void* workspace, size_t workspace_bytes,
+                                     xvec_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,7 +18,8 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "fit_calibration", "fit_calibration_all_pairs", "cllr", "min_cllr", "pav_segments", "calibration_report", "report", "DetCurve",
            "TrialReport", "trial_map", "score_range", "score_images", "det_curve", "det_curve_all_pairs", "trial_report", "vbx", "Vbx",
            "VbxModel", "VbxResult", "der", "DerResult", "read_rttm", "fuse", "Term", "Fusion", "FusionResult", "ScoreFuser", "fit_fusion",
-           "fit_fusion_all_pairs", "log_duration_terms", "row_quality", "col_quality"]
+           "fit_fusion_all_pairs", "log_duration_terms", "row_quality", "col_quality", "bootstrap", "BootstrapResult",
+           "BootstrapComparison", "bootstrap_trials", "bootstrap_all_pairs"]
 
 
 def __getattr__(name):
@@ -77,6 +78,9 @@ def __getattr__(name):
                 "row_quality", "col_quality"):
         import importlib
         return getattr(importlib.import_module(".fuse", __name__), name)
+    if name in ("BootstrapResult", "BootstrapComparison", "bootstrap_trials", "bootstrap_all_pairs"):
+        import importlib
+        return getattr(importlib.import_module(".bootstrap", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -84,7 +88,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der", "fuse"):
+                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der", "fuse", "bootstrap"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

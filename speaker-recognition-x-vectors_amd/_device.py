@@ -1,5 +1,5 @@
 """Host plumbing shared by every module that calls the library (model, frontend, scoring, plda, evaluate, snorm, identify,
-diarize, vbx, der, lda, augment, resample, vad, visualize, calibrate, fuse, report, train): error checks, the raw stream pointer, the pointer of an optional
+diarize, vbx, der, lda, augment, resample, vad, visualize, calibrate, fuse, bootstrap, report, train): error checks, the raw stream pointer, the pointer of an optional
 tensor, the device-only guard, host data onto the device, the check of a device score matrix, the check of a host rec_start,
 the pointer of a host int64 array, byte workspaces."""
 from __future__ import annotations

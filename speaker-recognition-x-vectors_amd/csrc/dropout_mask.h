@@ -2,7 +2,7 @@
 // channel, p), shared by the forward product's epilogue (csrc/tdnn_train_dropout.hip) and the host (xvec_dropout_keep_host).
 // Host-compilable (no HIP header, like mfcc_tables.h): __host__ __device__ under hipcc, plain inline C++ otherwise.
 //
-// The generator is Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): a 128-bit counter and
+// The generator is Philox4x32-10 (philox.h; shared with the bootstrap, boot_plan.h): a 128-bit counter and
 // a 64-bit key give four 32-bit words, with no state between calls.  Element (n, c) -- row n of the padded [B * T'] layout,
 // output channel c -- is decided by word n & 3 of
 //     philox(counter = (c, n >> 2, stream_lo, stream_hi), key = (seed_lo, seed_hi)):
@@ -11,6 +11,8 @@
 // so the four accumulators r & 3 of a lane are the four words of one call.
 #pragma once
 #include <cstdint>
+
+#include "philox.h"
 
 #if defined(__HIPCC__)
 #define XVEC_HD __host__ __device__ __forceinline__
@@ -21,30 +23,8 @@
 namespace xvec {
 namespace dropout {
 
-struct Words {
-    uint32_t w[4];
-};
-
-constexpr uint32_t kMul0 = 0xD2511F53u, kMul1 = 0xCD9E8D57u;     // round multipliers
-constexpr uint32_t kKey0 = 0x9E3779B9u, kKey1 = 0xBB67AE85u;     // key increments (golden ratio, sqrt(3) - 1)
-
-// ten rounds; the key is bumped between rounds (nine times)
-XVEC_HD Words philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int round = 0; round < 10; ++round) {
-        const uint64_t p0 = (uint64_t)kMul0 * c0, p1 = (uint64_t)kMul1 * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1;
-        c3 = (uint32_t)p0;
-        c0 = n0;
-        c2 = n2;
-        k0 += kKey0;
-        k1 += kKey1;
-    }
-    return Words{{c0, c1, c2, c3}};
-}
+using philox::Words;
+using philox::philox4x32_10;
 
 // the four words of rows 4 * quad .. 4 * quad + 3 of channel c
 XVEC_HD Words row_quad_words(uint32_t c, uint32_t quad, uint64_t seed, uint64_t stream) {

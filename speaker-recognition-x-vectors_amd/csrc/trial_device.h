@@ -136,6 +136,30 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t (&wtot)
     return add + x - v;
 }
 
+// The same in 64 bits (boot.hip: weighted counts do not fit 32).
+template <int WAVES>
+__device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t (&wtot)[WAVES], uint64_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t x = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint64_t y = __shfl_up(x, off);
+        if (lane >= off) x += y;
+    }
+    __syncthreads();
+    if (lane == 63) wtot[wave] = x;
+    __syncthreads();
+    uint64_t add = 0, t = 0;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+        const uint64_t s = wtot[w];
+        if (w < wave) add += s;
+        t += s;
+    }
+    if (total) *total = t;
+    return add + x - v;
+}
+
 // One block walks in[0 .. n) in chunks of its thread count, in rising order, and returns the sum; out (if given, in itself
 // or another array) receives the exclusive scan.
 template <int WAVES>
@@ -181,6 +205,68 @@ __device__ __forceinline__ long long block_count(long long v, long long (&wsum)[
 template <bool MIN, int WAVES>
 __device__ __forceinline__ double block_extreme(double v, double (&wbuf)[WAVES]) {
     return block_reduce(v, wbuf, [](double a, double b) { return MIN ? fmin(a, b) : fmax(a, b); });
+}
+
+// ---------------------------------------------------------------- candidate thresholds (eval.hip, boot.hip)
+
+// A candidate threshold: objective, sorted index, targets at or below it.  Order: smaller objective, then smaller index --
+// a total order, so the reduction gives the same winner whatever its shape.
+struct EerCand {
+    int64_t val, idx, tp;
+};
+struct DcfCand {
+    double val;
+    int64_t idx, tp;
+};
+__device__ __forceinline__ bool better(const EerCand& a, const EerCand& b) {
+    return a.val < b.val || (a.val == b.val && a.idx < b.idx);
+}
+__device__ __forceinline__ bool better(const DcfCand& a, const DcfCand& b) {
+    return a.val < b.val || (a.val == b.val && a.idx < b.idx);
+}
+constexpr int64_t kNoIdx = 0x7fffffffffffffffll;
+
+__device__ __forceinline__ EerCand no_eer_cand() { return EerCand{kNoIdx, kNoIdx, 0}; }
+__device__ __forceinline__ DcfCand no_dcf_cand() { return DcfCand{__longlong_as_double(0x7ff0000000000000ll), kNoIdx, 0}; }   // +inf
+
+// The threshold at sorted index i with tp targets and nn non-targets at or below it, of P targets and N non-targets
+// (P + N < 2^31: |fa P - tp N| < 2^62): both objectives of include/xvec_eval.h, kept where they beat be / bd.
+__device__ __forceinline__ void consider(int64_t i, int64_t tp, int64_t nn, int64_t P, int64_t N, double c_miss, double c_fa,
+                                         double p_target, EerCand& be, DcfCand& bd) {
+    const int64_t fa = N - nn;                            // non-targets above the threshold
+    const int64_t diff = fa * P - tp * N;
+    const EerCand ce{diff < 0 ? -diff : diff, i, tp};
+    if (better(ce, be)) be = ce;
+    const double frr = (double)tp / (double)P, far = (double)fa / (double)N;
+    const DcfCand cd{c_miss * frr * p_target + c_fa * far * (1.0 - p_target), i, tp};
+    if (better(cd, bd)) bd = cd;
+}
+
+// What the winners say: far, frr, eer of the EER candidate at index be.idx, of which `below` trials lie at or below it.
+struct Rates {
+    double far, frr, eer;
+};
+__device__ __forceinline__ Rates rates_at(int64_t tp, int64_t below, int64_t P, int64_t N) {
+    Rates r;
+    const int64_t fa = N - (below - tp);
+    r.far = (double)fa / (double)N;
+    r.frr = (double)tp / (double)P;
+    r.eer = (r.far + r.frr) / 2.0;
+    return r;
+}
+
+// The best of one candidate per thread, in every thread; sh holds one per thread of the block.
+template <typename C, int THREADS>
+__device__ __forceinline__ C block_best(C mine, C (&sh)[THREADS]) {
+    __syncthreads();
+    sh[threadIdx.x] = mine;
+    __syncthreads();
+#pragma unroll
+    for (int half = THREADS / 2; half > 0; half >>= 1) {
+        if ((int)threadIdx.x < half && better(sh[threadIdx.x + half], sh[threadIdx.x])) sh[threadIdx.x] = sh[threadIdx.x + half];
+        __syncthreads();
+    }
+    return sh[0];
 }
 
 }  // namespace trial_device

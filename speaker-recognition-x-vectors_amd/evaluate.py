@@ -28,7 +28,7 @@ import torch
 from . import hip as _hip
 from ._device import checker, dev_f64, require_device, score_matrix, sized_workspace, stream as _stream
 
-__all__ = ["TrialList", "TrialResult", "evaluate_trials", "evaluate_all_pairs", "sorted_keys", "EER", "minDCF",
+__all__ = ["TrialList", "TrialResult", "evaluate_trials", "evaluate_all_pairs", "sorted_keys", "sorted_order", "EER", "minDCF",
            "plda_score_stat_object"]
 
 
@@ -222,6 +222,27 @@ def sorted_keys(scores, is_target, workspace=None):
     return keys.to(torch.int64) & 0xFFFFFFFF, bits
 
 
+def sorted_order(scores, is_target, workspace=None):
+    """The sort with the trial's place as its payload (include/xvec_eval.h, xvec_eval_sorted_order): (keys uint32 as int64
+    tensor, order as int64 tensor) of a device vector of float64 trial scores.  order[k] is the index of the trial at sorted
+    position k; the sort is stable, so trials of equal key keep the order of their indices."""
+    if not isinstance(scores, torch.Tensor) or not scores.is_cuda:
+        raise RuntimeError("trial evaluation runs on a HIP device only (no CPU path)")
+    s = scores.to(torch.float64).contiguous().reshape(-1)
+    n = s.numel()
+    tgt = torch.as_tensor(is_target).to(device=s.device, dtype=torch.uint8).contiguous()
+    if tgt.numel() != n:
+        raise ValueError("sorted_order: one target flag per score")
+    refusal = lambda: ValueError(f"{n} trials: the count must lie in 1 .. 2^31 - 1")
+    ws = sized_workspace(_hip.lib.xvec_eval_sorted_order_workspace_bytes(n), refusal, s.device, workspace)
+    keys = torch.empty(n, dtype=torch.int32, device=s.device)
+    order = torch.empty(n, dtype=torch.int32, device=s.device)
+    with torch.cuda.device(s.device):
+        _check(_hip.lib.xvec_eval_sorted_order(s.data_ptr(), n, 1, n, None, None, tgt.data_ptr(), n, keys.data_ptr(),
+                                               order.data_ptr(), ws.data_ptr(), ws.numel(), _stream(s.device)))
+    return keys.to(torch.int64) & 0xFFFFFFFF, order.to(torch.int64) & 0xFFFFFFFF
+
+
 def _score_vector(scores, device):
     """Scores as the reference feeds them to the package: float32 values (round to nearest even), here held as float64."""
     if isinstance(scores, torch.Tensor) and scores.is_cuda:
@@ -339,6 +360,21 @@ class plda_score_stat_object:
         self.eer, self.eer_th = res.eer, res.eer_th
         self.min_dcf, self.min_dcf_th = res.min_dcf, res.min_dcf_th
         self._evaluated = True
+
+    def confidence(self, n_boot=1000, seed=0, level=0.95):
+        """Bootstrap confidence intervals of the collected trials' EER and minDCF over the SPEAKERS of the two trial sides
+        (bootstrap.bootstrap_trials, joint: enrolment and test ids are one set, so one resample of its speakers weighs both
+        sides).  The speaker of an id is the directory it starts with, as `checked_label` reads it.  Returns the
+        BootstrapResult; `eer_ci` and `min_dcf_ci` hold the (lo, hi) intervals at `level`.  Call test_plda first."""
+        from . import bootstrap
+        s, trials = self._scored("confidence")
+        speaker = lambda names: [name.split(".")[0].split("/")[0] for name in np.asarray(names).tolist()]
+        boot = bootstrap.bootstrap_trials(s, trials, row_groups=speaker(self.en_stat.modelset),
+                                          col_groups=speaker(self.te_stat.modelset), joint=True, n_boot=n_boot, seed=seed,
+                                          p_target=0.5)
+        self.eer_ci = boot.interval("eer", level)
+        self.min_dcf_ci = boot.interval("min_dcf", level)
+        return boot
 
     def _scored(self, what, thresholds=False):
         if self._trials is None:

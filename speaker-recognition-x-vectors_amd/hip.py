@@ -123,6 +123,18 @@ class _wsb_fuse(_wsb_der):
     table below as the DER unit's own; the fusion unit's answers are held by tests/test_fuse.py."""
 
 
+class _wsb_boot(_wsb_fuse):
+    """size_t workspace_bytes of include/xvec_boot.h and of xvec_eval_sorted_order (include/xvec_eval.h), whose sort the bootstrap
+    unit compiles: one more name.  tests/test_fuse.py lists every (void*, _wsb_fuse) pair of the table below as the fusion unit's
+    own; the answers of these are held by tests/test_bootstrap.py."""
+
+
+class BootParams(C.Structure):                                  # xvec_boot_params
+    _fields_ = [("row_group", C.c_void_p), ("col_group", C.c_void_p), ("n_row_groups", C.c_int32), ("n_col_groups", C.c_int32),
+                ("joint", C.c_int32), ("n_boot", C.c_int32), ("seed", C.c_uint64), ("c_miss", C.c_double), ("c_fa", C.c_double),
+                ("p_target", C.c_double)]
+
+
 _SIGS = {
     "xvec_create": (C.c_int, [C.POINTER(Cfg), C.POINTER(_vp)]),
     "xvec_destroy": (None, [_vp]),
@@ -185,6 +197,18 @@ _SIGS = {
     "xvec_eval_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.c_double, C.c_double, C.c_double, _vp, _vp,
                                       C.c_size_t, _vp]),
     "xvec_eval_sorted_keys": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, C.c_size_t, _vp]),
+    "xvec_eval_sorted_order_workspace_bytes": (C.c_size_t, [_i64]),
+    "xvec_eval_sorted_order": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _wsb_boot, _vp]),
+    "xvec_eval_sorted_order_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _vp, _vp, _vp, _wsb_boot, _vp]),
+    # include/xvec_boot.h  (the workspace size is spelt _wsb_boot: see the class above; `params` is a HOST xvec_boot_params)
+    "xvec_boot_last_error": (C.c_char_p, []),
+    "xvec_boot_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32, _i32]),
+    "xvec_boot_batch": (C.c_int32, [_i64, _i32]),
+    "xvec_boot_batches": (C.c_int32, [_i64, _i32]),
+    "xvec_boot_trials": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.POINTER(BootParams), _vp, _vp, _vp, _wsb_boot, _vp]),
+    "xvec_boot_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.POINTER(BootParams), _vp, _vp, _vp, _wsb_boot, _vp]),
+    "xvec_boot_counts_host": (C.c_int, [C.c_uint64, _i32, _i32, _i32, C.POINTER(C.c_uint16)]),
+    "xvec_boot_poisson_host": (C.c_int, [C.c_uint64, _i32, _i64, C.POINTER(C.c_int32)]),
     # include/xvec_snorm.h
     "xvec_snorm_last_error": (C.c_char_p, []),
     "xvec_snorm_workspace_bytes": (C.c_size_t, [_i64, _i64]),
