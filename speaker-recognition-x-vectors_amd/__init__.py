@@ -19,7 +19,9 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "TrialReport", "trial_map", "score_range", "score_images", "det_curve", "det_curve_all_pairs", "trial_report", "vbx", "Vbx",
            "VbxModel", "VbxResult", "der", "DerResult", "read_rttm", "fuse", "Term", "Fusion", "FusionResult", "ScoreFuser", "fit_fusion",
            "fit_fusion_all_pairs", "log_duration_terms", "row_quality", "col_quality", "bootstrap", "BootstrapResult",
-           "BootstrapComparison", "bootstrap_trials", "bootstrap_all_pairs"]
+           "BootstrapComparison", "bootstrap_trials", "bootstrap_all_pairs", "analyze", "ScoreSummary", "ScoreHistogram", "HardestTrials",
+           "score_summary", "score_summary_all_pairs", "hardest_trials", "hardest_all_pairs", "confusable_pairs",
+           "compare_speaker_results"]
 
 
 def __getattr__(name):
@@ -81,6 +83,10 @@ def __getattr__(name):
     if name in ("BootstrapResult", "BootstrapComparison", "bootstrap_trials", "bootstrap_all_pairs"):
         import importlib
         return getattr(importlib.import_module(".bootstrap", __name__), name)
+    if name in ("ScoreSummary", "ScoreHistogram", "HardestTrials", "score_summary", "score_summary_all_pairs", "hardest_trials",
+                "hardest_all_pairs", "confusable_pairs", "compare_speaker_results"):
+        import importlib
+        return getattr(importlib.import_module(".analyze", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -88,7 +94,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der", "fuse", "bootstrap"):
+                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der", "fuse", "bootstrap", "analyze"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

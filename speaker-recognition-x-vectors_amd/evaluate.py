@@ -376,6 +376,16 @@ class plda_score_stat_object:
         self.min_dcf_ci = boot.interval("min_dcf", level)
         return boot
 
+    def analyze(self, k=200, bins=None):
+        """What extra/compare_speaker_results.py looks at, for the collected trials, on the device (analyze.score_summary and
+        analyze.hardest_trials): returns (ScoreSummary, HardestTrials) and keeps them as `score_summary` / `hardest`.  `bins`:
+        an analyze.Bins for the histograms of the rounded scores, or None.  Call test_plda first."""
+        from . import analyze as _analyze
+        s, trials = self._scored("analyze")
+        self.score_summary = _analyze.score_summary(s, trials, bins=bins)
+        self.hardest = _analyze.hardest_trials(s, trials, k=k)
+        return self.score_summary, self.hardest
+
     def _scored(self, what, thresholds=False):
         if self._trials is None:
             raise RuntimeError(f"{what}: call test_plda first")

@@ -129,6 +129,20 @@ class _wsb_boot(_wsb_fuse):
     own; the answers of these are held by tests/test_bootstrap.py."""
 
 
+class _wsb_analyze(_wsb_boot):
+    """size_t workspace_bytes of include/xvec_analyze.h: one more name.  tests/test_bootstrap.py lists every (void*, _wsb_boot)
+    pair of the table below as the bootstrap unit's own; the analysis unit's answers are held by tests/test_analyze.py."""
+
+
+class AnalyzeBins(C.Structure):                                 # xvec_analyze_bins
+    _fields_ = [("width", C.c_double), ("first", C.c_int64), ("n_bins", C.c_int32), ("rounding", C.c_int32),
+                ("hist_copies", C.c_int32), ("reserved", C.c_int32)]
+
+
+class AnalyzeSelect(C.Structure):                               # xvec_analyze_select
+    _fields_ = [("k", C.c_int32), ("cand_cap", C.c_int32)]
+
+
 class BootParams(C.Structure):                                  # xvec_boot_params
     _fields_ = [("row_group", C.c_void_p), ("col_group", C.c_void_p), ("n_row_groups", C.c_int32), ("n_col_groups", C.c_int32),
                 ("joint", C.c_int32), ("n_boot", C.c_int32), ("seed", C.c_uint64), ("c_miss", C.c_double), ("c_fa", C.c_double),
@@ -209,6 +223,19 @@ _SIGS = {
     "xvec_boot_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, C.POINTER(BootParams), _vp, _vp, _vp, _wsb_boot, _vp]),
     "xvec_boot_counts_host": (C.c_int, [C.c_uint64, _i32, _i32, _i32, C.POINTER(C.c_uint16)]),
     "xvec_boot_poisson_host": (C.c_int, [C.c_uint64, _i32, _i64, C.POINTER(C.c_int32)]),
+    # include/xvec_analyze.h  (`bins` and `select` are HOST structs; bins may be null)
+    "xvec_analyze_last_error": (C.c_char_p, []),
+    "xvec_analyze_plan_host": (C.c_int, [_i64, _i32, C.POINTER(C.c_int64)]),
+    "xvec_analyze_summary_workspace_bytes": (C.c_size_t, [_i64, _i32]),
+    "xvec_analyze_hardest_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),
+    "xvec_analyze_summary": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.POINTER(AnalyzeBins), _vp, _vp, _vp,
+                                       _wsb_analyze, _vp]),
+    "xvec_analyze_summary_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, C.POINTER(AnalyzeBins), _vp, _vp, _vp,
+                                                 _wsb_analyze, _vp]),
+    "xvec_analyze_hardest": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, C.POINTER(AnalyzeSelect), _vp, _vp, _vp, _vp,
+                                       _wsb_analyze, _vp]),
+    "xvec_analyze_hardest_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, C.POINTER(AnalyzeSelect), _vp, _vp, _vp,
+                                                 _vp, _wsb_analyze, _vp]),
     # include/xvec_snorm.h
     "xvec_snorm_last_error": (C.c_char_p, []),
     "xvec_snorm_workspace_bytes": (C.c_size_t, [_i64, _i64]),
