@@ -21,7 +21,8 @@ __all__ = ["synth", "XVectorModel", "TdnnLayer", "get_time_context", "MfccFrontE
            "fit_fusion_all_pairs", "log_duration_terms", "row_quality", "col_quality", "bootstrap", "BootstrapResult",
            "BootstrapComparison", "bootstrap_trials", "bootstrap_all_pairs", "analyze", "ScoreSummary", "ScoreHistogram", "HardestTrials",
            "score_summary", "score_summary_all_pairs", "hardest_trials", "hardest_all_pairs", "confusable_pairs",
-           "compare_speaker_results"]
+           "compare_speaker_results", "gmm", "DiagGmm", "GmmStats", "fit_ubm", "map_adapt", "linear_scores", "llr_scores",
+           "frames_of"]
 
 
 def __getattr__(name):
@@ -87,6 +88,9 @@ def __getattr__(name):
                 "hardest_all_pairs", "confusable_pairs", "compare_speaker_results"):
         import importlib
         return getattr(importlib.import_module(".analyze", __name__), name)
+    if name in ("DiagGmm", "GmmStats", "fit_ubm", "map_adapt", "linear_scores", "llr_scores", "frames_of"):
+        import importlib
+        return getattr(importlib.import_module(".gmm", __name__), name)
     if name in ("WaveAugmenter", "AugmentPlan"):
         from . import augment
         return getattr(augment, name)
@@ -94,7 +98,7 @@ def __getattr__(name):
         from . import train
         return getattr(train, name)
     if name in ("hip", "model", "extract", "frontend", "scoring", "plda", "evaluate", "augment", "train", "snorm", "lda", "resample", "identify",
-                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der", "fuse", "bootstrap", "analyze"):
+                "diarize", "vad", "visualize", "calibrate", "report", "vbx", "der", "fuse", "bootstrap", "analyze", "gmm"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -36,6 +36,7 @@ IDENT_X_F32, IDENT_X_F64 = 0, 1                                 # XVEC_IDENT_X_*
 EMBED_MAX_DIM, EMBED_ROW_GROUP = 65536, 64                      # XVEC_EMBED_*
 AUG_POOL_F32, AUG_POOL_I16 = 0, 1                               # XVEC_AUG_POOL_*
 TSNE_X_F32, TSNE_X_F64 = 0, 1                                   # XVEC_TSNE_X_*
+GMM_X_F32, GMM_X_F64 = 0, 1                                     # XVEC_GMM_X_*
 MODE_LOGITS, MODE_POOLED, MODE_XVEC6, MODE_XVEC7 = 0, 5, 6, 7
 SEG6, SEG7, OUTPUT = 6, 7, 8
 KERNEL_NAMES = {0: None, 1: "tile128", 2: "pp", 3: "first"}      # XVEC_KERNEL_*
@@ -132,6 +133,20 @@ class _wsb_boot(_wsb_fuse):
 class _wsb_analyze(_wsb_boot):
     """size_t workspace_bytes of include/xvec_analyze.h: one more name.  tests/test_bootstrap.py lists every (void*, _wsb_boot)
     pair of the table below as the bootstrap unit's own; the analysis unit's answers are held by tests/test_analyze.py."""
+
+
+class _wsb_gmm(_wsb_analyze):
+    """size_t workspace_bytes of include/xvec_gmm.h: one more name.  tests/test_analyze.py lists every (void*, _wsb_analyze)
+    pair of the table below as the analysis unit's own; the GMM unit's answers are held by tests/test_gmm.py."""
+
+
+class GmmFrames(C.Structure):                                   # xvec_gmm_frames (utt_first / utt_count are HOST arrays)
+    _fields_ = [("x", C.c_void_p), ("x_type", C.c_int32), ("reserved", C.c_int32), ("rows", C.c_int64), ("ldx", C.c_int64),
+                ("utt_first", C.POINTER(C.c_int64)), ("utt_count", C.POINTER(C.c_int64)), ("n_utts", C.c_int64)]
+
+
+class GmmMstepOptions(C.Structure):                             # xvec_gmm_mstep_options
+    _fields_ = [("reg_covar", C.c_double), ("var_floor", C.c_double), ("min_count", C.c_double)]
 
 
 class AnalyzeBins(C.Structure):                                 # xvec_analyze_bins
@@ -236,6 +251,22 @@ _SIGS = {
                                        _wsb_analyze, _vp]),
     "xvec_analyze_hardest_all_pairs": (C.c_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i32, _i32, C.POINTER(AnalyzeSelect), _vp, _vp, _vp,
                                                  _vp, _wsb_analyze, _vp]),
+    # include/xvec_gmm.h  (`frames` and `options` are HOST structs)
+    "xvec_gmm_last_error": (C.c_char_p, []),
+    "xvec_gmm_plan_host": (C.c_int, [_i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64)]),
+    "xvec_gmm_loglik_workspace_bytes": (C.c_size_t, [_i64, _i32, _i32]),
+    "xvec_gmm_accumulate_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "xvec_gmm_em_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32, _i32, _i32]),
+    "xvec_gmm_linear_scores_workspace_bytes": (C.c_size_t, [_i64, _i64, _i32, _i32]),
+    "xvec_gmm_prepare": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    "xvec_gmm_loglik": (C.c_int, [C.POINTER(GmmFrames), _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _wsb_gmm, _vp]),
+    "xvec_gmm_accumulate": (C.c_int, [C.POINTER(GmmFrames), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _wsb_gmm, _vp]),
+    "xvec_gmm_mstep": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, C.POINTER(GmmMstepOptions), _vp, _vp, _vp, _vp]),
+    "xvec_gmm_em": (C.c_int, [C.POINTER(GmmFrames), _i32, _i32, _i32, C.c_double, C.POINTER(GmmMstepOptions), _i32, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _wsb_gmm, _vp]),
+    "xvec_gmm_map_means": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, C.c_double, _vp, _vp]),
+    "xvec_gmm_linear_scores": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _i64, _vp, _wsb_gmm, _vp]),
     # include/xvec_snorm.h
     "xvec_snorm_last_error": (C.c_char_p, []),
     "xvec_snorm_workspace_bytes": (C.c_size_t, [_i64, _i64]),
